@@ -107,9 +107,18 @@ def parse():
     ap.add_argument("--sweep", action="store_true", help="print the whole recall/QPS sweep to stderr")
     ap.add_argument("--query-sets", type=int, default=4,
                     help="distinct query sets of --nq queries each; timed step i searches set i %% query_sets")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (ids, distances, per-query "
+                         "stats) as DIR/<name>.npy (float64; a fixed, seeded sample of rows beyond 64 MB)")
     if len(sys.argv) == 1 and os.environ.get("DANN_BENCH_ARGV"):  # a rank spawned by maybe_spawn()
-        return ap.parse_args(json.loads(os.environ["DANN_BENCH_ARGV"]))
-    return ap.parse_args()
+        args = ap.parse_args(json.loads(os.environ["DANN_BENCH_ARGV"]))
+    else:
+        args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.only or args.only_large):
+        ap.error("--dump-outputs covers the headline workload only (not --only / --only-large)")
+    return args
 
 
 def log(*a):
@@ -394,6 +403,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - tstart
     kernel_ms, launches = prov.kernel_time(0)
+    if args.dump_outputs and args.scaling == "weak":  # (untimed) the last timed step's results, before any leg reuses the buffers
+        dump_outputs(args.dump_outputs, d_ids, d_dists, d_stats, rank, world)
     per_rank_qps = [args.nq * args.steps / elapsed]
     if world > 1:
         cdev = torch.device("cpu") if one_dev else dev
@@ -429,6 +440,8 @@ def main():
         run_shared()
     barrier()
     strong_elapsed = time.perf_counter() - ts
+    if args.dump_outputs and args.scaling == "strong":  # this rank's block of the shared set
+        dump_outputs(args.dump_outputs, s_ids[:hi - lo], s_d[:hi - lo], s_st[:hi - lo], rank, world)
     if world > 1:
         t = torch.tensor([strong_elapsed], device=torch.device("cpu") if one_dev else dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -793,6 +806,31 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, ids, dists, stats, rank, world):
+    """--dump-outputs: what a caller of dann_search_batch_device receives -- ids (uint32), distances (f32) and the
+    per-query stats (cmps, hops, result_count, status, written) -- as DIR/<name>.npy, ids and stats widened to float64
+    (exact), distances kept as float32.  Beyond 64 MB in all (over every rank) a fixed, seeded sample of query rows is
+    written instead, with the row numbers in DIR/query_rows.npy."""
+    arrays = {"ids": ids.cpu().numpy().view(np.uint32).astype(np.float64),
+              "distances": dists.cpu().numpy().astype(np.float32),
+              "stats": stats.cpu().numpy().view(np.uint32).astype(np.float64)}
+    nrows = arrays["ids"].shape[0]
+    per_row = sum(a[:1].nbytes for a in arrays.values())
+    limit = DUMP_LIMIT_BYTES // max(world, 1)
+    if nrows * per_row > limit:
+        m = (limit - 4096) // (per_row + 8)  # (4 KiB for the .npy headers; 8 B per row for query_rows)
+        rows = np.sort(np.random.default_rng(0xD15CD0).choice(nrows, m, replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["query_rows"] = rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + suffix + ".npy"), np.ascontiguousarray(a))
 
 
 def family_of(before, after):

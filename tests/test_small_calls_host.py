@@ -7,6 +7,8 @@ side by side, a failed launch reaches every call in it and none outside, a decli
 general path, more threads than the polling budget (the nap path) -- and ThreadSanitizer sees no data race in any of it.
 The GPU side: tests/test_gpu_server.py::test_small_host_calls_of_many_threads_share_launches."""
 import os
+import platform
+import shutil
 import subprocess
 
 import pytest
@@ -151,15 +153,19 @@ def harness(tmp_path_factory):
     return exes
 
 
-def _run(exe, *args, timeout=600):
-    r = subprocess.run([exe, *map(str, args)], capture_output=True, text=True, timeout=timeout)
+def _run(exe, *args, timeout=600, no_aslr=False):
+    # ThreadSanitizer's shadow layout does not cover every address a kernel with high mmap randomisation
+    # (vm.mmap_rnd_bits = 32) may hand out ("FATAL: ThreadSanitizer: unexpected memory mapping"): the sanitized
+    # harness runs with address randomisation off for its own process only
+    pre = [shutil.which("setarch"), platform.machine(), "-R"] if no_aslr and shutil.which("setarch") else []
+    r = subprocess.run([*pre, exe, *map(str, args)], capture_output=True, text=True, timeout=timeout)
     fields = dict(kv.split("=") for kv in r.stdout.split()) if r.stdout.strip() else {}
     return r, {k: int(v) for k, v in fields.items()}
 
 
 @pytest.mark.parametrize("threads,rounds,us,poison", [(8, 150, 60, 0), (24, 60, 80, 0), (6, 150, 40, 9)])
 def test_combiner_under_thread_sanitizer(harness, threads, rounds, us, poison):
-    r, f = _run(harness["tsan"], threads, rounds, us, poison)
+    r, f = _run(harness["tsan"], threads, rounds, us, poison, no_aslr=True)
     assert "ThreadSanitizer" not in r.stderr, r.stderr[:4000]
     assert r.returncode == 0, (r.stdout, r.stderr[:2000])
     assert f["bad"] == 0 and f["calls"] == threads * rounds and f["launches"] <= f["calls"]
