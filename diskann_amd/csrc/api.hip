@@ -2,7 +2,6 @@
 // staging and kernel dispatch.  No CPU fallback exists anywhere in this library: every
 // distance, search and prune result comes from a HIP kernel, and a missing/failed device
 // surfaces as DANN_EHIP.
-#include <sched.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -10,13 +9,9 @@
 #include <time.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <map>
-#include <memory>
 #include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "dann_device.h"
@@ -53,18 +48,6 @@ struct DevBuf {
     template <class T>
     T* as() {
         return reinterpret_cast<T*>(p);
-    }
-};
-
-struct DeviceGuard {
-    int prev = -1, cur = -1;
-    bool ok = true;
-    explicit DeviceGuard(int dev) : cur(dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0 && prev != cur) (void)hipSetDevice(prev);  // hipSetDevice costs ~0.5 ms on ROCm 7.2
     }
 };
 
@@ -114,18 +97,14 @@ int32_t SearchCtx::init() {
 
 void SearchCtx::destroy() {
     if (stream) (void)hipStreamSynchronize(stream);
-    if (copy_stream) (void)hipStreamSynchronize(copy_stream);
     if (d_fail) (void)hipFree(d_fail);
     if (h_flag) (void)hipHostFree(h_flag);
     if (d_spill) (void)hipFree(d_spill);
     for (void* p : stage)
         if (p) (void)hipFree(p);
     if (h_stage) (void)hipHostFree(h_stage);
-    for (hipEvent_t e : chunk_ev)
-        if (e) (void)hipEventDestroy(e);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
-    if (copy_stream) (void)hipStreamDestroy(copy_stream);
     if (stream) (void)hipStreamDestroy(stream);
     *this = SearchCtx();
 }
@@ -179,6 +158,92 @@ uint32_t auto_visited_entries(const dann_index* idx, uint32_t, uint32_t) {
     return 0;  // sized per launch by search_with_retry (search_kernels.hip)
 }
 
+// ---- search --------------------------------------------------------------------------------
+static int32_t pq_ready(const dann_index* idx) {
+    if (idx->cfg.dtype == DT_PQ && (!idx->d_pq_pivots || !idx->d_pq_offsets)) {
+        set_error("DANN_PQ index has no pivot table: call dann_set_pq_table first");
+        return DANN_EINVAL;
+    }
+    return DANN_OK;
+}
+
+int32_t search_device(dann_index* idx, SearchCtx& ctx, const void* d_queries, const uint32_t* d_qslots, uint32_t nq,
+                      uint32_t l_value, uint32_t beam, uint32_t k, uint32_t* d_ids, float* d_dists,
+                      dann_search_stats* d_stats, uint32_t* d_rec_ids, float* d_rec_d, uint32_t rec_stride,
+                      uint32_t* d_rec_n) {
+    if (int32_t prc = pq_ready(idx)) return prc;
+    if (idx->cfg.dtype == DT_PQ && d_qslots) {
+        set_error("insert-time search (query = stored row) is not defined for DANN_PQ");
+        return DANN_EUNSUPPORTED;
+    }
+    SearchArgs a;
+    a.ix = idx->view();
+    a.queries = d_queries;
+    a.qslots = d_qslots;
+    a.nq = nq;
+    a.l_value = l_value;
+    a.beam_width = beam;
+    a.k = k;
+    a.ht_entries = auto_visited_entries(idx, l_value, beam);
+    a.out_ids = d_ids;
+    a.out_dists = d_dists;
+    a.stats = d_stats;
+    a.rec_ids = d_rec_ids;
+    a.rec_dists = d_rec_d;
+    a.rec_stride = rec_stride;
+    a.rec_n = d_rec_n;
+    a.qmap = nullptr;
+    a.range_ids = nullptr;
+    a.range_d = nullptr;
+    a.range_second = nullptr;
+    a.range_cap = a.range_max = a.range_thresh = a.has_inner = 0;
+    a.radius = a.inner_radius = a.range_slack = 0.0f;
+    a.fail_flag = nullptr;
+    a.spill = nullptr;
+    a.spill_next = nullptr;
+    a.spill_slices = a.spill_bits = 0;
+    return search_with_retry(idx, ctx, a);
+}
+
+// shared access for the Knn search entry points: the index is read-only here, every call runs on its own context
+#define CHECK_IDX_SHARED(idx)                               \
+    if (!(idx)) {                                           \
+        set_error("null index");                            \
+        return DANN_EINVAL;                                 \
+    }                                                       \
+    std::shared_lock<std::shared_mutex> _rd((idx)->rw);     \
+    DeviceGuard _guard((idx)->device);                      \
+    CtxLease _lease(idx);                                   \
+    if (_lease.status != DANN_OK) return _lease.status;     \
+    SearchCtx& ctx = *_lease.ctx
+
+int32_t grow_stage(SearchCtx& ctx, int i, size_t need) {
+    if (ctx.stage_bytes[i] >= need) return DANN_OK;
+    if (ctx.stage[i]) (void)hipFree(ctx.stage[i]);
+    ctx.stage[i] = nullptr;
+    ctx.stage_bytes[i] = 0;
+    const size_t sz = need + need / 4;
+    DANN_HIP(hipMalloc(&ctx.stage[i], sz));
+    ctx.stage_bytes[i] = sz;
+    return DANN_OK;
+}
+
+// The scratch arena of the range / filtered searches (stage[4]) stays resident between calls only up to this size: a
+// call with per-query filter bitmaps on a large index can need gigabytes, and an index that nearly fills HBM would
+// miss them in its next build or search (the pool keeps up to 16 contexts).  Beyond it the block is released when the
+// call returns (a hipFree synchronises the device: the price of a call that large, not of every call).
+constexpr size_t kArenaKeepBytes = (size_t)256 << 20;
+struct ArenaTrim {
+    SearchCtx& ctx;
+    ~ArenaTrim() {
+        if (ctx.stage_bytes[4] > kArenaKeepBytes) {
+            (void)hipStreamSynchronize(ctx.stream);
+            (void)hipFree(ctx.stage[4]);
+            ctx.stage[4] = nullptr;
+            ctx.stage_bytes[4] = 0;
+        }
+    }
+};
 }  // namespace dann
 
 using namespace dann;
@@ -870,93 +935,6 @@ int32_t dann_expand_beam_batch(const dann_index* cidx, const void* queries, uint
     return DANN_OK;
 } DANN_CATCH_ALL
 
-// ---- search --------------------------------------------------------------------------------
-static int32_t pq_ready(const dann_index* idx) {
-    if (idx->cfg.dtype == DT_PQ && (!idx->d_pq_pivots || !idx->d_pq_offsets)) {
-        set_error("DANN_PQ index has no pivot table: call dann_set_pq_table first");
-        return DANN_EINVAL;
-    }
-    return DANN_OK;
-}
-
-static int32_t search_device(dann_index* idx, SearchCtx& ctx, const void* d_queries, const uint32_t* d_qslots, uint32_t nq,
-                             uint32_t l_value, uint32_t beam, uint32_t k, uint32_t* d_ids, float* d_dists,
-                             dann_search_stats* d_stats, uint32_t* d_rec_ids, float* d_rec_d, uint32_t rec_stride,
-                             uint32_t* d_rec_n) {
-    if (int32_t prc = pq_ready(idx)) return prc;
-    if (idx->cfg.dtype == DT_PQ && d_qslots) {
-        set_error("insert-time search (query = stored row) is not defined for DANN_PQ");
-        return DANN_EUNSUPPORTED;
-    }
-    SearchArgs a;
-    a.ix = idx->view();
-    a.queries = d_queries;
-    a.qslots = d_qslots;
-    a.nq = nq;
-    a.l_value = l_value;
-    a.beam_width = beam;
-    a.k = k;
-    a.ht_entries = auto_visited_entries(idx, l_value, beam);
-    a.out_ids = d_ids;
-    a.out_dists = d_dists;
-    a.stats = d_stats;
-    a.rec_ids = d_rec_ids;
-    a.rec_dists = d_rec_d;
-    a.rec_stride = rec_stride;
-    a.rec_n = d_rec_n;
-    a.qmap = nullptr;
-    a.range_ids = nullptr;
-    a.range_d = nullptr;
-    a.range_second = nullptr;
-    a.range_cap = a.range_max = a.range_thresh = a.has_inner = 0;
-    a.radius = a.inner_radius = a.range_slack = 0.0f;
-    a.fail_flag = nullptr;
-    a.spill = nullptr;
-    a.spill_next = nullptr;
-    a.spill_slices = a.spill_bits = 0;
-    return search_with_retry(idx, ctx, a);
-}
-
-// shared access for the Knn search entry points: the index is read-only here, every call runs on its own context
-#define CHECK_IDX_SHARED(idx)                               \
-    if (!(idx)) {                                           \
-        set_error("null index");                            \
-        return DANN_EINVAL;                                 \
-    }                                                       \
-    std::shared_lock<std::shared_mutex> _rd((idx)->rw);     \
-    DeviceGuard _guard((idx)->device);                      \
-    CtxLease _lease(idx);                                   \
-    if (_lease.status != DANN_OK) return _lease.status;     \
-    SearchCtx& ctx = *_lease.ctx
-
-static int32_t grow_stage(SearchCtx& ctx, int i, size_t need) {
-    if (ctx.stage_bytes[i] >= need) return DANN_OK;
-    if (ctx.stage[i]) (void)hipFree(ctx.stage[i]);
-    ctx.stage[i] = nullptr;
-    ctx.stage_bytes[i] = 0;
-    const size_t sz = need + need / 4;
-    DANN_HIP(hipMalloc(&ctx.stage[i], sz));
-    ctx.stage_bytes[i] = sz;
-    return DANN_OK;
-}
-
-// The scratch arena of the range / filtered searches (stage[4]) stays resident between calls only up to this size: a
-// call with per-query filter bitmaps on a large index can need gigabytes, and an index that nearly fills HBM would
-// miss them in its next build or search (the pool keeps up to 16 contexts).  Beyond it the block is released when the
-// call returns (a hipFree synchronises the device: the price of a call that large, not of every call).
-constexpr size_t kArenaKeepBytes = (size_t)256 << 20;
-struct ArenaTrim {
-    SearchCtx& ctx;
-    ~ArenaTrim() {
-        if (ctx.stage_bytes[4] > kArenaKeepBytes) {
-            (void)hipStreamSynchronize(ctx.stream);
-            (void)hipFree(ctx.stage[4]);
-            ctx.stage[4] = nullptr;
-            ctx.stage_bytes[4] = 0;
-        }
-    }
-};
-
 int32_t dann_search_batch_device(dann_index* idx, const void* d_queries, uint32_t nq, uint32_t l_value,
                                  uint32_t beam_width, uint32_t k, uint32_t* d_out_ids, float* d_out_dists,
                                  dann_search_stats* d_out_stats) try {
@@ -969,488 +947,6 @@ int32_t dann_search_batch_device(dann_index* idx, const void* d_queries, uint32_
     }
     return search_device(idx, ctx, d_queries, nullptr, nq, l_value, beam_width, k, d_out_ids, d_out_dists, d_out_stats,
                          nullptr, nullptr, 0, nullptr);
-} DANN_CATCH_ALL
-
-static int32_t first_failed_query(const dann_search_stats* stats, uint32_t nq, uint32_t base) {
-    for (uint32_t i = 0; i < nq; ++i) {
-        if (stats[i].status == (uint32_t)(-DANN_EINVAL)) {
-            set_error("query %u: could not retrieve start point (a start slot is not readable)", base + i);
-            return DANN_EINVAL;
-        }
-        if (stats[i].status) {
-            set_error("query %u: per-query scratch exhausted (visited table and spill pool); raise the table "
-                      "size with dann_set_visited_bits", base + i);
-            return DANN_EOVERFLOW;
-        }
-    }
-    return DANN_OK;
-}
-
-// ---- small host-pointer calls: one launch for all callers that are waiting (the queue and the leadership: small_calls.h)
-extern "C++" {
-namespace {
-void grab_error_text(std::string& t) {
-    char buf[512];
-    buf[0] = 0;
-    dann_last_error(buf, sizeof buf);
-    t = buf;
-}
-// one launch for `n` calls (same L, beam, k; `total` queries).  Returns kSmallCallDeclined if the staging cannot be
-// mapped (the calls then take the general path one by one).
-int32_t small_batch_run(dann_index* idx, SmallCall* const* calls, uint32_t n, uint32_t total, size_t qb) {
-    CtxLease lease(idx);
-    if (lease.status != DANN_OK) return lease.status;
-    SearchCtx& ctx = *lease.ctx;
-    if (ctx.h_stage_bytes < kSmallStage) {
-        if (ctx.h_stage) (void)hipHostFree(ctx.h_stage);
-        ctx.h_stage = nullptr;
-        ctx.h_stage_bytes = 0;
-        DANN_HIP(hipHostMalloc(&ctx.h_stage, kSmallStage, hipHostMallocMapped));
-        ctx.h_stage_bytes = kSmallStage;
-    }
-    void* dbase = nullptr;
-    if (hipHostGetDevicePointer(&dbase, ctx.h_stage, 0) != hipSuccess) {
-        // (a block another path of this context allocated without the mapping: once more, mapped)
-        (void)hipGetLastError();
-        (void)hipHostFree(ctx.h_stage);
-        ctx.h_stage = nullptr;
-        ctx.h_stage_bytes = 0;
-        DANN_HIP(hipHostMalloc(&ctx.h_stage, kSmallStage, hipHostMallocMapped));
-        ctx.h_stage_bytes = kSmallStage;
-        if (hipHostGetDevicePointer(&dbase, ctx.h_stage, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            return kSmallCallDeclined;
-        }
-    }
-    const uint32_t k = calls[0]->k;
-    const size_t in_b = ((size_t)total * qb + 15) & ~(size_t)15, ids_b = ((size_t)total * k * 4 + 15) & ~(size_t)15;
-    uint8_t* const h = reinterpret_cast<uint8_t*>(ctx.h_stage);
-    uint8_t* const d = reinterpret_cast<uint8_t*>(dbase);
-    size_t off = 0;
-    for (uint32_t c = 0; c < n; ++c) {
-        memcpy(h + off, calls[c]->queries, (size_t)calls[c]->nq * qb);
-        off += (size_t)calls[c]->nq * qb;
-    }
-    // row types whose kernels read a query more than once (PQ: the table build; SQ-8: the compensation) get the queries
-    // in device memory: one copy for the whole group of calls; the results still land in the mapped block
-    const int dt = idx->cfg.dtype;
-    const void* dq = d;
-    if (!(dt == DT_F32 || dt == DT_F16 || dt == DT_U8 || dt == DT_I8)) {
-        if (int32_t grc = grow_stage(ctx, 0, in_b + 16)) return grc;
-        DANN_HIP(hipMemcpyAsync(ctx.stage[0], h, (size_t)total * qb, hipMemcpyHostToDevice, ctx.stream));
-        dq = ctx.stage[0];
-    }
-    int32_t rc = search_device(idx, ctx, dq, nullptr, total, calls[0]->l_value, calls[0]->beam, k,
-                               reinterpret_cast<uint32_t*>(d + in_b), reinterpret_cast<float*>(d + in_b + ids_b),
-                               reinterpret_cast<dann_search_stats*>(d + in_b + 2 * ids_b), nullptr, nullptr, 0, nullptr);
-    if (rc != DANN_OK) return rc;
-    DANN_HIP(hipStreamSynchronize(ctx.stream));
-    const uint32_t* ri = reinterpret_cast<const uint32_t*>(h + in_b);
-    const float* rd = reinterpret_cast<const float*>(h + in_b + ids_b);
-    const dann_search_stats* rs = reinterpret_cast<const dann_search_stats*>(h + in_b + 2 * ids_b);
-    uint32_t q0 = 0;
-    for (uint32_t c = 0; c < n; ++c) {
-        SmallCall& r = *calls[c];
-        memcpy(r.out_ids, ri + (size_t)q0 * k, (size_t)r.nq * k * 4);
-        memcpy(r.out_dists, rd + (size_t)q0 * k, (size_t)r.nq * k * 4);
-        if (r.out_stats) memcpy(r.out_stats, rs + q0, (size_t)r.nq * sizeof(dann_search_stats));
-        r.rc = first_failed_query(rs + q0, r.nq, 0);
-        if (r.rc != DANN_OK) grab_error_text(r.text);
-        q0 += r.nq;
-    }
-    return DANN_OK;
-}
-}  // namespace
-}  // extern "C++"
-
-// queries per chunk of the host-pointer pipeline, and the batch size from which it is used
-constexpr uint32_t kHostChunk = 16384;
-
-extern "C++" {
-namespace {
-// is [p, p + bytes) page-locked host memory the device can reach by DMA (hipHostMalloc / hipHostRegister)?  Then the
-// pipeline copies straight from / to it; pageable buffers travel through the context's pinned ring.
-bool host_pinned(const void* p, size_t bytes) {
-    if (!p || !bytes) return false;
-    hipPointerAttribute_t at;
-    for (const void* q : {p, (const void*)(reinterpret_cast<const uint8_t*>(p) + bytes - 1)}) {
-        if (hipPointerGetAttributes(&at, q) != hipSuccess) {
-            (void)hipGetLastError();  // (a pageable pointer is an "invalid value" to the runtime: not an error of this call)
-            return false;
-        }
-        if (at.type != hipMemoryTypeHost) return false;
-    }
-    return true;
-}
-
-// Page-locking a caller's pageable buffer for the duration of one call (hipHostRegister, mapped): on this runtime the
-// first registration of a range costs ~65 us per MB (3.3 ms for the 51 MB of 100 000 f32 queries), registering the same
-// range again ~1 us (scratch/probe_host_register.hip) -- a caller that reuses its buffers from call to call, as a
-// serving loop does, can be given the zero-copy launch of page-locked memory at no cost from its second call on.
-// Several threads may pass one buffer (a shared query block) at the same time: temporary registrations are counted in a
-// process-wide table, the last user unregisters.
-struct TempPins {
-    std::mutex mu;
-    std::map<const void*, std::pair<size_t, uint32_t>> live;  // base -> (bytes, users)
-    bool acquire(const void* p, size_t bytes) {
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = live.find(p);
-        if (it != live.end()) {
-            if (it->second.first < bytes) return false;  // (registered shorter by another caller: not worth untangling)
-            ++it->second.second;
-            return true;
-        }
-        if (hipHostRegister(const_cast<void*>(p), bytes, hipHostRegisterMapped) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        live.emplace(p, std::make_pair(bytes, 1u));
-        return true;
-    }
-    void release(const void* p) {
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = live.find(p);
-        if (it == live.end()) return;
-        if (--it->second.second == 0) {
-            (void)hipHostUnregister(const_cast<void*>(p));
-            live.erase(it);
-        }
-    }
-    // page-locked by the CALLER (stable for the call), not by another thread's temporary registration -- decided under the
-    // table's lock: a release on another thread unregisters and erases inside it, so the answer is never "pinned, not ours"
-    // for memory that is about to lose its pin
-    bool caller_pinned(const void* p, size_t bytes) {
-        std::lock_guard<std::mutex> lk(mu);
-        return live.count(p) == 0 && host_pinned(p, bytes);
-    }
-};
-TempPins& temp_pins() {
-    static TempPins t;
-    return t;
-}
-// the set of temporary registrations of one call; everything acquired is released when it goes out of scope
-struct PinScope {
-    const void* held[4] = {nullptr, nullptr, nullptr, nullptr};
-    int n = 0;
-    bool add(const void* p, size_t bytes) {
-        if (!temp_pins().acquire(p, bytes)) return false;
-        held[n++] = p;
-        return true;
-    }
-    ~PinScope() {
-        for (int i = 0; i < n; ++i) temp_pins().release(held[i]);
-    }
-};
-}  // namespace
-}  // extern "C++"
-
-int32_t dann_search_batch(dann_index* idx, const void* queries, uint32_t nq, uint32_t l_value, uint32_t beam_width,
-                          uint32_t k, uint32_t* out_ids, float* out_dists, dann_search_stats* out_stats) try {
-    if (!idx) {
-        set_error("null index");
-        return DANN_EINVAL;
-    }
-    std::shared_lock<std::shared_mutex> _rd(idx->rw);
-    DeviceGuard _guard(idx->device);
-    if (nq == 0) return DANN_OK;
-    if (!queries || !out_ids || !out_dists) return DANN_EINVAL;
-    const size_t qb = idx->cfg.dtype == DT_PQ ? (size_t)idx->cfg.dim * 4 : idx->layer_bytes;  // PQ: f32 queries
-    const uint32_t pipeline_dbg = idx->dbg_u32(DANN_DBG_HOST_PIPELINE, 1u);  // 0 off, 1 default, 2 .. 8 lanes
-    {   // a small call: one launch reading and writing mapped host memory, shared with the small calls of other threads
-        if (pipeline_dbg == 1u && nq <= kSmallCall && small_call_bytes(nq, qb, k) <= kSmallStage / 4) {
-            SmallCall me;
-            me.queries = queries;
-            me.nq = nq;
-            me.l_value = l_value;
-            me.beam = beam_width;
-            me.k = k;
-            me.out_ids = out_ids;
-            me.out_dists = out_dists;
-            me.out_stats = out_stats;
-            const int32_t src = small_call(idx->comb, me, qb, [&](SmallCall* const* calls, uint32_t n, uint32_t total, std::string& text) {
-                const int32_t rrc = small_batch_run(idx, calls, n, total, qb);
-                if (rrc != DANN_OK && rrc != kSmallCallDeclined) grab_error_text(text);
-                return rrc;
-            });
-            if (src != DANN_OK && src != kSmallCallDeclined && !me.text.empty()) set_error("%s", me.text.c_str());
-            if (src != kSmallCallDeclined) return src;
-        }
-    }
-    CtxLease _lease(idx);
-    if (_lease.status != DANN_OK) return _lease.status;
-    SearchCtx& ctx = *_lease.ctx;
-    const bool pipeline_off = pipeline_dbg == 0u;
-    const uint32_t host_chunk = std::max<uint32_t>(idx->dbg_u32(DANN_DBG_HOST_CHUNK, kHostChunk), 256u);
-    const bool chunked = nq >= 2 * host_chunk && !pipeline_off;
-    const uint32_t cq = chunked ? host_chunk : nq;  // queries per device pass
-    // device staging owned by the context (grow-only): [0] queries, [1] ids | dists | stats in one block (the chunked form:
-    // one of each per lane, in the lane's own context)
-    const size_t ids_b = ((size_t)cq * k * 4 + 15) & ~(size_t)15, st_b = ((size_t)cq * sizeof(dann_search_stats) + 15) & ~(size_t)15;
-    const size_t in_b = (size_t)cq * qb, out_b = 2 * ids_b + st_b;
-    if (!chunked) {
-        if (int32_t rc = grow_stage(ctx, 0, in_b + 16)) return rc;
-        if (int32_t rc = grow_stage(ctx, 1, out_b + 16)) return rc;
-    }
-    // pinned host staging: copies from / to pageable memory are neither asynchronous nor fast on ROCm 7.2
-    const bool pinned = !chunked && in_b + out_b <= (1u << 20);
-    const size_t h_need = (size_t)1 << 20;
-    if (pinned && ctx.h_stage_bytes < h_need) {
-        if (ctx.h_stage) (void)hipHostFree(ctx.h_stage);
-        ctx.h_stage = nullptr;
-        ctx.h_stage_bytes = 0;
-        DANN_HIP(hipHostMalloc(&ctx.h_stage, h_need, hipHostMallocMapped));
-        ctx.h_stage_bytes = h_need;
-    }
-    if (!chunked) {
-        void* bq = ctx.stage[0];
-        uint8_t* ob = reinterpret_cast<uint8_t*>(ctx.stage[1]);
-        uint32_t* bi = reinterpret_cast<uint32_t*>(ob);
-        float* bd = reinterpret_cast<float*>(ob + ids_b);
-        dann_search_stats* bs = reinterpret_cast<dann_search_stats*>(ob + 2 * ids_b);
-        std::vector<dann_search_stats> stats(nq);
-        if (pinned) {
-            uint8_t* hs = reinterpret_cast<uint8_t*>(ctx.h_stage);
-            memcpy(hs, queries, in_b);
-            DANN_HIP(hipMemcpyAsync(bq, hs, in_b, hipMemcpyHostToDevice, ctx.stream));
-            int32_t rc = search_device(idx, ctx, bq, nullptr, nq, l_value, beam_width, k, bi, bd, bs, nullptr, nullptr, 0, nullptr);
-            if (rc != DANN_OK) return rc;
-            DANN_HIP(hipMemcpyAsync(hs + in_b, ob, out_b, hipMemcpyDeviceToHost, ctx.stream));
-            DANN_HIP(hipStreamSynchronize(ctx.stream));
-            memcpy(out_ids, hs + in_b, (size_t)nq * k * 4);
-            memcpy(out_dists, hs + in_b + ids_b, (size_t)nq * k * 4);
-            memcpy(stats.data(), hs + in_b + 2 * ids_b, (size_t)nq * sizeof(dann_search_stats));
-        } else {
-            DANN_HIP(hipMemcpyAsync(bq, queries, in_b, hipMemcpyHostToDevice, ctx.stream));
-            int32_t rc = search_device(idx, ctx, bq, nullptr, nq, l_value, beam_width, k, bi, bd, bs, nullptr, nullptr, 0, nullptr);
-            if (rc != DANN_OK) return rc;
-            DANN_HIP(hipMemcpyAsync(out_ids, bi, (size_t)nq * k * 4, hipMemcpyDeviceToHost, ctx.stream));
-            DANN_HIP(hipMemcpyAsync(out_dists, bd, (size_t)nq * k * 4, hipMemcpyDeviceToHost, ctx.stream));
-            DANN_HIP(hipMemcpyAsync(stats.data(), bs, (size_t)nq * sizeof(dann_search_stats), hipMemcpyDeviceToHost, ctx.stream));
-            DANN_HIP(hipStreamSynchronize(ctx.stream));
-        }
-        if (out_stats) memcpy(out_stats, stats.data(), (size_t)nq * sizeof(dann_search_stats));
-        return first_failed_query(stats.data(), nq, 0);
-    }
-    // ---- chunked pipeline: up to three lanes -- the calling thread and two helpers, each with a search context (stream,
-    // device staging, pinned ring slot) of its own -- take the chunks round robin; a lane runs copy in, kernel, copy out
-    // of its chunk back to back on its stream, and the lanes overlap one another: while one lane's kernel drains (the
-    // last queries of a batch leave most of the chip idle) or its host thread copies between the caller's pageable
-    // buffers and the ring, another lane's kernel has the chip.  Rounds 3-5 ran the chunks' kernels one after the other
-    // with the calling thread's copies between them (11.7 M QPS on 100 000 queries where the device-resident call does
-    // 18.6 M).  Buffers the caller page-locked (hipHostMalloc / hipHostRegister) need no ring: the DMA reads and writes
-    // them directly.
-    // (a buffer page-locked by another thread of this process for the length of ITS call -- temp_pins -- is pageable to us)
-    const bool q_direct = temp_pins().caller_pinned(queries, (size_t)nq * qb);
-    const bool o_direct = temp_pins().caller_pinned(out_ids, (size_t)nq * k * 4) &&
-                          temp_pins().caller_pinned(out_dists, (size_t)nq * k * 4);
-    int dev = 0;
-    DANN_HIP(hipGetDevice(&dev));
-    // ---- no copies at all: page-locked, device-mapped caller buffers are read and written by the search kernel itself
-    // (a query is read once, when its wavefront stages it; 51 MB in and 8 MB out over the 5 ms of a 100 000-query launch
-    // are a fifth of what the link carries).  One launch for the whole batch -- the chunked lanes below pay for their
-    // smaller launches (the last queries of every chunk leave the chip half idle).  Row types whose kernels read the
-    // query more than once (PQ: the table build; SQ-8: the compensation) keep the lanes.
-    const int dt = idx->cfg.dtype;
-    const bool zc_rows = dt == DT_F32 || dt == DT_F16 || dt == DT_U8 || dt == DT_I8;
-    // Pageable buffers this index has been handed before (same pointers, same batch) are page-locked for the call and take
-    // the same launch -- unless registering them turned out to be expensive on this system (then never again).  A buffer
-    // another thread of this process has page-locked the same way counts as pageable here, not as the caller's.
-    const size_t q_bytes = (size_t)nq * qb, o_bytes = (size_t)nq * k * 4, s_bytes = (size_t)nq * sizeof(dann_search_stats);
-    bool q_zc = q_direct;
-    bool i_zc = temp_pins().caller_pinned(out_ids, o_bytes);
-    bool d_zc = temp_pins().caller_pinned(out_dists, o_bytes);
-    bool s_zc = !out_stats || temp_pins().caller_pinned(out_stats, s_bytes);
-    PinScope pins;
-    if (zc_rows && !(q_zc && i_zc && d_zc && s_zc) && pipeline_dbg == 1u /* (an explicit lane count: lanes only) */ &&
-        idx->host_register_pays.load(std::memory_order_relaxed)) {
-        uint32_t registered_before = 0;
-        bool seen = false;
-        {
-            std::lock_guard<std::mutex> lk(idx->stat_mu);
-            const dann_index::HostCall key{queries, out_ids, out_dists, nq, 0};
-            for (auto& h : idx->host_calls)
-                if (h == key) {
-                    seen = true;
-                    registered_before = h.registered++;
-                }
-            if (!seen) idx->host_calls[idx->host_calls_next++ % 8u] = key;
-        }
-        if (seen) {
-            const auto t0 = std::chrono::steady_clock::now();
-            bool ok = true;
-            if (ok && !q_zc) ok = pins.add(queries, q_bytes);
-            if (ok && !i_zc) ok = pins.add(out_ids, o_bytes);
-            if (ok && !d_zc) ok = pins.add(out_dists, o_bytes);
-            if (ok && !s_zc) ok = pins.add(out_stats, s_bytes);
-            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            // the first registration of a range is expensive everywhere; if the second one is too, this runtime does not keep
-            // ranges warm and the lanes are the better deal
-            if (registered_before >= 1 && ms > 1.0) idx->host_register_pays.store(false, std::memory_order_relaxed);
-            if (ok) q_zc = i_zc = d_zc = s_zc = true;
-        }
-    }
-    if (zc_rows && q_zc && i_zc && d_zc && s_zc) {
-        void *dq = nullptr, *di = nullptr, *dd = nullptr, *ds = nullptr;
-        bool mapped = hipHostGetDevicePointer(&dq, const_cast<void*>(queries), 0) == hipSuccess &&
-                      hipHostGetDevicePointer(&di, out_ids, 0) == hipSuccess &&
-                      hipHostGetDevicePointer(&dd, out_dists, 0) == hipSuccess &&
-                      (!out_stats || hipHostGetDevicePointer(&ds, out_stats, 0) == hipSuccess);
-        if (!mapped) (void)hipGetLastError();  // (registered without hipHostRegisterMapped: the lanes copy instead)
-        if (mapped) {
-            std::vector<dann_search_stats> hstats;
-            if (!ds) {  // statistics the caller did not ask for: the call's status is still read from them
-                if (int32_t rc = grow_stage(ctx, 1, (size_t)nq * sizeof(dann_search_stats) + 16)) return rc;
-                ds = ctx.stage[1];
-            }
-            int32_t rc = search_device(idx, ctx, dq, nullptr, nq, l_value, beam_width, k, static_cast<uint32_t*>(di),
-                                       static_cast<float*>(dd), static_cast<dann_search_stats*>(ds), nullptr, nullptr, 0, nullptr);
-            if (rc != DANN_OK) return rc;
-            DANN_HIP(hipStreamSynchronize(ctx.stream));
-            if (!out_stats) {
-                hstats.resize(nq);
-                DANN_HIP(hipMemcpy(hstats.data(), ds, (size_t)nq * sizeof(dann_search_stats), hipMemcpyDeviceToHost));
-                return first_failed_query(hstats.data(), nq, 0);
-            }
-            return first_failed_query(out_stats, nq, 0);
-        }
-    }
-    const uint32_t nchunks = (nq + cq - 1) / cq;
-    auto chunk_len = [&](uint32_t c) { return std::min(cq, nq - c * cq); };
-    struct Lane {
-        int32_t rc = DANN_OK;          // a call-level failure (HIP, arguments)
-        int32_t failed = DANN_OK;      // the first failed query of this lane's chunks
-        uint32_t failed_chunk = ~0u;
-        std::string text;              // error text of whichever comes first (set_error is thread-local)
-    };
-    auto grab_text = [](std::string& t) {
-        char buf[512];
-        buf[0] = 0;
-        dann_last_error(buf, sizeof buf);
-        t = buf;
-    };
-    // everything one lane does, on context `lc`; `first` / `step`: its chunks
-    auto run_lane = [&](SearchCtx& lc, uint32_t first, uint32_t step, Lane& ln) -> int32_t {
-#define DANN_HIP_RC(call)                                  \
-    do {                                                   \
-        hipError_t e_ = (call);                            \
-        if (e_ != hipSuccess) return hip_fail(e_, #call);  \
-    } while (0)
-        if (int32_t rc = grow_stage(lc, 0, in_b + 16)) return rc;
-        if (int32_t rc = grow_stage(lc, 1, out_b + 16)) return rc;
-        if (lc.h_stage_bytes < in_b + out_b) {
-            if (lc.h_stage) (void)hipHostFree(lc.h_stage);
-            lc.h_stage = nullptr;
-            lc.h_stage_bytes = 0;
-            DANN_HIP_RC(hipHostMalloc(&lc.h_stage, in_b + out_b, hipHostMallocMapped));
-            lc.h_stage_bytes = in_b + out_b;
-        }
-        uint8_t* const h_in = reinterpret_cast<uint8_t*>(lc.h_stage);
-        uint8_t* const h_out = h_in + in_b;
-        void* const d_in = lc.stage[0];
-        uint8_t* const ob = reinterpret_cast<uint8_t*>(lc.stage[1]);
-        for (uint32_t c = first; c < nchunks; c += step) {
-            const uint32_t n = chunk_len(c);
-            const uint8_t* src = reinterpret_cast<const uint8_t*>(queries) + (size_t)c * cq * qb;
-            if (!q_direct) {
-                memcpy(h_in, src, (size_t)n * qb);
-                src = h_in;
-            }
-            DANN_HIP_RC(hipMemcpyAsync(d_in, src, (size_t)n * qb, hipMemcpyHostToDevice, lc.stream));
-            int32_t rc = search_device(idx, lc, d_in, nullptr, n, l_value, beam_width, k, reinterpret_cast<uint32_t*>(ob),
-                                       reinterpret_cast<float*>(ob + ids_b), reinterpret_cast<dann_search_stats*>(ob + 2 * ids_b),
-                                       nullptr, nullptr, 0, nullptr);
-            if (rc != DANN_OK) return rc;
-            if (o_direct) {
-                DANN_HIP_RC(hipMemcpyAsync(out_ids + (size_t)c * cq * k, ob, (size_t)n * k * 4, hipMemcpyDeviceToHost, lc.stream));
-                DANN_HIP_RC(hipMemcpyAsync(out_dists + (size_t)c * cq * k, ob + ids_b, (size_t)n * k * 4, hipMemcpyDeviceToHost,
-                                           lc.stream));
-                // the statuses always pass through the ring: the call's return value is read from them
-                DANN_HIP_RC(hipMemcpyAsync(h_out + 2 * ids_b, ob + 2 * ids_b, (size_t)n * sizeof(dann_search_stats),
-                                           hipMemcpyDeviceToHost, lc.stream));
-            } else {
-                DANN_HIP_RC(hipMemcpyAsync(h_out, ob, out_b, hipMemcpyDeviceToHost, lc.stream));
-            }
-            DANN_HIP_RC(hipStreamSynchronize(lc.stream));
-            const dann_search_stats* st = reinterpret_cast<const dann_search_stats*>(h_out + 2 * ids_b);
-            if (!o_direct) {
-                memcpy(out_ids + (size_t)c * cq * k, h_out, (size_t)n * k * 4);
-                memcpy(out_dists + (size_t)c * cq * k, h_out + ids_b, (size_t)n * k * 4);
-            }
-            if (out_stats) memcpy(out_stats + (size_t)c * cq, st, (size_t)n * sizeof(dann_search_stats));
-            if (ln.failed == DANN_OK) {
-                ln.failed = first_failed_query(st, n, c * cq);
-                if (ln.failed != DANN_OK) {
-                    ln.failed_chunk = c;
-                    grab_text(ln.text);
-                }
-            }
-        }
-        return DANN_OK;
-#undef DANN_HIP_RC
-    };
-    constexpr uint32_t kMaxLanes = 8, kDefaultLanes = 3;
-    const uint32_t want = std::min<uint32_t>(nchunks, pipeline_dbg >= 2u ? std::min(pipeline_dbg, kMaxLanes) : kDefaultLanes);
-    // helper lanes take a context only if one is free or may still be created: sixteen callers all waiting for a second
-    // context would wait for one another
-    std::unique_ptr<CtxLease> extra[kMaxLanes - 1];
-    uint32_t lanes = 1;
-    for (uint32_t t = 1; t < want; ++t) {
-        extra[lanes - 1].reset(new CtxLease(idx, /*try_only=*/true));
-        if (extra[lanes - 1]->status != DANN_OK || !extra[lanes - 1]->ctx) {
-            extra[lanes - 1].reset();
-            break;
-        }
-        ++lanes;
-    }
-    Lane ln[kMaxLanes];
-    // (the helpers are joined on every way out of this scope: a joinable std::thread must never be destroyed)
-    struct Helpers {
-        std::thread th[kMaxLanes - 1];
-        ~Helpers() {
-            for (auto& t : th)
-                if (t.joinable()) t.join();
-        }
-    } helpers;
-    bool started[kMaxLanes] = {true};
-    for (uint32_t t = 1; t < lanes; ++t) {
-        try {
-            helpers.th[t - 1] = std::thread([&, t]() {
-                try {
-                    (void)hipSetDevice(dev);
-                    ln[t].rc = run_lane(*extra[t - 1]->ctx, t, lanes, ln[t]);
-                    if (ln[t].rc != DANN_OK) grab_text(ln[t].text);
-                } catch (...) {
-                    ln[t].rc = DANN_EINTERNAL;
-                    ln[t].text = "exception in a lane of the host-pointer pipeline";
-                }
-            });
-            started[t] = true;
-        } catch (...) {  // no thread to be had: the calling thread takes that lane's chunks after its own
-            started[t] = false;
-        }
-    }
-    ln[0].rc = run_lane(ctx, 0, lanes, ln[0]);
-    if (ln[0].rc != DANN_OK) grab_text(ln[0].text);
-    for (uint32_t t = 1; t < lanes; ++t)
-        if (!started[t] && ln[0].rc == DANN_OK) {
-            ln[t].rc = run_lane(ctx, t, lanes, ln[t]);
-            if (ln[t].rc != DANN_OK) grab_text(ln[t].text);
-        }
-    for (uint32_t t = 1; t < lanes; ++t)
-        if (helpers.th[t - 1].joinable()) helpers.th[t - 1].join();
-    for (uint32_t t = 0; t < lanes; ++t)
-        if (ln[t].rc != DANN_OK) {
-            set_error("%s", ln[t].text.c_str());
-            return ln[t].rc;
-        }
-    const Lane* worst = nullptr;  // the failed query with the smallest index, whichever lane saw it
-    for (uint32_t t = 0; t < lanes; ++t)
-        if (ln[t].failed != DANN_OK && (!worst || ln[t].failed_chunk < worst->failed_chunk)) worst = &ln[t];
-    if (worst) {
-        set_error("%s", worst->text.c_str());
-        return worst->failed;
-    }
-    return DANN_OK;
 } DANN_CATCH_ALL
 
 int32_t dann_range_search_batch(dann_index* idx, const void* queries, uint32_t nq, uint32_t starting_l,

@@ -2200,17 +2200,6 @@ struct DevBuf {
     }
 };
 
-struct DeviceGuard {
-    int prev = -1, cur = -1;
-    explicit DeviceGuard(int dev) : cur(dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0 && prev != cur) (void)hipSetDevice(prev);  // hipSetDevice costs ~0.5 ms on ROCm 7.2
-    }
-};
-
 // persistent per-index scratch for batched inserts
 struct BuildScratch {
     uint32_t batch_cap = 0, rec_stride = 0, pend_stride = 0, degree = 0;

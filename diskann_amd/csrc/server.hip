@@ -118,17 +118,6 @@ struct ServerPin {
 
 namespace {
 
-struct DeviceGuard {
-    int prev = -1, cur = -1;
-    explicit DeviceGuard(int dev) : cur(dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0 && prev != cur) (void)hipSetDevice(prev);
-    }
-};
-
 inline uint32_t* host_u32(const uint32_t* p) { return const_cast<uint32_t*>(p); }
 
 // (re)launch the kernel; caller holds launch_mu and the kernel is not running

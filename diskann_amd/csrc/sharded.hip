@@ -189,17 +189,6 @@ struct AbortOnError {
 
 namespace {
 
-struct DeviceGuard {
-    int prev = -1, cur = -1;
-    explicit DeviceGuard(int dev) : cur(dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0 && prev != cur) (void)hipSetDevice(prev);
-    }
-};
-
 struct DevBuf {
     void* p = nullptr;
     ~DevBuf() {

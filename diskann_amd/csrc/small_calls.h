@@ -1,4 +1,4 @@
-// Small host-pointer search calls of several threads share launches (dann_search_batch, api.hip).  Host code only -- no
+// Small host-pointer search calls of several threads share launches (dann_search_batch, host_search.hip).  Host code only -- no
 // HIP in here: the launch itself is the `run` functor the caller passes, so that tests/test_small_calls_host.py can
 // compile this header with g++ and ThreadSanitizer and drive it with a stand-in for the device.
 //
@@ -51,6 +51,9 @@ struct SmallCall {
     std::atomic<bool> done{false};
     int32_t rc = DANN_OK;
     std::string text;  // the error text that goes with rc (set_error is thread-local: the waiter repeats it)
+    SmallCall() = default;
+    SmallCall(const void* q, uint32_t n, uint32_t L, uint32_t W, uint32_t k_, uint32_t* ids, float* d, dann_search_stats* st)
+        : queries(q), nq(n), l_value(L), beam(W), k(k_), out_ids(ids), out_dists(d), out_stats(st) {}
 };
 
 struct SmallCallQueue {

@@ -52,7 +52,7 @@ def bits(a):
 
 
 def small_calls_from_threads(gix, q, L, W, k, want_ids, want_d, nthreads=4, rounds=12):
-    """dann_search_batch calls of 1 .. 8 queries from `nthreads` threads at once (they share launches: api.hip,
+    """dann_search_batch calls of 1 .. 8 queries from `nthreads` threads at once (they share launches: host_search.hip,
     small_call); every call must return the rows of want_ids / want_d (the oracle's, for all of q) for its queries"""
     import ctypes as C
     import threading

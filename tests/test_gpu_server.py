@@ -40,7 +40,7 @@ def test_single_query_calls_from_many_threads_overlap():
 
 @pytest.mark.parametrize("odt", [oracle.F32, oracle.U8, oracle.F16, oracle.I8])
 def test_small_host_calls_of_many_threads_share_launches(odt):
-    """dann_search_batch calls of at most 16 queries go through the combiner (api.hip: small_call): queries and results
+    """dann_search_batch calls of at most 16 queries go through the combiner (host_search.hip: small_call): queries and results
     in page-locked mapped staging, one launch per call -- and per *group* of calls when several threads call side by side.
     Twelve Python threads with call sizes 1 .. 16 and three different (L, k) between them (only equal parameters may
     share a launch): every call returns what the oracle returns for its queries, statistics included; the counters show
