@@ -98,6 +98,7 @@ int32_t SearchCtx::init() {
 void SearchCtx::destroy() {
     if (stream) (void)hipStreamSynchronize(stream);
     if (d_fail) (void)hipFree(d_fail);
+    if (d_sched) (void)hipFree(d_sched);
     if (h_flag) (void)hipHostFree(h_flag);
     if (d_spill) (void)hipFree(d_spill);
     for (void* p : stage)
@@ -426,6 +427,7 @@ int32_t dann_index_destroy(dann_index* idx) try {
     if (idx->d_pq_pivots) (void)hipFree(idx->d_pq_pivots);
     if (idx->d_pq_offsets) (void)hipFree(idx->d_pq_offsets);
     if (idx->d_pq_pack) (void)hipFree(idx->d_pq_pack);
+    if (idx->d_sched_piv) (void)hipFree(idx->d_sched_piv);
     if (idx->build_scratch && idx->build_scratch_free) idx->build_scratch_free(idx->build_scratch);
     delete idx;
     return DANN_OK;

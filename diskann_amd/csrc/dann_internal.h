@@ -201,6 +201,8 @@ struct SearchCtx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     uint32_t* d_fail = nullptr;  // retry scratch: [count, pad, list A (cap), list B (cap)]
     size_t fail_cap = 0;
+    uint32_t* d_sched = nullptr;  // locality scheduling: [slot map (cap), keys (cap), per-block histograms]
+    size_t sched_words = 0;
     uint32_t* d_spill = nullptr;  // spill tables | counter (+pad) | busy flags | cmps histogram
     uint32_t spill_slices = 0, spill_bits = 0;
     uint32_t* h_flag = nullptr;  // pinned, device-visible: set by a query that exhausts its scratch
@@ -216,6 +218,12 @@ struct SearchCtx {
 };
 
 int32_t launch_search(const SearchArgs& a, hipStream_t stream, int* regs_out = nullptr);
+// query_schedule.hip: locality scheduling of large launches
+uint32_t sched_pivot_count(uint32_t dim);
+size_t sched_scratch_words(uint32_t dim, uint32_t nq);
+int32_t sched_build_pivots(dann_index* idx, hipStream_t st);
+int32_t sched_build_map(const dann_index* idx, hipStream_t st, const void* queries, uint32_t nq, uint32_t parts,
+                        uint32_t* scratch, uint32_t* qmap);
 // one translation unit per row type (search_<type>.hip) holds the kernel instantiations
 #define DANN_DECL_LAUNCH(name) \
     int32_t launch_search_##name(const SearchArgs& a, uint32_t qcap, size_t lds, hipStream_t stream, int* regs_out)
@@ -336,6 +344,11 @@ struct dann_index {
     size_t pq_pack_bytes = 0;
     uint32_t pq_pack_stride = 0, pq_pack_codes = 0;
     bool pq_pack_valid = false;
+    // locality scheduling of large search launches (query_schedule.hip): the pivot rows in the key kernel's layout, built
+    // on the first scheduled search and again on the first one after a mutation (sched_mu; they only ever affect speed)
+    _Float16* d_sched_piv = nullptr;
+    bool sched_stale = true;
+    std::mutex sched_mu;
     std::unordered_map<uint64_t, dann::VisitedCalib> calib;  // guarded by stat_mu
     void* build_scratch = nullptr;            // owned by build_kernels.hip
     void (*build_scratch_free)(void*) = nullptr;
@@ -411,7 +424,10 @@ struct MutationScope {
         i->mutating.fetch_add(1, std::memory_order_seq_cst);
         ok = i->srv_outstanding.sum() == 0;
         if (!ok) i->mutating.fetch_sub(1, std::memory_order_seq_cst);
-        else i->pq_pack_valid = false;  // (the caller holds the index exclusively) derived layouts die with the mutation
+        else {  // (the caller holds the index exclusively) derived layouts die with the mutation
+            i->pq_pack_valid = false;
+            i->sched_stale = true;
+        }
     }
     ~MutationScope() {
         if (ok) i->mutating.fetch_sub(1, std::memory_order_seq_cst);

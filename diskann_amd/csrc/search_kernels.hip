@@ -511,6 +511,41 @@ int32_t search_with_retry(dann_index* idx, SearchCtx& ctx, SearchArgs a) {
     if (int32_t prc = prepare_launch(idx, ctx, a, inflight)) return prc;
     cap_grid(a);  // (the counter lives behind the spill pool prepare_launch has just attached)
     if (a.grid) a.team = 0;  // persistent waves over a block: one wave per query
+    // locality scheduling (query_schedule.hip): a large Knn launch of f32 / f16 rows runs its queries grouped by nearest
+    // pivot, each XCD a contiguous run of the groups (persistent waves: the groups in order), through a slot map of its
+    // own -- told apart from a caller's or the retry's map by `caller_qmap`.  DANN_DBG_TUNE_OFF bit 128 /
+    // DANN_DBG_SCHED_MIN_QUERIES: development switches.
+    const uint32_t* const caller_qmap = a.qmap;
+    const uint32_t sched_min = idx->dbg_u32(DANN_DBG_SCHED_MIN_QUERIES, 16384u);
+    if (a.nq >= sched_min) {
+        const bool sched = !a.qmap && a.queries && !a.qslots && !a.rec_ids && !a.range_ids && !a.srv.ring && !a.team &&
+                           !a.pair && !a.pqlut && a.filter_mode == 0 && (a.ix.dtype == DT_F32 || a.ix.dtype == DT_F16) &&
+                           sched_pivot_count(a.ix.dim) >= 32u && !idx->tune_off(128);
+        if (sched) {
+            const size_t words = (size_t)a.nq + sched_scratch_words(a.ix.dim, a.nq);
+            if (ctx.sched_words < words) {
+                if (ctx.d_sched) (void)hipFree(ctx.d_sched);
+                ctx.d_sched = nullptr;
+                ctx.sched_words = 0;
+                DANN_HIP(hipMalloc((void**)&ctx.d_sched, words * 4));
+                ctx.sched_words = words;
+            }
+            {
+                std::lock_guard<std::mutex> lk(idx->sched_mu);
+                if (!idx->d_sched_piv || idx->sched_stale) {
+                    if (int32_t brc = sched_build_pivots(idx, st)) return brc;
+                    idx->sched_stale = false;
+                }
+            }
+            if (int32_t mrc = sched_build_map(idx, st, a.queries, a.nq, a.grid ? 1u : 8u, ctx.d_sched + a.nq, ctx.d_sched))
+                return mrc;
+            a.qmap = ctx.d_sched;
+        }
+        if (idx->verbose())
+            fprintf(stderr, "[dann] schedule: %u queries %s\n", a.nq,
+                    sched ? (a.grid ? "sorted by nearest pivot (persistent waves)" : "sorted by nearest pivot, 8 XCD runs")
+                          : "in caller order");
+    }
     volatile uint32_t* hflag = ctx.h_flag;
     *hflag = 0;
     a.fail_flag = ctx.h_flag;
@@ -554,7 +589,7 @@ int32_t search_with_retry(dann_index* idx, SearchCtx& ctx, SearchArgs a) {
         idx->clocks[0].launches += 1;  // one logical search = one "launch" (+ rare retry launches, time included)
     }
     // recalibrate on calls 1, 2, 4, 8, ... of this key (a 512-bin histogram of cmps, 2 KiB D2H)
-    if (autosize && a.stats && !a.qmap && !a.range_ids && a.nq >= 256) {
+    if (autosize && a.stats && !caller_qmap && !a.range_ids && a.nq >= 256) {
         uint64_t calls;
         {
             std::lock_guard<std::mutex> lk(idx->stat_mu);
@@ -584,7 +619,7 @@ int32_t search_with_retry(dann_index* idx, SearchCtx& ctx, SearchArgs a) {
     if (!*hflag || !a.stats) return DANN_OK;
     // rare path: queries that exhausted LDS table + spill pool are re-run with a larger LDS table
     uint32_t n = a.nq;
-    const uint32_t* qmap = a.qmap;
+    const uint32_t* qmap = caller_qmap;  // (a scheduled launch ran every query once: its retries go unscheduled)
     for (int round = 0;; ++round) {
         DANN_HIP(hipMemsetAsync(count, 0, 4, st));
         hipLaunchKernelGGL(collect_failed_kernel, dim3((n + 255) / 256), dim3(256), 0, st, a.stats, qmap, n, count,

@@ -38,8 +38,8 @@ int32_t dann_debug_concurrent_callers(dann_index* idx, const void* queries, uint
 enum {
     DANN_DBG_TUNE_OFF = 0,               /* bit mask: 1 row prefetch in latency mode, 2 latency-mode table sizing, 4 teams of
                                             wavefronts, 8 the teams' speculative expansion, 16 two queries per wavefront,
-                                            32 the lookup-table kernel of PQ rows, 64 the self-start of the teams' visited wave
-                                            (default 0) */
+                                            32 the lookup-table kernel of PQ rows, 64 the self-start of the teams' visited wave,
+                                            128 the locality scheduling of large launches (default 0) */
     DANN_DBG_TUNE_ON = 1,                /* bit mask: 1 row prefetch in the throughput regime too (default 0) */
     DANN_DBG_PAIR_MIN_QUERIES = 2,       /* launches of at least this many queries take two queries per wavefront
                                             (default 20 x compute units) */
@@ -67,7 +67,10 @@ enum {
     DANN_DBG_TIME_SMALL_LAUNCHES = 17,   /* 1: HIP events also around Knn search launches of at most 2 048 queries (they
                                             cost such a call 4-5 us of its 80 ... 300; default 0: those launches count in
                                             dann_kernel_time and dann_debug_search_families with 0 ms) */
-    DANN_DBG_COUNT = 18
+    DANN_DBG_SCHED_MIN_QUERIES = 18,     /* Knn search launches of f32 / f16 rows with at least this many queries run them
+                                            grouped by nearest pivot, each XCD a contiguous run of the groups (default
+                                            16384) */
+    DANN_DBG_COUNT = 19
 };
 int32_t dann_debug_set(dann_index* idx, int32_t key, double value);
 int32_t dann_debug_get(const dann_index* idx, int32_t key, double* value);
