@@ -17,6 +17,8 @@ OK, EINVAL, ELENGTH, EBOUNDS, ETOOLONG, EHIP, ENOMEM, EOVERFLOW, EUNSUPPORTED, E
 IBC_NONE, IBC_ALL = 0, 0xFFFFFFFF
 TIE_POSITION, TIE_RUST = 0, 1  # dann_set_prune_tie_order
 BUILD_MFMA_BACKEDGE, BUILD_MFMA_POOL, BUILD_ROW_KERNEL_ONLY = 1, 2, 4
+CONSOLIDATE_COMPLETE, CONSOLIDATE_DELETED = 0, 1  # ConsolidateKind (dann_consolidate out_kind)
+CONSOLIDATE_DROP_DELETED = 1  # dann_consolidate flag
 
 
 class Config(C.Structure):
@@ -125,6 +127,9 @@ SYMBOLS = {
     "dann_build": (_i32, [_vp, _P(BuildConfig), _u32, _u32, _f32, _u32]),
     "dann_set_build_options": (_i32, [_vp, _u32]),
     "dann_build_counters": (_i32, [_vp, _vp, _u32]),
+    "dann_delete_points": (_i32, [_vp, _vp, _u32]),
+    "dann_get_deleted": (_i32, [_vp, _u32, _u32, _vp]),
+    "dann_consolidate": (_i32, [_vp, _P(BuildConfig), _vp, _u32, _u32, _vp, _vp]),
     "dann_debug_gram_tiles": (_i32, [_i32, _i32, _vp, _u32, _u32, _u32, _vp, _vp]),
     "dann_save_graph": (_i32, [_vp, C.c_char_p]),
     "dann_load_graph": (_i32, [_vp, C.c_char_p, _P(_u32), _P(_u64), _P(_u64)]),

@@ -428,6 +428,7 @@ int32_t dann_index_destroy(dann_index* idx) try {
     if (idx->d_pq_offsets) (void)hipFree(idx->d_pq_offsets);
     if (idx->d_pq_pack) (void)hipFree(idx->d_pq_pack);
     if (idx->d_sched_piv) (void)hipFree(idx->d_sched_piv);
+    if (idx->d_deleted) (void)hipFree(idx->d_deleted);
     if (idx->build_scratch && idx->build_scratch_free) idx->build_scratch_free(idx->build_scratch);
     delete idx;
     return DANN_OK;

@@ -36,11 +36,11 @@
 #include "dann_device.h"
 #include "dann_internal.h"
 #include "rust_order.h"
+#include "prune_common.h"
 
 namespace dann {
 namespace {
 
-constexpr int kWave = 64;
 constexpr uint32_t kMaxPool = 4096;
 
 struct PruneCfg {
@@ -361,6 +361,8 @@ struct PoolArgs {
     uint32_t* out;             // n x out_stride
     uint32_t out_stride;
     uint32_t* err;             // set to 1 on pool overflow
+    uint32_t into_rows = 0;    // 1: the result goes straight into locs[item]'s adjacency row (out unused), and an empty
+                               // pool leaves the row alone (graph consolidation: prune_pools_into_rows)
 };
 
 template <int DT, int OP, bool NORM>
@@ -386,7 +388,8 @@ __global__ __launch_bounds__(kWave) void pool_prune_kernel(PoolArgs a) {
     // extras = around(ids, position, cand) (utils/async_tools.rs:51-131)
     uint32_t nex = 0;
     if (a.cand != 0 && a.n > 1) nex = a.cand < a.n - 1 ? a.cand : a.n - 1;
-    uint32_t* out = a.out + (uint64_t)wi * a.out_stride;
+    if (a.into_rows && cnt + nex == 0) return;
+    uint32_t* out = a.into_rows ? a.ix.adj + (uint64_t)loc * a.ix.adj_stride : a.out + (uint64_t)wi * a.out_stride;
     if (cnt + nex > a.pcap) {
         if (lane == 0) {
             *a.err = 1;
@@ -442,26 +445,6 @@ struct ListArgs {
     uint32_t out_stride;
     uint32_t* err;
 };
-
-template <int DT, int OP, bool NORM>
-__device__ void fill_list_distances(const IndexView& ix, uint32_t loc, uint32_t* pid, float* pd, uint32_t cnt) {
-    using S = Scheme<DT, OP, true>;
-    using RT = typename RowType<DT>::type;
-    constexpr int G = S::G, GROUPS = kWave / G;
-    const uint32_t lane = threadIdx.x;
-    const int g = lane / G, v = lane % G;
-    const RT* x = reinterpret_cast<const RT*>(ix.rows + (uint64_t)loc * ix.row_stride);
-    for (uint32_t r0 = 0; r0 < cnt; r0 += GROUPS) {
-        const uint32_t r = r0 + g;
-        if (r < cnt) {
-            const uint8_t* y = ix.rows + (uint64_t)pid[r] * ix.row_stride;
-            float d = finish_distance<DT, OP, NORM>(group_distance_rows<DT, OP>(reinterpret_cast<const uint8_t*>(x), y, (int)ix.dim, v),
-                                                    reinterpret_cast<const uint8_t*>(x), y, ix.dim,
-                                                    SqParams{ix.sq_k, ix.sq_shift_norm_sq});
-            if (v == 0) pd[r] = d;
-        }
-    }
-}
 
 template <int DT, int OP, bool NORM>
 __global__ __launch_bounds__(kWave) void bootstrap_kernel(ListArgs a) {
@@ -1313,10 +1296,12 @@ __global__ __launch_bounds__(kWave) void pool_sort_kernel(SortArgs sa) {
     }
     uint32_t nex = 0;
     if (a.cand != 0 && a.n > 1) nex = a.cand < a.n - 1 ? a.cand : a.n - 1;
-    if (cnt + nex > a.pcap) {
-        if (lane == 0) {
+    if ((cnt + nex > a.pcap) || (a.into_rows && cnt + nex == 0)) {
+        if (lane == 0 && cnt + nex != 0) {
             *a.err = 1;
-            a.out[(uint64_t)wi * a.out_stride] = 0;
+            if (!a.into_rows) a.out[(uint64_t)wi * a.out_stride] = 0;
+        }
+        if (lane == 0) {
             sa.sn[wi] = 0;
         }
         return;
@@ -2030,58 +2015,6 @@ __global__ void set_bulk_kernel(IndexView ix, const uint32_t* locs, const uint32
 }
 
 // ---- dispatch helpers ------------------------------------------------------------------------
-template <template <int, int, bool> class Launcher, class Args>
-int32_t dispatch(const IndexView& ix, const Args& a, uint32_t grid, size_t lds, hipStream_t stream) {
-    int op;
-    bool norm;
-    if (!resolve_metric(ix.dtype, ix.metric, &op, &norm)) {
-        set_error("metric %d is not defined for dtype %d", ix.metric, ix.dtype);
-        return DANN_EUNSUPPORTED;
-    }
-#define DANN_CASE(DT)                                                                                  \
-    case DT:                                                                                           \
-        if (op == OP_L2) {                                                                             \
-            if constexpr (DT == DT_SQ8) {                                                              \
-                if (norm) return Launcher<DT, OP_L2, true>::run(a, grid, lds, stream);                 \
-            }                                                                                          \
-            return Launcher<DT, OP_L2, false>::run(a, grid, lds, stream);                              \
-        }                                                                                              \
-        if (op == OP_IP) {                                                                             \
-            if constexpr (DT == DT_F32 || DT == DT_F16) {                                              \
-                if (norm) return Launcher<DT, OP_IP, true>::run(a, grid, lds, stream);                 \
-            }                                                                                          \
-            return Launcher<DT, OP_IP, false>::run(a, grid, lds, stream);                              \
-        }                                                                                              \
-        if constexpr (DT != DT_SQ8) return Launcher<DT, OP_COS, false>::run(a, grid, lds, stream);     \
-        return DANN_EUNSUPPORTED;
-    switch (ix.dtype) {
-        DANN_CASE(DT_F32)
-        DANN_CASE(DT_F16)
-        DANN_CASE(DT_U8)
-        DANN_CASE(DT_I8)
-        DANN_CASE(DT_SQ8)
-    }
-#undef DANN_CASE
-    set_error("bad dtype %d", ix.dtype);
-    return DANN_EINVAL;
-}
-
-#define DANN_LAUNCHER(NAME, KERNEL, ARGS)                                                          \
-    template <int DT, int OP, bool NORM>                                                           \
-    struct NAME {                                                                                  \
-        static int32_t run(const ARGS& a, uint32_t grid, size_t lds, hipStream_t stream) {         \
-            auto kern = KERNEL<DT, OP, NORM>;                                                      \
-            if (lds > 64 * 1024) {                                                                 \
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),            \
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-                if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute");                    \
-            }                                                                                      \
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(kWave), lds, stream, a);                     \
-            hipError_t e = hipGetLastError();                                                      \
-            if (e != hipSuccess) return hip_fail(e, #KERNEL " launch");                            \
-            return DANN_OK;                                                                        \
-        }                                                                                          \
-    };
 DANN_LAUNCHER(PoolLauncher, pool_prune_kernel, PoolArgs)
 DANN_LAUNCHER(BootLauncher, bootstrap_kernel, ListArgs)
 DANN_LAUNCHER(BackLauncher, backedge_kernel, BackArgs)
@@ -2807,6 +2740,114 @@ static BuildScratch& scratch_of(dann_index* idx) {
     }
     return *static_cast<BuildScratch*>(idx->build_scratch);
 }
+
+namespace dann {
+// the back-edge policy (batch_commit): float rows of 1 KiB and more, or DANN_BUILD_MFMA_BACKEDGE, unless
+// DANN_BUILD_ROW_KERNEL_ONLY
+bool prune_pools_use_gram(const dann_index* idx) {
+    const IndexView ix = idx->view();
+    return (ix.dtype == DT_F32 || ix.dtype == DT_F16) && ix.metric != M_COSINE &&
+           ((idx->build_flags & DANN_BUILD_MFMA_BACKEDGE) ||
+            (!(idx->build_flags & DANN_BUILD_ROW_KERNEL_ONLY) && ix.layer_bytes >= 1024u));
+}
+
+// robust_prune_list (index.rs:2397-2454) with force_saturate = false over m caller-built pools, for graph consolidation
+// (consolidate.hip).  Pool i: ids[i * stride + j] and their distances to locs[i], j < counts[i], in pool order (the
+// order SortedNeighbors::new receives them in); the pruned list is written straight into locs[i]'s adjacency row, an empty
+// pool leaves its row alone.  stride is a power of two >= every count and <= kMaxPool.  The same kernels as the back-edge
+// prunes: the row kernel (pool_prune_kernel) or, where dann_set_build_options picks the matrix cores for back-edges, sort +
+// Gram tiles + sweep.  Queued on the index stream, nothing waited for.  *used_gram: whether the MFMA path ran.
+int32_t prune_pools_into_rows(dann_index* idx, const dann_build_config& cfg, const uint32_t* d_locs, const uint32_t* d_ids,
+                              const float* d_dists, const uint32_t* d_counts, uint32_t stride, uint32_t m, bool* used_gram) {
+    *used_gram = false;
+    if (m == 0) return DANN_OK;
+    if (stride > kMaxPool || (stride & (stride - 1u))) {
+        set_error("prune_pools_into_rows: pool stride %u", stride);
+        return DANN_EINTERNAL;
+    }
+    BuildScratch& s = scratch_of(idx);
+    if (!s.counters.p) {
+        DANN_HIP(s.counters.alloc((size_t)kStatStripes * 64 + 64));
+        DANN_HIP(hipMemset(s.counters.p, 0, (size_t)kStatStripes * 64 + 64));
+    }
+    if (!s.meta.p) {
+        DANN_HIP(s.meta.alloc(128));
+        DANN_HIP(hipMemset(s.meta.p, 0, 128));
+    }
+    const IndexView ix = idx->view();
+    PruneCfg pc = to_prune_cfg(idx, cfg);
+    pc.counters = s.counters.as<unsigned long long>();
+    hipStream_t st = idx->main.stream;
+    PoolArgs pa;
+    pa.ix = ix;
+    pa.cfg = pc;
+    pa.locs = d_locs;
+    pa.pool_ids = d_ids;
+    pa.pool_d = d_dists;
+    pa.offsets = nullptr;
+    pa.stride = stride;
+    pa.counts = d_counts;
+    pa.cand = 0;
+    pa.n = m;
+    pa.pos0 = 0;
+    pa.pcap = stride;
+    pa.force_saturate = 0;
+    pa.out = nullptr;
+    pa.out_stride = 0;
+    pa.err = s.meta.as<uint32_t>() + 3;
+    pa.into_rows = 1;
+    const bool want_gram = prune_pools_use_gram(idx);
+    const size_t lds = pool_lds_layout(stride, pc.pruned_degree).total;
+    if (!want_gram) return dispatch<PoolLauncher>(ix, pa, m, lds, st);
+    uint32_t mg = idx->dbg_u32(DANN_DBG_GRAM_COLS, 96u);
+    mg = std::min<uint32_t>(std::max<uint32_t>((mg + 31u) & ~31u, 32u), 32u * kTileColBlocks);
+    const uint32_t ng = std::max<uint32_t>(mg, std::min<uint32_t>(32u * kTileRowBlocks, stride));
+    int32_t rc = ensure_gram_scratch(s, m, stride, ng, mg);
+    if (rc != DANN_OK) return rc;
+    SortArgs so;
+    so.p = pa;
+    so.sid = s.g_sid.as<uint32_t>();
+    so.sd = s.g_sd.as<float>();
+    so.sn = s.g_sn.as<uint32_t>();
+    rc = dispatch_float<SortLauncher>(ix, so, m, lds, st);
+    if (rc != DANN_OK) return rc;
+    TileArgs ta;
+    ta.ix = ix;
+    ta.sid = so.sid;
+    ta.sn = so.sn;
+    ta.pcap = stride;
+    ta.ng = ng;
+    ta.mg = mg;
+    ta.gram = s.g_gram.as<float>();
+    ta.nrm = s.g_nrm.as<float>();
+    ta.counters = pc.counters;
+    ta.order = longest_first(s, so.sn, m, st);
+    if (int32_t trc = s.tile_begin(st)) return trc;
+    rc = launch_gram_tiles(ta, m, st, idx->dbg_u32(DANN_DBG_GRAM_F16_WIDEN, 0u) == 0u);
+    if (rc != DANN_OK) return rc;
+    if (int32_t trc = s.tile_end(st)) return trc;
+    SweepArgs sw;
+    sw.p = pa;
+    sw.sid = so.sid;
+    sw.sd = so.sd;
+    sw.sn = so.sn;
+    sw.gram = ta.gram;
+    sw.nrm = ta.nrm;
+    sw.ng = ng;
+    sw.mg = mg;
+    sw.escale = (float)idx->dbg_value(DANN_DBG_GRAM_ESCALE, 1.0);
+    sw.c1 = gram_c1_chained(ix.dim);
+    sw.c2 = gram_c2_for_dim(ix.dim);
+    sw.one_by_one = sweep_one_by_one(idx);
+    sw.order = ta.order;
+    sw.out_loc = d_locs;
+    sw.compact_lds = sweep_is_batched(pc, mg, sw.one_by_one) ? 1u : 0u;
+    rc = dispatch_float<SweepLauncher>(ix, sw, m, sweep_lds_bytes(sw), st);
+    if (rc != DANN_OK) return rc;
+    *used_gram = true;
+    return DANN_OK;
+}
+}  // namespace dann
 
 extern "C" {
 

@@ -260,6 +260,12 @@ struct VisitedCalib {
 // HIP-event time of the MFMA Gram-tile launches of the build path (build_kernels.hip; dann_kernel_time which = 5)
 int32_t build_tile_clock(const dann_index* idx, double* total_ms, uint64_t* launches);
 void build_tile_clock_reset(const dann_index* idx);
+// robust_prune_list (force_saturate = false) of caller-built pools straight into the adjacency rows (build_kernels.hip;
+// graph consolidation, consolidate.hip).  Queued on idx->main.stream; prune_pools_use_gram: whether
+// it takes the matrix-core path (the back-edge prunes' policy).
+bool prune_pools_use_gram(const dann_index* idx);
+int32_t prune_pools_into_rows(dann_index* idx, const dann_build_config& cfg, const uint32_t* d_locs, const uint32_t* d_ids,
+                              const float* d_dists, const uint32_t* d_counts, uint32_t stride, uint32_t m, bool* used_gram);
 
 int32_t launch_expand_beam(const IndexView& ix, const void* d_queries, uint32_t nq, const uint32_t* d_ids,
                            const uint64_t* d_offsets, uint64_t max_len, float* d_out, hipStream_t stream);
@@ -349,6 +355,9 @@ struct dann_index {
     _Float16* d_sched_piv = nullptr;
     bool sched_stale = true;
     std::mutex sched_mu;
+    // dann_delete_points: one bit per slot, set = deleted (DataProvider::delete).  Allocated by the first delete; null =
+    // nothing was ever deleted.  Read by dann_consolidate (consolidate.hip).
+    uint32_t* d_deleted = nullptr;
     std::unordered_map<uint64_t, dann::VisitedCalib> calib;  // guarded by stat_mu
     void* build_scratch = nullptr;            // owned by build_kernels.hip
     void (*build_scratch_free)(void*) = nullptr;

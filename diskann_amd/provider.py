@@ -393,6 +393,34 @@ class Provider:
         check(_ffi.lib().dann_build_counters(self._h, _p(out), 11), "dann_build_counters")
         return out
 
+    # -- DataProvider::delete / DiskANNIndex::consolidate_vector -------------
+    def delete_points(self, slots):
+        """mark slots deleted (start points cannot be); on an inline_tags index their tags become RETIRING"""
+        s = np.ascontiguousarray(slots, dtype=np.uint32).ravel()
+        check(_ffi.lib().dann_delete_points(self._h, _p(s), s.size), "dann_delete_points")
+
+    def get_deleted(self, first_slot=0, n=None):
+        if n is None:
+            n = self.capacity + self.num_start_points - first_slot
+        out = np.empty(n, np.uint8)
+        check(_ffi.lib().dann_get_deleted(self._h, first_slot, n, _p(out)), "dann_get_deleted")
+        return out
+
+    def consolidate(self, cfg, ids=None, drop_deleted=False):
+        """consolidate_vector on every id (None: every slot, start points included) -> (kinds, counters): kinds is one
+        CONSOLIDATE_COMPLETE / CONSOLIDATE_DELETED per id, counters the eight words of dann_consolidate (dann.h)"""
+        if ids is None:
+            a, n = None, self.capacity + self.num_start_points
+        else:
+            a = np.ascontiguousarray(ids, dtype=np.uint32).ravel()
+            n = a.size
+        kinds = np.empty(n, np.int32)
+        counters = np.zeros(8, np.uint64)
+        flags = _ffi.CONSOLIDATE_DROP_DELETED if drop_deleted else 0
+        check(_ffi.lib().dann_consolidate(self._h, C.byref(cfg), _p(a), 0 if a is None else n, flags, _p(kinds),
+                                          _p(counters)), "dann_consolidate")
+        return kinds, counters
+
     def build(self, cfg, first, n, growth=0.02, max_batch=16384):
         return check(_ffi.lib().dann_build(self._h, C.byref(cfg), first, n, growth, max_batch), "dann_build")
 

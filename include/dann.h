@@ -442,6 +442,53 @@ int32_t dann_set_build_options(dann_index* idx, uint32_t flags);
  * dann_set_prune_tie_order holds for every pool of this index's builds).  n <= 11 entries are written. */
 int32_t dann_build_counters(const dann_index* idx, uint64_t* out, uint32_t n);
 
+/* ---- deletion and graph consolidation -------------------------------------------------------
+ * DataProvider::delete (diskann/src/provider.rs:165) + DiskANNIndex::consolidate_vector (diskann/src/graph/index.rs:
+ * 1819-1930) + drop_adj_list (index.rs:1060).  The deleted state is one bit per slot on the device, created by the first
+ * delete (an index that never deletes has none).
+ *
+ * dann_delete_points marks `slots` deleted; deleting a slot twice is fine.  A slot >= capacity + num_start_points is
+ * DANN_EBOUNDS, a start point DANN_EINVAL (start points are FROZEN); on either error nothing is marked.  On an
+ * inline_tags index the slots' tags also become RETIRING (2, diskann-inmem/src/tag.rs:81-135), so searches skip them
+ * at once.  On an index without tags the mark only drives dann_consolidate: searches are unchanged and may still return a
+ * deleted point until the graph has been consolidated (and its list dropped with DANN_CONSOLIDATE_DROP_DELETED).
+ * Slots are never reused or freed here: a deleted slot stays deleted for dann_consolidate even if its row is written
+ * again with dann_set_element(s) (which publishes its tag) -- do not rewrite a deleted slot.
+ *
+ * dann_get_deleted writes 0 / 1 per slot of [first_slot, first_slot + n).
+ *
+ * dann_consolidate runs consolidate_vector on every id of ids[0, n) -- ids == NULL: on every slot of
+ * [0, capacity + num_start_points), n is then ignored -- in one batched pass whose result equals the reference's
+ * sequential loop in any order:
+ *   - a deleted vertex is left alone: DANN_CONSOLIDATE_DELETED;
+ *   - otherwise the pool is the vertex's live neighbours plus the live neighbours of each of its deleted neighbours (not
+ *     transitive), without duplicates and without the vertex itself;
+ *   - no deleted neighbour and a pool (counting the vertex itself if it is listed, as the reference does) of at most
+ *     cfg->pruned_degree entries: nothing is written; else a pool of fewer than pruned_degree entries becomes the list;
+ *     else robust_prune_list (index.rs:2397-2454) with force_saturate = false prunes it, under the tie order of
+ *     dann_set_prune_tie_order, on the kernels of the back-edge prunes (dann_set_build_options; their work is counted
+ *     with theirs in dann_build_counters: [0] the prunes on the matrix cores, [4] - [9] the distances and Gram entries).
+ * Pool order: the reference collects the pool in a HashSet with a random hasher, so its order -- and any tie it breaks --
+ * is unspecified.  Here it is first-occurrence order: the vertex's own live neighbours in list order, then the live
+ * neighbours of each deleted neighbour, the deleted neighbours taken in the order of the vertex's list.
+ * out_kind (may be NULL): one DANN_CONSOLIDATE_* per id.  flags: DANN_CONSOLIDATE_DROP_DELETED empties the lists of all
+ * deleted slots after the pass.  out_counters (may be NULL): 8 words -- [0] vertices scanned, [1] lists rewritten without
+ * a prune, [2] pools pruned, [3] largest pool, [4] distances evaluated: d(vertex, c) of every pruned pool plus the pair
+ * distances the prune sweeps asked for (dann_build_counters [4] + [8] over the call), [5] pools pruned on the matrix
+ * cores, [6] pools of more than 4096 candidates (possible only with max_degree > 64): their max_occlusion_size nearest
+ * are selected exactly in global memory before the prune, [7] those of [6] whose selected head holds equal distances
+ * under DANN_TIE_RUST -- there the order of equal distances is by pool position, not Rust's order of the whole pool.
+ * Pools of any size are consolidated.
+ * Errors: DANN_EBOUNDS for an id out of range, DANN_EINVAL for a bad config or flag, DANN_EUNSUPPORTED for DANN_PQ
+ * indexes and for max_occlusion_size > 4096 (as for the build).
+ * All three calls are mutations: DANN_EBUSY while search-server tickets are outstanding. */
+enum { DANN_CONSOLIDATE_COMPLETE = 0, DANN_CONSOLIDATE_DELETED = 1 };
+enum { DANN_CONSOLIDATE_DROP_DELETED = 1 };
+int32_t dann_delete_points(dann_index* idx, const uint32_t* slots, uint32_t n);
+int32_t dann_get_deleted(const dann_index* idx, uint32_t first_slot, uint32_t n, uint8_t* out);
+int32_t dann_consolidate(dann_index* idx, const dann_build_config* cfg, const uint32_t* ids, uint32_t n, uint32_t flags,
+                         int32_t* out_kind, uint64_t* out_counters);
+
 /* ABI revision of this header; bumped on any incompatible change of a signature or struct layout */
 #define DANN_ABI_VERSION 4
 int32_t dann_abi_version(void);
