@@ -46,6 +46,14 @@ RNG_INDEX_FN = C.CFUNCTYPE(C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64)
 RNG_F64_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_uint32, C.c_double)
 
 
+class Diverse(C.Structure):
+    """dann_diverse: DiverseSearchParams without the attribute provider (dann_set_attributes holds the values)"""
+    _fields_ = [("diverse_k", C.c_uint32), ("total_k", C.c_uint32)]
+
+
+NO_ATTRIBUTE = 0xFFFFFFFF  # DANN_NO_ATTRIBUTE: AttributeValueProvider::get returns None
+
+
 class Rng(C.Structure):
     """dann_rng: the caller's generator for the two random draws of k-means++ (plusplus.rs:417, 440-444)."""
     _fields_ = [("ctx", C.c_void_p), ("uniform_index", RNG_INDEX_FN), ("uniform_f64", RNG_F64_FN)]
@@ -129,6 +137,9 @@ SYMBOLS = {
     "dann_build_counters": (_i32, [_vp, _vp, _u32]),
     "dann_delete_points": (_i32, [_vp, _vp, _u32]),
     "dann_get_deleted": (_i32, [_vp, _u32, _u32, _vp]),
+    "dann_set_attributes": (_i32, [_vp, _u32, _u32, _vp]),
+    "dann_get_attributes": (_i32, [_vp, _u32, _u32, _vp]),
+    "dann_diverse_search_batch": (_i32, [_vp, _vp, _u32, _u32, _u32, _u32, _P(Diverse), _vp, _vp, _vp]),
     "dann_consolidate": (_i32, [_vp, _P(BuildConfig), _vp, _u32, _u32, _vp, _vp]),
     "dann_debug_gram_tiles": (_i32, [_i32, _i32, _vp, _u32, _u32, _u32, _vp, _vp]),
     "dann_save_graph": (_i32, [_vp, C.c_char_p]),
@@ -193,8 +204,8 @@ DBG_KEYS = {"tune_off": 0, "tune_on": 1, "pair_min_queries": 2, "team_max_querie
             "sweep_one_by_one": 5, "pool_gram": 6, "gram_cols": 7, "gram_escale": 8, "backedge_gram_rows": 9,
             "server_max_resident_us": 10, "verbose": 11, "ht16_open_eighths": 12, "backedge_single_pool": 13,
             "ht16_max_probes": 14, "host_chunk": 15, "gram_f16_widen": 16, "time_small_launches": 17,
-            "sched_min_queries": 18}
-FAMILIES = ("one_wave", "team", "pair", "persistent", "server", "pq_lut")
+            "sched_min_queries": 18, "diverse_pool": 19}
+FAMILIES = ("one_wave", "team", "pair", "persistent", "server", "pq_lut", "diverse")
 
 _lib = None
 

@@ -429,6 +429,7 @@ int32_t dann_index_destroy(dann_index* idx) try {
     if (idx->d_pq_pack) (void)hipFree(idx->d_pq_pack);
     if (idx->d_sched_piv) (void)hipFree(idx->d_sched_piv);
     if (idx->d_deleted) (void)hipFree(idx->d_deleted);
+    if (idx->d_attr) (void)hipFree(idx->d_attr);
     if (idx->build_scratch && idx->build_scratch_free) idx->build_scratch_free(idx->build_scratch);
     delete idx;
     return DANN_OK;
@@ -1281,6 +1282,109 @@ int32_t dann_filtered_range_search_batch(dann_index* idx, const void* queries, u
     return filtered_search(idx, ctx, c);
 } DANN_CATCH_ALL
 
+// ---- diversity-aware search (search_diverse.hip) ---------------------------------------------------------------------
+int32_t dann_set_attributes(dann_index* idx, uint32_t first_slot, uint32_t n, const uint32_t* values) try {
+    CHECK_IDX(idx);
+    DANN_MUTATION(idx);
+    if ((uint64_t)first_slot + n > idx->nslots) {
+        set_error("dann_set_attributes: slots [%u, %llu) out of bounds (%u slots)", first_slot,
+                  (unsigned long long)first_slot + n, idx->nslots);
+        return DANN_EBOUNDS;
+    }
+    if (n == 0) return DANN_OK;
+    if (!values) return DANN_EINVAL;
+    hipStream_t st = idx->main.stream;
+    if (!idx->d_attr) {
+        DANN_HIP(hipMalloc((void**)&idx->d_attr, (size_t)idx->nslots * 4));
+        DANN_HIP(hipMemsetAsync(idx->d_attr, 0xFF, (size_t)idx->nslots * 4, st));  // DANN_NO_ATTRIBUTE
+    }
+    DANN_HIP(hipMemcpyAsync(idx->d_attr + first_slot, values, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    DANN_HIP(hipStreamSynchronize(st));
+    return DANN_OK;
+} DANN_CATCH_ALL
+
+int32_t dann_get_attributes(const dann_index* idx, uint32_t first_slot, uint32_t n, uint32_t* out) try {
+    if (!idx || (n && !out)) return DANN_EINVAL;
+    ::dann::ExclusiveGuard lock(idx);
+    if ((uint64_t)first_slot + n > idx->nslots) return DANN_EBOUNDS;
+    if (n == 0) return DANN_OK;
+    if (!idx->d_attr) {
+        for (uint32_t i = 0; i < n; ++i) out[i] = DANN_NO_ATTRIBUTE;
+        return DANN_OK;
+    }
+    DeviceGuard guard(idx->device);
+    DANN_HIP(hipMemcpyAsync(out, idx->d_attr + first_slot, (size_t)n * 4, hipMemcpyDeviceToHost, idx->main.stream));
+    DANN_HIP(hipStreamSynchronize(idx->main.stream));
+    return DANN_OK;
+} DANN_CATCH_ALL
+
+int32_t dann_diverse_search_batch(dann_index* idx, const void* queries, uint32_t nq, uint32_t l_value,
+                                  uint32_t beam_width, uint32_t k, const dann_diverse* params, uint32_t* out_ids,
+                                  float* out_dists, dann_search_stats* out_stats) try {
+    CHECK_IDX_SHARED(idx);
+    ArenaTrim _trim{ctx};
+    if (!params) return DANN_EINVAL;
+    // DiverseSearchError (diverse_search.rs:27-93) and DiverseError (:48-131)
+    if (params->total_k == 0) {
+        set_error("total k_value cannot be zero");
+        return DANN_EINVAL;
+    }
+    if (params->diverse_k == 0) {
+        set_error("diverse k_value cannot be zero");
+        return DANN_EINVAL;
+    }
+    if (params->diverse_k > params->total_k) {
+        set_error("diverse k_value (%u) cannot exceed total k_value (%u)", params->diverse_k, params->total_k);
+        return DANN_EINVAL;
+    }
+    if (l_value == 0 || beam_width == 0) {
+        set_error("l_value and beam_width must be non-zero (KnnSearchError, knn_search.rs:27-33)");
+        return DANN_EINVAL;
+    }
+    if (l_value < params->total_k) {
+        set_error("l_value (%u) must be greater than or equal to total_k_value (%u)", l_value, params->total_k);
+        return DANN_EINVAL;
+    }
+    if (idx->cfg.dtype == DT_PQ) {
+        set_error("dann_diverse_search_batch: not defined on DANN_PQ rows");
+        return DANN_EUNSUPPORTED;
+    }
+    if (beam_width > 16) {
+        set_error("beam_width %u exceeds the supported maximum of 16", beam_width);
+        return DANN_EUNSUPPORTED;
+    }
+    if (l_value + idx->cfg.num_start_points > 1024) {
+        set_error("search list size L + start points = %u exceeds the supported maximum of 1024",
+                  l_value + idx->cfg.num_start_points);
+        return DANN_EUNSUPPORTED;
+    }
+    if (nq == 0) return DANN_OK;
+    if (!queries || !out_ids || !out_dists || k == 0) return DANN_EINVAL;
+    hipStream_t st = ctx.stream;
+    const size_t qb = idx->layer_bytes;
+    const uint32_t chunk = std::min<uint32_t>(nq, 65536u);
+    Carve cv;
+    const size_t o_q = cv.take((size_t)chunk * qb + 16), o_i = cv.take((size_t)chunk * k * 4),
+                 o_d = cv.take((size_t)chunk * k * 4), o_s = cv.take((size_t)chunk * sizeof(dann_search_stats));
+    if (int32_t grc = grow_stage(ctx, 4, cv.off)) return grc;
+    void* const ar = ctx.stage[4];
+    const ArenaPtr bq{ar, o_q}, bi{ar, o_i}, bd{ar, o_d}, bs{ar, o_s};
+    std::vector<dann_search_stats> stats(chunk);
+    for (uint32_t off = 0; off < nq; off += chunk) {
+        const uint32_t n = std::min(chunk, nq - off);
+        DANN_HIP(hipMemcpyAsync(bq.p, (const uint8_t*)queries + (size_t)off * qb, (size_t)n * qb, hipMemcpyHostToDevice, st));
+        int32_t rc = diverse_search_device(idx, st, bq.p, n, l_value, beam_width, k, params->diverse_k, params->total_k,
+                                           bi.as<uint32_t>(), bd.as<float>(), bs.as<dann_search_stats>());
+        if (rc != DANN_OK) return rc;
+        DANN_HIP(hipMemcpyAsync(out_ids + (size_t)off * k, bi.p, (size_t)n * k * 4, hipMemcpyDeviceToHost, st));
+        DANN_HIP(hipMemcpyAsync(out_dists + (size_t)off * k, bd.p, (size_t)n * k * 4, hipMemcpyDeviceToHost, st));
+        if (out_stats)
+            DANN_HIP(hipMemcpyAsync(out_stats + off, bs.p, (size_t)n * sizeof(dann_search_stats), hipMemcpyDeviceToHost, st));
+        DANN_HIP(hipStreamSynchronize(st));
+    }
+    return DANN_OK;
+} DANN_CATCH_ALL
+
 int32_t dann_rerank_batch_device(dann_index* idx, const void* d_queries, uint32_t nq, const uint32_t* d_cand_ids,
                                  uint32_t cand_stride, uint32_t k, uint32_t* d_out_ids, float* d_out_dists) try {
     CHECK_IDX(idx);
@@ -1590,7 +1694,7 @@ int32_t dann_debug_search_families(const dann_index* idx, uint64_t* out_launches
 } DANN_CATCH_ALL
 
 const char* dann_debug_family_name(int32_t family) {
-    static const char* const names[DANN_FAMILY_COUNT] = {"one_wave", "team", "pair", "persistent", "server", "pq_lut"};
+    static const char* const names[DANN_FAMILY_COUNT] = {"one_wave", "team", "pair", "persistent", "server", "pq_lut", "diverse"};
     return family >= 0 && family < DANN_FAMILY_COUNT ? names[family] : nullptr;
 }
 

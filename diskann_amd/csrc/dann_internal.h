@@ -233,6 +233,10 @@ DANN_DECL_LAUNCH(u8);
 DANN_DECL_LAUNCH(i8);
 DANN_DECL_LAUNCH(sq8);
 DANN_DECL_LAUNCH(pq);
+// search_diverse.hip: dann_diverse_search_batch on device-resident queries and outputs (host-synchronous on `stream`)
+int32_t diverse_search_device(dann_index* idx, hipStream_t stream, const void* d_queries, uint32_t nq, uint32_t l_value,
+                              uint32_t beam_width, uint32_t k, uint32_t diverse_k, uint32_t total_k, uint32_t* d_ids,
+                              float* d_dists, dann_search_stats* d_stats);
 #undef DANN_DECL_LAUNCH
 int32_t launch_search_pqlut(const SearchArgs& a, size_t lds, hipStream_t stream);  // search_pqlut.hip (SearchArgs::pqlut)
 int32_t launch_search_pqlut_g1(const SearchArgs& a, size_t lds, hipStream_t stream);
@@ -358,6 +362,9 @@ struct dann_index {
     // dann_delete_points: one bit per slot, set = deleted (DataProvider::delete).  Allocated by the first delete; null =
     // nothing was ever deleted.  Read by dann_consolidate (consolidate.hip).
     uint32_t* d_deleted = nullptr;
+    // dann_set_attributes: one u32 per slot (DANN_NO_ATTRIBUTE = none), allocated by the first set; null = no slot has one.
+    // Read by the diverse search (search_diverse.hip).
+    uint32_t* d_attr = nullptr;
     std::unordered_map<uint64_t, dann::VisitedCalib> calib;  // guarded by stat_mu
     void* build_scratch = nullptr;            // owned by build_kernels.hip
     void (*build_scratch_free)(void*) = nullptr;

@@ -393,6 +393,32 @@ class Provider:
         check(_ffi.lib().dann_build_counters(self._h, _p(out), 11), "dann_build_counters")
         return out
 
+    # -- graph::search::Diverse (diverse_search.rs) ----------------------------
+    def set_attributes(self, first_slot, values):
+        """AttributeValueProvider values of slots [first_slot, first_slot + len(values)); NO_ATTRIBUTE = None"""
+        v = np.ascontiguousarray(values, dtype=np.uint32).ravel()
+        check(_ffi.lib().dann_set_attributes(self._h, first_slot, v.size, _p(v)), "dann_set_attributes")
+
+    def get_attributes(self, first_slot=0, n=None):
+        if n is None:
+            n = self.capacity + self.num_start_points - first_slot
+        out = np.empty(n, np.uint32)
+        check(_ffi.lib().dann_get_attributes(self._h, first_slot, n, _p(out)), "dann_get_attributes")
+        return out
+
+    def diverse_search(self, params, queries, k, diverse_k, total_k):
+        """Diverse::new(Knn, DiverseSearchParams{diverse_k, total_k}) for a batch; returns (ids, dists, stats)"""
+        q = np.ascontiguousarray(queries, dtype=self.query_dtype).reshape(-1, self.query_elems)
+        nq = q.shape[0]
+        ids = np.empty((nq, k), np.uint32)
+        dists = np.empty((nq, k), np.float32)
+        stats = np.zeros(nq, STATS_DTYPE)
+        p = _ffi.Diverse(diverse_k, total_k)
+        check(_ffi.lib().dann_diverse_search_batch(self._h, _p(q), nq, params.l_value, params.beam_width, k,
+                                                   C.byref(p), _p(ids), _p(dists), _p(stats)),
+              "dann_diverse_search_batch")
+        return ids, dists, stats
+
     # -- DataProvider::delete / DiskANNIndex::consolidate_vector -------------
     def delete_points(self, slots):
         """mark slots deleted (start points cannot be); on an inline_tags index their tags become RETIRING"""

@@ -489,6 +489,40 @@ int32_t dann_get_deleted(const dann_index* idx, uint32_t first_slot, uint32_t n,
 int32_t dann_consolidate(dann_index* idx, const dann_build_config* cfg, const uint32_t* ids, uint32_t n, uint32_t flags,
                          int32_t* out_kind, uint64_t* out_counters);
 
+/* ---- diversity-aware search: graph::search::Diverse (diskann/src/graph/search/diverse_search.rs:27-233) over
+ * DiverseNeighborQueue (diskann/src/neighbor/diverse_priority_queue.rs:63-238).
+ *
+ * Attributes: the AttributeValueProvider crosses the boundary as one u32 per slot of [0, capacity + num_start_points)
+ * (the slot range of the filter bitmap), stored on the device.  The store is created by the first dann_set_attributes
+ * with every slot DANN_NO_ATTRIBUTE (the provider returns None: the slot is never queued -- not the same as value 0) and
+ * freed with the index.  A range past the last slot is DANN_EBOUNDS.  dann_set_attributes is a mutation.
+ *
+ * dann_diverse_search_batch: index.search(Diverse::new(Knn{l_value, beam_width}, DiverseSearchParams{diverse_k,
+ * total_k}), ..) for nq queries; queries and outputs as dann_search_batch (host memory, nq x k, unwritten entries
+ * 0xFFFFFFFF / +inf, slot ids).  DiverseSearchParams::diverse_attribute_id is never read by the queue and does not cross.
+ *   - The local queues hold dl = diverse_k * l_value / total_k entries (integer division, :90-104); the global queue L.
+ *   - The beam loop is search_internal (index.rs:1933-2000); the candidates of a hop are inserted one by one in
+ *     adjacency order.  Afterwards every local queue is cut to diverse_k and what was cut leaves the global queue
+ *     (post_process, :112-138); best.iter().take(l_value) then goes through the Knn post-processor: start points are
+ *     dropped, result_count and stats as dann_search_batch.
+ *   - Equal distances follow NeighborPriorityQueue exactly (neighbor/queue.rs:130-222): lower-bound insertion, and a
+ *     remove that only looks at the lower-bound position and so may fail.
+ *   - An index without attributes (or whose start points have none) returns 0 results, 0 hops.
+ *   - Rows: f32, f16, u8, i8, SQ-8 with the metrics of dann_search_batch; DANN_PQ is DANN_EUNSUPPORTED.  Inline-tag
+ *     indexes skip unreadable slots as dann_search_batch does.  l_value + num_start_points <= 1024, beam_width <= 16.
+ * Errors (DiverseSearchError / DiverseError): DANN_EINVAL for total_k == 0, diverse_k == 0, diverse_k > total_k,
+ * l_value < total_k, l_value == 0 or beam_width == 0. */
+#define DANN_NO_ATTRIBUTE 0xFFFFFFFFu
+typedef struct {
+    uint32_t diverse_k;  /* DiverseSearchParams::diverse_results_k */
+    uint32_t total_k;    /* DiverseSearchParams::total_k_value */
+} dann_diverse;
+int32_t dann_set_attributes(dann_index* idx, uint32_t first_slot, uint32_t n, const uint32_t* values);
+int32_t dann_get_attributes(const dann_index* idx, uint32_t first_slot, uint32_t n, uint32_t* out);
+int32_t dann_diverse_search_batch(dann_index* idx, const void* queries, uint32_t nq, uint32_t l_value,
+                                  uint32_t beam_width, uint32_t k, const dann_diverse* params, uint32_t* out_ids,
+                                  float* out_dists, dann_search_stats* out_stats);
+
 /* ABI revision of this header; bumped on any incompatible change of a signature or struct layout */
 #define DANN_ABI_VERSION 4
 int32_t dann_abi_version(void);

@@ -70,7 +70,9 @@ enum {
     DANN_DBG_SCHED_MIN_QUERIES = 18,     /* Knn search launches of f32 / f16 rows with at least this many queries run them
                                             grouped by nearest pivot, each XCD a contiguous run of the groups (default
                                             16384) */
-    DANN_DBG_COUNT = 19
+    DANN_DBG_DIVERSE_POOL = 19,          /* test hook: entries of the LDS pool of the diverse search's local queues (default
+                                            2 L + 64); a smaller pool sends more queries to the exact global-memory re-run */
+    DANN_DBG_COUNT = 20
 };
 int32_t dann_debug_set(dann_index* idx, int32_t key, double value);
 int32_t dann_debug_get(const dann_index* idx, int32_t key, double* value);
@@ -85,10 +87,11 @@ enum {
     DANN_FAMILY_PERSISTENT = 3,  /* beam_search_kernel, persistent wavefronts sharing a batch (dann_set_max_concurrency) */
     DANN_FAMILY_SERVER = 4,      /* the resident server kernel */
     DANN_FAMILY_PQ_LUT = 5,      /* pq_search_kernel, lookup table in registers (PQ rows) */
-    DANN_FAMILY_COUNT = 6
+    DANN_FAMILY_DIVERSE = 6,     /* diverse_search_kernel, one wavefront per query (dann_diverse_search_batch) */
+    DANN_FAMILY_COUNT = 7
 };
 int32_t dann_debug_search_families(const dann_index* idx, uint64_t* out_launches, double* out_ms);
-/* family name for logs ("one_wave", "team", "pair", "persistent", "server", "pq_lut"); null for an unknown family */
+/* family name for logs ("one_wave", "team", "pair", "persistent", "server", "pq_lut", "diverse"); null for an unknown family */
 const char* dann_debug_family_name(int32_t family);
 
 /* small dann_search_batch calls (host pointers, at most 16 queries) of several threads share launches: out2 = {launches,
