@@ -19,6 +19,8 @@ TIE_POSITION, TIE_RUST = 0, 1  # dann_set_prune_tie_order
 BUILD_MFMA_BACKEDGE, BUILD_MFMA_POOL, BUILD_ROW_KERNEL_ONLY = 1, 2, 4
 CONSOLIDATE_COMPLETE, CONSOLIDATE_DELETED = 0, 1  # ConsolidateKind (dann_consolidate out_kind)
 CONSOLIDATE_DROP_DELETED = 1  # dann_consolidate flag
+INPLACE_VISITED_AND_TOPK, INPLACE_TWO_HOP_AND_ONE_HOP, INPLACE_ONE_HOP = 0, 1, 2  # dann_inplace_delete_params.method
+INPLACE_COUNTERS = 9
 
 
 class Config(C.Structure):
@@ -49,6 +51,11 @@ RNG_F64_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_uint32, C.c_double)
 class Diverse(C.Structure):
     """dann_diverse: DiverseSearchParams without the attribute provider (dann_set_attributes holds the values)"""
     _fields_ = [("diverse_k", C.c_uint32), ("total_k", C.c_uint32)]
+
+
+class InplaceDeleteParams(C.Structure):
+    """dann_inplace_delete_params: graph::InplaceDeleteMethod + num_to_replace"""
+    _fields_ = [("method", C.c_uint32), ("k_value", C.c_uint32), ("l_value", C.c_uint32), ("num_to_replace", C.c_uint32)]
 
 
 NO_ATTRIBUTE = 0xFFFFFFFF  # DANN_NO_ATTRIBUTE: AttributeValueProvider::get returns None
@@ -141,6 +148,8 @@ SYMBOLS = {
     "dann_get_attributes": (_i32, [_vp, _u32, _u32, _vp]),
     "dann_diverse_search_batch": (_i32, [_vp, _vp, _u32, _u32, _u32, _u32, _P(Diverse), _vp, _vp, _vp]),
     "dann_consolidate": (_i32, [_vp, _P(BuildConfig), _vp, _u32, _u32, _vp, _vp]),
+    "dann_inplace_delete": (_i32, [_vp, _P(BuildConfig), _vp, _u32, _P(InplaceDeleteParams), _vp]),
+    "dann_drop_deleted_neighbors": (_i32, [_vp, _P(BuildConfig), _vp, _u32, _u32, _vp]),
     "dann_debug_gram_tiles": (_i32, [_i32, _i32, _vp, _u32, _u32, _u32, _vp, _vp]),
     "dann_save_graph": (_i32, [_vp, C.c_char_p]),
     "dann_load_graph": (_i32, [_vp, C.c_char_p, _P(_u32), _P(_u64), _P(_u64)]),

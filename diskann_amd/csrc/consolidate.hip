@@ -367,7 +367,9 @@ struct CallBuf {
     }
 };
 
-int32_t ensure_bitmap(dann_index* idx) {
+}  // namespace
+
+int32_t ensure_deleted_bitmap(dann_index* idx) {
     if (idx->d_deleted) return DANN_OK;
     const size_t bytes = (size_t)((idx->nslots + 31u) / 32u) * 4u;
     uint32_t* p = nullptr;
@@ -382,7 +384,6 @@ int32_t ensure_bitmap(dann_index* idx) {
     return DANN_OK;
 }
 
-}  // namespace
 }  // namespace dann
 
 using namespace dann;
@@ -406,7 +407,7 @@ int32_t dann_delete_points(dann_index* idx, const uint32_t* slots, uint32_t n) t
         }
     }
     DeviceGuard guard(idx->device);
-    if (int32_t rc = ensure_bitmap(idx)) return rc;
+    if (int32_t rc = ensure_deleted_bitmap(idx)) return rc;
     CallBuf d_slots;
     DANN_HIP(d_slots.alloc((size_t)n * 4));
     hipStream_t st = idx->main.stream;

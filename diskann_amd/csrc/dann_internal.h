@@ -270,6 +270,8 @@ void build_tile_clock_reset(const dann_index* idx);
 bool prune_pools_use_gram(const dann_index* idx);
 int32_t prune_pools_into_rows(dann_index* idx, const dann_build_config& cfg, const uint32_t* d_locs, const uint32_t* d_ids,
                               const float* d_dists, const uint32_t* d_counts, uint32_t stride, uint32_t m, bool* used_gram);
+// idx->d_deleted, allocated and cleared on first use (consolidate.hip; dann_delete_points, dann_inplace_delete)
+int32_t ensure_deleted_bitmap(dann_index* idx);
 
 int32_t launch_expand_beam(const IndexView& ix, const void* d_queries, uint32_t nq, const uint32_t* d_ids,
                            const uint64_t* d_offsets, uint64_t max_len, float* d_out, hipStream_t stream);

@@ -447,6 +447,35 @@ class Provider:
                                           _p(counters)), "dann_consolidate")
         return kinds, counters
 
+    # -- DiskANNIndex::multi_inplace_delete / drop_deleted_neighbors ---------
+    def inplace_delete(self, cfg, ids, method=_ffi.INPLACE_TWO_HOP_AND_ONE_HOP, k=0, l=0, num_to_replace=3,
+                       minibatch=None):
+        """multi_inplace_delete: ids in chunks of `minibatch` (None: one call), one dann_inplace_delete each, run one after
+        another -> the counters of dann_inplace_delete (dann.h) summed over the chunks"""
+        a = np.ascontiguousarray(ids, dtype=np.uint32).ravel()
+        step = a.size if not minibatch else int(minibatch)
+        prm = _ffi.InplaceDeleteParams(method, k, l, num_to_replace)
+        total = np.zeros(_ffi.INPLACE_COUNTERS, np.uint64)
+        for lo in range(0, a.size, max(step, 1)):
+            chunk = np.ascontiguousarray(a[lo: lo + step])
+            counters = np.zeros(_ffi.INPLACE_COUNTERS, np.uint64)
+            check(_ffi.lib().dann_inplace_delete(self._h, C.byref(cfg), _p(chunk), chunk.size, C.byref(prm), _p(counters)),
+                  "dann_inplace_delete")
+            total += counters
+        return total
+
+    def drop_deleted_neighbors(self, cfg, ids=None, only_orphans=False):
+        """drop_deleted_neighbors on every id (None: every slot) -> one CONSOLIDATE_COMPLETE / CONSOLIDATE_DELETED per id"""
+        if ids is None:
+            a, n = None, self.capacity + self.num_start_points
+        else:
+            a = np.ascontiguousarray(ids, dtype=np.uint32).ravel()
+            n = a.size
+        kinds = np.empty(n, np.int32)
+        check(_ffi.lib().dann_drop_deleted_neighbors(self._h, C.byref(cfg), _p(a), 0 if a is None else n,
+                                                     1 if only_orphans else 0, _p(kinds)), "dann_drop_deleted_neighbors")
+        return kinds
+
     def build(self, cfg, first, n, growth=0.02, max_batch=16384):
         return check(_ffi.lib().dann_build(self._h, C.byref(cfg), first, n, growth, max_batch), "dann_build")
 

@@ -523,6 +523,78 @@ int32_t dann_diverse_search_batch(dann_index* idx, const void* queries, uint32_t
                                   uint32_t beam_width, uint32_t k, const dann_diverse* params, uint32_t* out_ids,
                                   float* out_dists, dann_search_stats* out_stats);
 
+/* ---- in-place deletes ------------------------------------------------------------------------
+ * DiskANNIndex::multi_inplace_delete / inplace_delete (diskann/src/graph/index.rs:1338-1551, inplace_delete_inner
+ * 1585-1747) + drop_deleted_neighbors (index.rs:1756-1816): the graph is repaired around the deleted points at delete
+ * time, without a pass over the whole index.  Meant to be paired with an occasional dann_drop_deleted_neighbors sweep
+ * and, once many points are gone, dann_consolidate.
+ *
+ * dann_inplace_delete is one minibatch of multi_inplace_delete (the caller splits a longer list into chunks of
+ * max_minibatch_par and runs them one after another, as the reference does; n = 1 is inplace_delete):
+ *   1. Deletion comes first: every id of the call is marked deleted (as dann_delete_points) before any work list is built.
+ *      The reference deletes inside each parallel task; "all marks first" is one of its schedules, and the only one that
+ *      makes the result deterministic.  A repeated id counts once, at its first position.
+ *   2. Readable: for the whole call a slot is unreadable if it is marked deleted or, on an inline_tags index, its tag is
+ *      below PUBLISHED -- so a tagless index behaves like the same index with tags.  Unreadable slots are never replace
+ *      candidates or in-neighbours, and robust_prune_list leaves them out of its pool (view.get is None).
+ *   3. Work lists (index.rs:1168-1336), `live` meaning readable:
+ *        DANN_INPLACE_ONE_HOP: the live out-neighbours of the id, in list order, are both the replace candidates and the
+ *          in-neighbour candidates;
+ *        DANN_INPLACE_TWO_HOP_AND_ONE_HOP: the replace candidates as for ONE_HOP; the in-neighbour candidates are those
+ *          neighbours plus every entry of their lists, deduplicated, unreadable ids removed, in first-occurrence order
+ *          (the reference's HashSet order is unspecified; no output depends on it);
+ *        DANN_INPLACE_VISITED_AND_TOPK: a Knn search_internal with the deleted row as the query, L = l_value, beam
+ *          width 1 (NeighborPriorityQueue: capacity l_value + start points, lower-bound inserts, so a later candidate at
+ *          an equal distance goes in front of an earlier one -- a start point, inserted first, included), unreadable
+ *          slots put into the visited set and skipped, distances the pair distances d(id, c) of the prunes.  The CopyIds
+ *          post-processor: start points kept, the first min(l_value, size) entries in queue order are the in-neighbour
+ *          candidates; the first k_value of them are the replace candidates (index.rs:1168-1233);
+ *        the in-neighbours are the candidates whose list contains the id.
+ *   4. Replacement edges: for each in-neighbour c, d(c, r) for every replace candidate r != c (the bit-exact pair
+ *      distances of the prunes), ordered as sort_unstable_by(fast_distance) under dann_set_prune_tie_order
+ *      (DANN_TIE_POSITION: (distance, position); DANN_TIE_RUST: Rust's order -- insertion sort up to 20, ipnsort beyond),
+ *      and the first num_to_replace give the edges c -> r.  For each live out-neighbour o of the id the same selection
+ *      over the candidates r != o gives the edges r -> o.
+ *   5. Aggregation: a source's targets are concatenated over the call's ids in call order, each id's in its own edge
+ *      order (c's edges as in-neighbour first, then r -> o in the order of the id's list).  Every distinct source (every
+ *      in-neighbour is one, even without a replacement) gets add_edge_and_prune (index.rs:2264-2341) with to_remove = the
+ *      ids of this call only: edges to points deleted by earlier calls stay.  The extend skips ids already in the list.
+ *      Nothing added and nothing removed: nothing is written; a list that fits cfg->max_degree (max_degree_with_slack)
+ *      becomes the row; else robust_prune_list (force_saturate = false) under the index's tie order, on the back-edge
+ *      prune kernels.  Each source reads only its own list and the rows, so the batch does not depend on order.
+ *   6. The lists of the call's ids are dropped (drop_adj_list).
+ *   out_counters (may be NULL): DANN_INPLACE_COUNTERS words -- [0] ids repaired (distinct), [1] in-neighbours found,
+ *   [2] replace candidates, [3] pair distances of the edge step, [4] distinct sources, [5] lists appended, [6] lists set
+ *   without a prune (an edge was removed), [7] lists pruned, [8] of those, the pools pruned on the matrix cores.
+ *   Errors: DANN_EBOUNDS for an id out of range; DANN_EINVAL for a start point, an id an earlier
+ *   call deleted (the reference's id translation fails for the whole chunk, diskann-inmem/src/provider.rs:274-294), a bad
+ *   cfg or params (VISITED_AND_TOPK: k_value > 0, 0 < l_value <= 2048), or more than 2^20 ids; DANN_EUNSUPPORTED for
+ *   DANN_PQ rows, max_degree + the replace candidates' capacity above 4096, TWO_HOP_AND_ONE_HOP with max_degree > 256,
+ *   and a call whose edges would overflow its buffers (a vertex with a pool of more than 4096 candidates, 2^31 edges):
+ *   split the minibatch.  Every error before the rows are rewritten removes the call's marks again; a HIP error while
+ *   rows are being rewritten leaves the marks and the rows written so far.
+ *   A mutation: DANN_EBUSY while search-server tickets are outstanding.
+ *
+ * dann_drop_deleted_neighbors runs drop_deleted_neighbors on ids[0, n) -- ids == NULL: every slot of
+ * [0, capacity + num_start_points) -- in one batched pass that equals the sequential loop (a vertex's rewrite reads only
+ * its own list and its deleted neighbours' list lengths, and a deleted vertex is never rewritten).  "Deleted" is
+ * unreadable as above.  A deleted vertex gets DANN_CONSOLIDATE_DELETED; otherwise the pool is its live neighbours in list
+ * order, then with only_orphans the deleted neighbours whose own list is non-empty, in list order.  No deleted neighbour
+ * and a pool of at most cfg->pruned_degree: nothing is written; else the list becomes the pool, without a prune.
+ * out_kind (may be NULL): one DANN_CONSOLIDATE_* per id.  DANN_EBOUNDS for an id out of range.  A mutation. */
+enum { DANN_INPLACE_VISITED_AND_TOPK = 0, DANN_INPLACE_TWO_HOP_AND_ONE_HOP = 1, DANN_INPLACE_ONE_HOP = 2 };
+enum { DANN_INPLACE_COUNTERS = 9 };
+typedef struct {
+    uint32_t method;         /* DANN_INPLACE_* (graph::InplaceDeleteMethod, diskann/src/graph/misc.rs:28-32) */
+    uint32_t k_value;        /* VISITED_AND_TOPK only: replace candidates = the first k_value search results */
+    uint32_t l_value;        /* VISITED_AND_TOPK only: the search's L and the number of results kept */
+    uint32_t num_to_replace;
+} dann_inplace_delete_params;
+int32_t dann_inplace_delete(dann_index* idx, const dann_build_config* cfg, const uint32_t* ids, uint32_t n,
+                            const dann_inplace_delete_params* p, uint64_t* out_counters);
+int32_t dann_drop_deleted_neighbors(dann_index* idx, const dann_build_config* cfg, const uint32_t* ids, uint32_t n,
+                                    uint32_t only_orphans, int32_t* out_kind);
+
 /* ABI revision of this header; bumped on any incompatible change of a signature or struct layout */
 #define DANN_ABI_VERSION 4
 int32_t dann_abi_version(void);
