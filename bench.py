@@ -12,8 +12,11 @@ Multi-GPU (launched by torch.distributed.run, one rank per GPU): the index is re
 every GPU's HBM, each rank searches its own query stream (no data-path collective), `value`
 is the whole-job QPS = N * nq * K / max-over-ranks time ("weak" scaling).
 
-Rank 0 prints ONE JSON line with the `roofline` (HIP-event time of the beam-search kernel vs
-its algorithmic bytes) and `cpu_baseline` (the CPU oracle on this box's host cores) objects.
+A plain run does only what the headline needs: set-up (data, build, ground truth, the L sweep), the warm-up, the K timed
+steps, --dump-outputs, and ONE JSON line on rank 0.  `--full` adds to that line everything else the benchmark measures
+or checks: the `roofline` (HIP-event time of the beam-search kernel vs its algorithmic bytes), the strong-scaling shared
+set and its identity check, `cpu_baseline` (the CPU oracle on the host's cores), the other BASELINE configurations,
+row types and precisions, and the indexes far beyond the Infinity Cache.
 """
 import argparse
 import ctypes as C
@@ -39,10 +42,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=None,
                     help="GPUs of this node (one rank each).  Without a launcher bench.py spawns the ranks itself; "
                          "under torch.distributed.run it must equal WORLD_SIZE.  Default: WORLD_SIZE or 1")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run everything else the benchmark measures or checks (roofline, the "
+                         "strong-scaling shared set, CPU baseline, the other configurations, row types and sizes); without "
+                         "it a run sets up, warms up, times the steps, writes --dump-outputs and prints the headline line")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: every rank searches its own --nq queries per step.  strong: one shared set of "
                          "--nq-shared queries is block-partitioned over the ranks (diskann-benchmark-core "
-                         "search/api.rs:399-436) and the gathered output must equal the 1-rank output byte for byte")
+                         "search/api.rs:399-436); with --full the gathered output must equal the 1-rank output byte for byte")
     ap.add_argument("--nq-shared", type=int, default=10000, help="size of the shared query set (the protocol's nq)")
     ap.add_argument("--only-large", action="store_true",
                     help="run only the roofline_large workload and print its object (used under rocprofv3)")
@@ -69,13 +76,14 @@ def parse():
     ap.add_argument("--beam-width", type=int, default=1)
     ap.add_argument("--L", type=int, default=0, help="fixed L (0 = first L of the sweep with recall >= target)")
     ap.add_argument("--target-recall", type=float, default=0.95)
+    # (the next five shape what --full adds; a plain run has none of it)
     ap.add_argument("--cpu-queries", type=int, default=20000)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sq8", action="store_true")
     ap.add_argument("--no-pq", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the headline workload (used under rocprofv3 so that every launch of the "
-                         "beam-search kernel is the timed one)")
+                    help="with --full: only the headline workload, its roofline and the CPU baseline (used under "
+                         "rocprofv3 so that every launch of the beam-search kernel is the timed one)")
     ap.add_argument("--pq-chunks", type=int, default=16)
     ap.add_argument("--replicated-build", action="store_true",
                     help="with --gpus N > 1: every rank builds its own replica with dann_build (no exchange); default "
@@ -379,18 +387,19 @@ def main():
         if int(t.item()) != chosen:
             chosen = int(t.item())
             rec, st = evaluate(chosen, W)
-    # algorithmic bytes of a launch: the mean over the query sets the timed steps cycle through
-    set_cmps, set_hops = [int(st[:, 0].sum())], [int(st[:, 1].sum())]
-    for i in range(1, nsets):
-        run_search(chosen, W, i)
-        sti = d_stats.cpu().numpy().view(np.uint32)
-        if sti[:, 3].any():
-            raise RuntimeError(f"per-query scratch overflow at L={chosen} (query set {i})")
-        set_cmps.append(int(sti[:, 0].sum()))
-        set_hops.append(int(sti[:, 1].sum()))
-    used = [i % nsets for i in range(args.steps)] or [0]
-    cmps_sum = sum(set_cmps[i] for i in used) / len(used)
-    hops_sum = sum(set_hops[i] for i in used) / len(used)
+    # --full: algorithmic bytes of a launch (the roofline), the mean over the query sets the timed steps cycle through
+    if args.full:
+        set_cmps, set_hops = [int(st[:, 0].sum())], [int(st[:, 1].sum())]
+        for i in range(1, nsets):
+            run_search(chosen, W, i)
+            sti = d_stats.cpu().numpy().view(np.uint32)
+            if sti[:, 3].any():
+                raise RuntimeError(f"per-query scratch overflow at L={chosen} (query set {i})")
+            set_cmps.append(int(sti[:, 0].sum()))
+            set_hops.append(int(sti[:, 1].sum()))
+        used = [i % nsets for i in range(args.steps)] or [0]
+        cmps_sum = sum(set_cmps[i] for i in used) / len(used)
+        hops_sum = sum(set_hops[i] for i in used) / len(used)
 
     # ---- timed region ------------------------------------------------------------------------------
     for w_ in range(args.warmup):
@@ -417,55 +426,54 @@ def main():
         elapsed = float(t.item())
 
     # ---- strong scaling: ONE shared query set, block-partitioned over the ranks (the reference's protocol:
-    # diskann-benchmark-core/src/search/api.rs:399-436); the gathered g-rank output must equal the 1-rank output
-    from diskann_amd.sharding import partition, search_sharded
-    # (skipped in single-rank --no-extras runs: under rocprofv3 every beam-search launch is then the timed workload)
-    nqs = args.nq_shared if (world > 1 or not args.no_extras or args.scaling == "strong") else 0
-    _, shared = make_data(torch, dev, 0, args.dim, nqs, args.dist, 0xD15CA11, 0xD15CA20)  # same set on every rank
-    lo, hi = partition(nqs, world, rank)
-    s_ids = torch.empty((max(hi - lo, 1), k), dtype=torch.int32, device=dev)
-    s_d = torch.empty((max(hi - lo, 1), k), dtype=torch.float32, device=dev)
-    s_st = torch.empty((max(hi - lo, 1), 5), dtype=torch.int32, device=dev)
+    # diskann-benchmark-core/src/search/api.rs:399-436).  The headline of --scaling strong; --full times it beside the weak
+    # headline too and checks that the gathered g-rank output equals the 1-rank output
+    strong = None
+    if args.full or args.scaling == "strong":
+        from diskann_amd.sharding import partition, search_sharded
+        # (skipped in single-rank --no-extras runs: under rocprofv3 every beam-search launch is then the timed workload)
+        nqs = args.nq_shared if (world > 1 or not args.no_extras or args.scaling == "strong") else 0
+        _, shared = make_data(torch, dev, 0, args.dim, nqs, args.dist, 0xD15CA11, 0xD15CA20)  # same set on every rank
+        lo, hi = partition(nqs, world, rank)
+        s_ids = torch.empty((max(hi - lo, 1), k), dtype=torch.int32, device=dev)
+        s_d = torch.empty((max(hi - lo, 1), k), dtype=torch.float32, device=dev)
+        s_st = torch.empty((max(hi - lo, 1), 5), dtype=torch.int32, device=dev)
 
-    def run_shared():
-        if hi > lo:
-            _ffi.check(lib.dann_search_batch_device(prov._h, C.c_void_p(shared[lo:hi].data_ptr()), hi - lo, chosen, W, k,
-                                                    C.c_void_p(s_ids.data_ptr()), C.c_void_p(s_d.data_ptr()),
-                                                    C.c_void_p(s_st.data_ptr())), "dann_search_batch_device")
-    for _ in range(max(args.warmup, 1)):
-        run_shared()
-    barrier()
-    ts = time.perf_counter()
-    for _ in range(args.steps):
-        run_shared()
-    barrier()
-    strong_elapsed = time.perf_counter() - ts
-    if args.dump_outputs and args.scaling == "strong":  # this rank's block of the shared set
-        dump_outputs(args.dump_outputs, s_ids[:hi - lo], s_d[:hi - lo], s_st[:hi - lo], rank, world)
-    if world > 1:
-        t = torch.tensor([strong_elapsed], device=torch.device("cpu") if one_dev else dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        strong_elapsed = float(t.item())
-    shared_h = shared.cpu().numpy()
-    empty = (np.zeros((0, k), np.uint32), np.zeros((0, k), np.float32))
-    g_ids, g_d = empty if nqs == 0 else search_sharded(
-        lambda qs: prov.search(da.Knn(chosen, W), qs, k)[:2] if len(qs) else empty, shared_h, k, rank, world)
-    strong = {"queries": nqs, "qps": nqs * args.steps / max(strong_elapsed, 1e-9), "ms_per_pass": strong_elapsed / args.steps * 1e3,
-              "ranks": world}
-    if rank == 0 and nqs:
-        one_ids, one_d, _ = prov.search(da.Knn(chosen, W), shared_h, k)  # the same set through ONE rank
-        strong["identical_to_single_rank"] = bool(np.array_equal(one_ids, g_ids) and
-                                                  np.array_equal(one_d.view(np.uint32), g_d.view(np.uint32)))
-        if not strong["identical_to_single_rank"]:
-            raise SystemExit("bench.py: sharded output differs from the single-rank output")
+        def run_shared():
+            if hi > lo:
+                _ffi.check(lib.dann_search_batch_device(prov._h, C.c_void_p(shared[lo:hi].data_ptr()), hi - lo, chosen, W,
+                                                        k, C.c_void_p(s_ids.data_ptr()), C.c_void_p(s_d.data_ptr()),
+                                                        C.c_void_p(s_st.data_ptr())), "dann_search_batch_device")
+        for _ in range(max(args.warmup, 1)):
+            run_shared()
+        barrier()
+        ts = time.perf_counter()
+        for _ in range(args.steps):
+            run_shared()
+        barrier()
+        strong_elapsed = time.perf_counter() - ts
+        if args.dump_outputs and args.scaling == "strong":  # this rank's block of the shared set
+            dump_outputs(args.dump_outputs, s_ids[:hi - lo], s_d[:hi - lo], s_st[:hi - lo], rank, world)
+        if world > 1:
+            t = torch.tensor([strong_elapsed], device=torch.device("cpu") if one_dev else dev, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            strong_elapsed = float(t.item())
+        strong = {"queries": nqs, "qps": nqs * args.steps / max(strong_elapsed, 1e-9),
+                  "ms_per_pass": strong_elapsed / args.steps * 1e3, "ranks": world}
+        if args.full and nqs:
+            shared_h = shared.cpu().numpy()
+            empty = (np.zeros((0, k), np.uint32), np.zeros((0, k), np.float32))
+            g_ids, g_d = search_sharded(
+                lambda qs: prov.search(da.Knn(chosen, W), qs, k)[:2] if len(qs) else empty, shared_h, k, rank, world)
+            if rank == 0:
+                one_ids, one_d, _ = prov.search(da.Knn(chosen, W), shared_h, k)  # the same set through ONE rank
+                strong["identical_to_single_rank"] = bool(np.array_equal(one_ids, g_ids) and
+                                                          np.array_equal(one_d.view(np.uint32), g_d.view(np.uint32)))
+                if not strong["identical_to_single_rank"]:
+                    raise SystemExit("bench.py: sharded output differs from the single-rank output")
 
     if rank == 0:
         qps = world * args.nq * args.steps / elapsed
-        row_bytes = args.dim * 4
-        adj_bytes = (args.max_degree + 1) * 4
-        alg_bytes = cmps_sum * row_bytes + hops_sum * adj_bytes  # per launch
-        avg_kernel_ms = kernel_ms / max(launches, 1)
-        achieved = alg_bytes / (avg_kernel_ms * 1e-3) / 1e9
         out = {
             "metric": "QPS @ recall@10>=0.95, SIFT-1M-shaped d=128 f32 L2",
             "value": qps,
@@ -489,8 +497,7 @@ def main():
                 "recall_at_10": round(rec, 4),
                 "L": chosen,
                 "beam_width": W,
-                "mean_cmps": cmps_sum / args.nq,
-                "mean_hops": hops_sum / args.nq,
+                **({"mean_cmps": cmps_sum / args.nq, "mean_hops": hops_sum / args.nq} if args.full else {}),
                 "query_sets_rotated": nsets,
                 "build_seconds": round(t_build, 2),
                 **({"build_exchange": build_stats} if build_stats is not None else {}),
@@ -500,7 +507,14 @@ def main():
                 "rccl_world": 0 if (world == 1 or one_dev) else world,
                 "per_rank_qps": per_rank_qps,
             },
-            "roofline": {
+        }
+        if args.full:
+            row_bytes = args.dim * 4
+            adj_bytes = (args.max_degree + 1) * 4
+            alg_bytes = cmps_sum * row_bytes + hops_sum * adj_bytes  # per launch
+            avg_kernel_ms = kernel_ms / max(launches, 1)
+            achieved = alg_bytes / (avg_kernel_ms * 1e-3) / 1e9
+            out["roofline"] = {
                 "kernel": "beam_search_kernel",
                 # a 644 MB working set against a 256 MiB Infinity Cache: the rate below is what the fabric delivers
                 # (HBM + cache hits); the HBM-side fraction of the same kernel is `hbm_side_frac` (the 6.4 GB index)
@@ -512,8 +526,19 @@ def main():
                 "traffic": None,
                 "algorithmic_bytes_per_launch": alg_bytes,
                 "avg_kernel_ms": avg_kernel_ms,
-            },
-        }
+            }
+        if strong is not None:
+            out["other_configs"] = {"strong_scaling_shared_set": strong}
+        if args.scaling == "strong":  # headline = the shared set; the weak number moves to other_configs
+            out["other_configs"]["weak_scaling"] = {"qps": qps, "ms_per_step": out["ms_per_step"],
+                                                    "queries_per_step_per_gpu": args.nq}
+            out["value"] = strong["qps"]
+            out["ms_per_step"] = strong["ms_per_pass"]
+            out["scaling"] = "strong"
+            out["config"]["workload"] = (f"batched beam search over a {args.n}x{args.dim} f32 index resident in HBM, ONE "
+                                         f"shared set of {nqs} queries per step block-partitioned over {world} GPU(s), "
+                                         f"k=10, L={chosen}, beam_width={W}")
+    if rank == 0 and args.full:
         # the other BASELINE.json configurations, measured on the same index (not the headline):
         # configs[1] single-query beam search at L=64, configs[2] 1024 concurrent queries
         def timed_small(nq_small, L_small, reps):
@@ -530,16 +555,6 @@ def main():
                                              C.c_void_p(d_stats.data_ptr()))
             torch.cuda.synchronize()
             return (time.perf_counter() - t_0) / reps
-        out["other_configs"] = {"strong_scaling_shared_set": strong}
-        if args.scaling == "strong":  # headline = the shared set; the weak number moves to other_configs
-            out["other_configs"]["weak_scaling"] = {"qps": qps, "ms_per_step": out["ms_per_step"],
-                                                    "queries_per_step_per_gpu": args.nq}
-            out["value"] = strong["qps"]
-            out["ms_per_step"] = strong["ms_per_pass"]
-            out["scaling"] = "strong"
-            out["config"]["workload"] = (f"batched beam search over a {args.n}x{args.dim} f32 index resident in HBM, ONE "
-                                         f"shared set of {nqs} queries per step block-partitioned over {world} GPU(s), "
-                                         f"k=10, L={chosen}, beam_width={W}")
         oix_head, qh_all, ref_small = None, None, None
         if not args.no_cpu_baseline and world == 1:
             import oracle
@@ -802,6 +817,7 @@ def main():
             out["roofline"]["hbm_side"] = {
                 "beam_search_first_touch": out["roofline_large"].get("hbm_side"),
                 "distance_kernel_rows_read_once": out["roofline_large"].get("hbm_side_distance_kernel")}
+    if rank == 0:
         print(json.dumps(_strict(out)), flush=True)
     if world > 1:
         dist.barrier()

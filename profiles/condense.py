@@ -43,7 +43,7 @@ fetch_kb, write_kb = vals["FETCH_SIZE"], vals["WRITE_SIZE"]
 hbm = (fetch_kb * 2 + write_kb) * 1024
 summary = {
     "source": f"profiles/run_profiles.sh {tag}: rocprofv3 --pmc (one counter group per pass, --kernel-trace only) over "
-              "`python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --L <chosen>`; rows of the timed "
+              "`python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras --L <chosen>`; rows of the timed "
               f"launch (grid {nq} workgroups x 64)",
     "workload": {"nq": nq, "L": bench["config"]["L"], "beam_width": bench["config"]["beam_width"], "n": 1000000,
                  "dim": 128},

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Run on the GPU box (through gpurun): plain bench, kernel trace at the chosen L, separate PMC passes.
+# Run on the GPU box: the full bench line, kernel trace at the chosen L, separate PMC passes.
 # Usage: profiles/run_profiles.sh <tag>     -> gpurun_out/<tag>_*.{json,csv}
 set -u
 TAG=${1:-r01}
@@ -8,11 +8,11 @@ OUT=$R/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_$TAG && mkdir -p /tmp/prof_$TAG
-if [ -z "${SKIP_PLAIN:-}" ]; then python $R/bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; fi
+if [ -z "${SKIP_PLAIN:-}" ]; then python $R/bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; fi
 if [ -n "${FIXED_L:-}" ]; then L=$FIXED_L; else L=$(python -c "import json;print(json.load(open('$OUT/${TAG}_bench.json'))['config']['L'])"); fi
 # kernel trace with L fixed: every beam_search_kernel launch of this run is the timed workload
 if [ -z "${SKIP_TRACE:-}" ]; then
-rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG/trace -o t -- python $R/bench.py --steps 20 --no-cpu-baseline --no-extras --L $L --graph-cache /tmp/prof_$TAG/graph.bin \
+rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG/trace -o t -- python $R/bench.py --full --steps 20 --no-cpu-baseline --no-extras --L $L --graph-cache /tmp/prof_$TAG/graph.bin \
     > $OUT/${TAG}_bench_under_rocprof.json 2> /tmp/prof_$TAG/trace.err
 python $R/profiles/summarize_rocprof.py trace /tmp/prof_$TAG/trace/t_results.db $OUT/${TAG}_kernel_trace.csv 20
 fi
@@ -28,7 +28,7 @@ else
 fi
 for C in "$@"; do
     N=$(echo $C | tr ' ' '_' | cut -c1-40)
-    rocprofv3 --pmc $C --kernel-trace -d /tmp/prof_$TAG/pmc_$N -o p -- python $R/bench.py --steps 3 --warmup 1 \
+    rocprofv3 --pmc $C --kernel-trace -d /tmp/prof_$TAG/pmc_$N -o p -- python $R/bench.py --full --steps 3 --warmup 1 \
         --no-cpu-baseline --no-extras --L $L --graph-cache /tmp/prof_$TAG/graph.bin > /dev/null 2> /tmp/prof_$TAG/pmc_$N.err
     python $R/profiles/summarize_rocprof.py pmc /tmp/prof_$TAG/pmc_$N/p_results.db $OUT/${TAG}_pmc_$N.csv beam_search
 done

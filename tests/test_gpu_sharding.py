@@ -134,7 +134,7 @@ def test_bench_spawns_its_own_ranks(tmp_path):
     env = dict(os.environ, DANN_BENCH_ONE_DEVICE="1", OMP_NUM_THREADS="1")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--n", "60000",
-           "--nq", "4000", "--nq-shared", "1001", "--no-extras", "--no-cpu-baseline", "--max-batch", "4096"]
+           "--nq", "4000", "--nq-shared", "1001", "--full", "--no-extras", "--no-cpu-baseline", "--max-batch", "4096"]
     r = _run(cmd, env, timeout=900)
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     out = json.loads(line)
