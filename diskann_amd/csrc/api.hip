@@ -34,8 +34,11 @@ int32_t hip_fail(hipError_t e, const char* what) {
 }
 
 static uint32_t elem_size(int32_t dtype) { return dtype == DT_F32 ? 4u : dtype == DT_F16 ? 2u : 1u; }
-static uint32_t layer_bytes_of(int32_t dtype, uint32_t dim) { return dim * elem_size(dtype) + (dtype == DT_SQ8 ? 4u : 0u); }
-static bool valid_dtype(int32_t d) { return d >= 0 && d <= 5; }
+static uint32_t layer_bytes_of(int32_t dtype, uint32_t dim) {
+    if (dt_is_sq(dtype)) return sq_code_bytes(dtype, dim) + 4u;  // code bytes + the f32 compensation
+    return dim * elem_size(dtype);
+}
+static bool valid_dtype(int32_t d) { return (d >= 0 && d <= 5) || d == DT_SQ1 || d == DT_SQ4; }
 static bool valid_metric(int32_t m) { return m >= 0 && m <= 3; }
 
 // temporary device buffer with RAII
@@ -263,8 +266,9 @@ dann::IndexView dann_index::view() const {
     v.dtype = cfg.dtype;
     v.metric = cfg.metric;
     v.layer_bytes = layer_bytes;
-    {   // (1/255)^2 * scale^2 in f32, in the reference's order (vectors.rs:236-241, quantizer.rs:316-320)
-        const float ibs = 1.0f / 255.0f;
+    {   // (1/(2^bits - 1))^2 * scale^2 in f32, in the reference's order (scalar/mod.rs:129-135, vectors.rs:231-241,
+        // quantizer.rs:316-320)
+        const float ibs = 1.0f / (float)((1u << (dt_is_sq(cfg.dtype) ? sq_bits(cfg.dtype) : 8)) - 1u);
         const float bit_scale = ibs * ibs;
         const float scale_sq = cfg.sq_scale * cfg.sq_scale;
         v.sq_k = bit_scale * scale_sq;
@@ -329,8 +333,8 @@ int32_t dann_index_create(const dann_config* cfg, const void* start_rows, uint64
             set_error("metric %d is not defined for dtype %d", cfg->metric, cfg->dtype);
             return DANN_EUNSUPPORTED;
         }
-        if (cfg->dtype == DT_SQ8 && !(cfg->sq_scale > 0.0f)) {
-            set_error("DANN_SQ8 needs sq_scale > 0");
+        if (dt_is_sq(cfg->dtype) && !(cfg->sq_scale > 0.0f)) {
+            set_error("DANN_SQ8 / DANN_SQ4 / DANN_SQ1 need sq_scale > 0");
             return DANN_EINVAL;
         }
     }
@@ -1598,8 +1602,8 @@ int32_t dann_save_vectors_bin(const dann_index* idx, const char* path, uint32_t 
         set_error("cannot open %s for writing", path);
         return DANN_EINVAL;
     }
-    // `.bin`: dim counts elements of the stored type (SQ-8 rows are written as dim + 4 bytes)
-    const uint32_t dim = idx->cfg.dtype == DT_SQ8 ? idx->layer_bytes : idx->cfg.dim;
+    // `.bin`: dim counts elements of the stored type (scalar-quantised rows are written as their payload bytes)
+    const uint32_t dim = dt_is_sq(idx->cfg.dtype) ? idx->layer_bytes : idx->cfg.dim;
     if (fwrite(&n, 4, 1, out.f) != 1 || fwrite(&dim, 4, 1, out.f) != 1 ||
         (rows.size() && fwrite(rows.data(), 1, rows.size(), out.f) != rows.size())) {
         set_error("short write to %s", path);
@@ -1620,7 +1624,7 @@ int32_t dann_load_vectors_bin(dann_index* idx, const char* path, uint32_t first_
     }
     uint32_t n = 0, dim = 0;
     if (fread(&n, 4, 1, in.f) != 1 || fread(&dim, 4, 1, in.f) != 1) return DANN_ELENGTH;
-    const uint32_t want_dim = idx->cfg.dtype == DT_SQ8 ? idx->layer_bytes : idx->cfg.dim;
+    const uint32_t want_dim = dt_is_sq(idx->cfg.dtype) ? idx->layer_bytes : idx->cfg.dim;
     if (dim != want_dim) {
         set_error("data of dimension %u does not match full precision layer's dimension %u", dim, want_dim);
         return DANN_ELENGTH;

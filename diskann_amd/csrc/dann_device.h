@@ -23,7 +23,15 @@
 
 namespace dann {
 
-enum : int { DT_F32 = 0, DT_F16 = 1, DT_U8 = 2, DT_I8 = 3, DT_SQ8 = 4, DT_PQ = 5 };
+enum : int { DT_F32 = 0, DT_F16 = 1, DT_U8 = 2, DT_I8 = 3, DT_SQ8 = 4, DT_PQ = 5, DT_SQ1 = 17, DT_SQ4 = 20 };
+// scalar-quantised rows: SQ-8 (one byte per code) and the packed widths, whose dtype value is 16 + bits
+__host__ __device__ constexpr bool dt_is_sq(int dt) { return dt == DT_SQ8 || dt == DT_SQ4 || dt == DT_SQ1; }
+__host__ __device__ constexpr bool dt_is_packed(int dt) { return dt == DT_SQ4 || dt == DT_SQ1; }
+__host__ __device__ constexpr int sq_bits(int dt) { return dt == DT_SQ8 ? 8 : dt - 16; }
+// code bytes of a scalar-quantised row: ceil(dim * bits / 8); the f32 compensation follows them
+__host__ __device__ constexpr uint32_t sq_code_bytes(int dt, uint32_t dim) {
+    return (uint32_t)(((uint64_t)dim * (uint32_t)sq_bits(dt) + 7u) >> 3);
+}
 enum : int { M_COSINE = 0, M_IP = 1, M_L2 = 2, M_COSN = 3 };
 enum : int { OP_L2 = 0, OP_IP = 1, OP_COS = 2 };
 
@@ -714,6 +722,156 @@ __device__ __forceinline__ int group_norm_int_pre(const uint4& x) {
     return group8_sum(xx);
 }
 
+// ---- packed scalar-quantised rows (SQ4: two codes per byte, SQ1: eight), CompensatedVector<NBITS> with the Dense
+// permutation: element i occupies bits [i * bits, (i + 1) * bits) of the code bytes, little-endian within a byte.
+// Exact integer sums as above, so any lane assignment is bit-identical to the reference's loops
+// (diskann-quantization/src/bits/distances.rs:261-300 1-bit, :470-555 4-bit).
+//   SQ4: v_dot8_u32_u4 on whole dwords -- xy, and for L2 xx + yy - 2 xy modulo 2^32 as the u8 path does;
+//   SQ1: L2 = popcount(x ^ y), IP = popcount(x & y) (v_bcnt_u32_b32).
+// Shape.  A 128-d row is 64 (SQ4) or 16 (SQ1) code bytes: the 8-lane x 16-byte step of the u8 path would leave
+// half or seven eighths of the lanes idle.  A group is 4 lanes here, 16 rows per wavefront: a lane reads 16 bytes
+// (SQ4) or 4 bytes (SQ1) per step, a group 64 or 16 bytes -- 128 dimensions per step for both, one request per
+// lane for the common length.  Every load starts at a multiple of its own width below the code-byte count, so it
+// stays inside the row's 16-byte-aligned stride; bits at or beyond dim * bits (padding of the last byte, the
+// compensation, whatever follows inside the load) are masked to zero before they are used, in both operands.
+template <int BITS>
+struct PackedShape {
+    static constexpr int NW = BITS == 4 ? 4 : 1;  // dwords per lane per step
+    static constexpr int LB = 4 * NW, G = 4, STEP = G * LB;
+};
+template <int NW>
+struct PWords {
+    uint32_t w[NW];
+};
+template <int NW>
+__device__ __forceinline__ PWords<NW> packed_load(const uint8_t* p) {
+    if constexpr (NW == 4) {
+        const uint4 t = *reinterpret_cast<const uint4*>(p);
+        return {{t.x, t.y, t.z, t.w}};
+    } else {
+        return {{*reinterpret_cast<const uint32_t*>(p)}};
+    }
+}
+// keep the first `valid` bits of the lane's chunk (valid <= 0: none)
+template <int NW>
+__device__ __forceinline__ void packed_mask(PWords<NW>& a, int valid) {
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        const int nb = valid - 32 * i;
+        a.w[i] &= nb >= 32 ? 0xFFFFFFFFu : nb <= 0 ? 0u : ((1u << nb) - 1u);
+    }
+}
+__device__ __forceinline__ uint32_t group4_sum(uint32_t x) {
+    x += (uint32_t)dpp_i<DPP_XOR1>((int)x);
+    x += (uint32_t)dpp_i<DPP_XOR2>((int)x);
+    return x;
+}
+// U rows against one query (or stored row) `q`; rows[u] must be readable even where the caller discards out[u]
+// (the loads are unconditional, see group_distance_many).  Valid in every lane of the group.
+template <int BITS, int OP, int U>
+__device__ __forceinline__ void group_distance_packed(const uint8_t* __restrict__ q, const uint8_t* const (&rows)[U],
+                                                      int dim, int v, float (&out)[U]) {
+    static_assert(OP == OP_L2 || OP == OP_IP, "scalar-quantised rows: L2 and inner product");
+    using P = PackedShape<BITS>;
+    constexpr int NW = P::NW;
+    const int total_bits = dim * BITS, cb = (total_bits + 7) >> 3;
+    uint32_t t[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) t[u] = 0u;
+    for (int o0 = 0; o0 < cb; o0 += P::STEP) {
+        const int o = o0 + P::LB * v;
+        const bool in = o < cb;
+        const int ol = in ? o : 0;  // clamped: every request is issued, none behind a branch, all inside the row
+        const int valid = in ? total_bits - 8 * o : 0;
+        PWords<NW> y[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) y[u] = packed_load<NW>(rows[u] + ol);
+        PWords<NW> x = packed_load<NW>(q + ol);
+        packed_mask<NW>(x, valid);
+        uint32_t xx = 0u;
+        if constexpr (BITS == 4 && OP == OP_L2) {
+#pragma unroll
+            for (int i = 0; i < NW; ++i) xx = __builtin_amdgcn_udot8(x.w[i], x.w[i], xx, false);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if constexpr (OP == OP_L2) packed_mask<NW>(y[u], valid);  // (inner product: x's zeros suffice)
+            if constexpr (BITS == 4) {
+                uint32_t xy = 0u, yy = 0u;
+#pragma unroll
+                for (int i = 0; i < NW; ++i) {
+                    xy = __builtin_amdgcn_udot8(x.w[i], y[u].w[i], xy, false);
+                    if constexpr (OP == OP_L2) yy = __builtin_amdgcn_udot8(y[u].w[i], y[u].w[i], yy, false);
+                }
+                t[u] += OP == OP_L2 ? xx + yy - 2u * xy : xy;
+            } else {
+#pragma unroll
+                for (int i = 0; i < NW; ++i)
+                    t[u] += (uint32_t)__builtin_popcount(OP == OP_L2 ? x.w[i] ^ y[u].w[i] : x.w[i] & y[u].w[i]);
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) out[u] = (float)(int)group4_sum(t[u]);
+}
+template <int BITS, int OP>
+__device__ __forceinline__ float group_distance_packed1(const uint8_t* q, const uint8_t* row, int dim, int v) {
+    const uint8_t* const rows[1] = {row};
+    float out[1];
+    group_distance_packed<BITS, OP, 1>(q, rows, dim, v, out);
+    return out[0];
+}
+
+// Fixed 128-dimension packed rows -- exactly one step of group_distance_packed: 64 code bytes (SQ4, 16 per lane) or 16
+// (SQ1, 4 per lane), no tail and nothing to mask.  The lane's query dwords (`x`; SQ1 uses x.x) and, for SQ4 L2, the
+// query's squared norm (`xx`, the same for every row, summed once per search) stay in registers, as in
+// group_distance_int_pre; per row only xy and yy are accumulated.  rows[] must all be readable.
+template <int BITS>
+__device__ __forceinline__ uint4 packed_query_pre(const uint8_t* qs, int v) {
+    if constexpr (BITS == 4) {
+        return *reinterpret_cast<const uint4*>(qs + 16 * v);
+    } else {
+        return uint4{*reinterpret_cast<const uint32_t*>(qs + 4 * v), 0u, 0u, 0u};
+    }
+}
+template <int BITS>
+__device__ __forceinline__ int group_norm_packed_pre(const uint4& x) {
+    if constexpr (BITS != 4) return 0;  // (1-bit rows: L2 = popcount(x ^ y) needs no norm)
+    uint32_t xx = __builtin_amdgcn_udot8(x.x, x.x, 0u, false);
+    xx = __builtin_amdgcn_udot8(x.y, x.y, xx, false);
+    xx = __builtin_amdgcn_udot8(x.z, x.z, xx, false);
+    xx = __builtin_amdgcn_udot8(x.w, x.w, xx, false);
+    return (int)group4_sum(xx);
+}
+template <int BITS, int OP, int U>
+__device__ __forceinline__ void group_distance_packed_pre(const uint4& x, int xx, const uint8_t* const (&rows)[U], int v,
+                                                          float (&out)[U]) {
+    static_assert(OP == OP_L2 || OP == OP_IP, "scalar-quantised rows: L2 and inner product");
+    using P = PackedShape<BITS>;
+    constexpr int NW = P::NW;
+    PWords<NW> y[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) y[u] = packed_load<NW>(rows[u] + P::LB * v);
+    const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        uint32_t t = 0u;
+        if constexpr (BITS == 4) {
+            uint32_t xy = 0u, yy = 0u;
+#pragma unroll
+            for (int i = 0; i < NW; ++i) {
+                xy = __builtin_amdgcn_udot8(xs[i], y[u].w[i], xy, false);
+                if constexpr (OP == OP_L2) yy = __builtin_amdgcn_udot8(y[u].w[i], y[u].w[i], yy, false);
+            }
+            // |x - y|^2 = xx + sum(yy - 2 xy) modulo 2^32: one cross-lane sum
+            t = OP == OP_L2 ? (uint32_t)xx + group4_sum(yy - 2u * xy) : group4_sum(xy);
+        } else {
+            t = group4_sum((uint32_t)__builtin_popcount(OP == OP_L2 ? xs[0] ^ y[u].w[0] : xs[0] & y[u].w[0]));
+        }
+        out[u] = (float)(int)t;
+    }
+}
+
 // ---- dtype dispatch ------------------------------------------------------------------
 // Query-side staging type and group width for the *search* path
 // (Full<T>::query_distance, diskann-inmem/src/layers/full.rs:351-504):
@@ -724,9 +882,9 @@ __device__ __forceinline__ int group_norm_int_pre(const uint4& x) {
 //   f16 x f16: L2/IP/cosine all Strategy2x4 (NACC 2)  (simd.rs:989,1752,2591)
 template <int DT, int OP, bool PAIR>
 struct Scheme {
-    static constexpr bool kInt = (DT == DT_U8 || DT == DT_I8 || DT == DT_SQ8 || DT == DT_PQ);
+    static constexpr bool kInt = (DT == DT_U8 || DT == DT_I8 || DT == DT_PQ || dt_is_sq(DT));
     static constexpr int NACC = (OP == OP_COS) ? 2 : ((DT == DT_F16 && PAIR) ? 2 : 4);
-    static constexpr int G = kInt ? 8 : 2 * NACC;
+    static constexpr int G = dt_is_packed(DT) ? 4 : kInt ? 8 : 2 * NACC;  // (packed rows: PackedShape::G)
     // search-path gather: 2-byte rows use the wide layout (one lane per accumulator)
     static constexpr bool kWide = (DT == DT_F16) && !PAIR;
     static constexpr int GS = kWide ? NACC : G;
@@ -753,6 +911,14 @@ struct RowType<DT_SQ8> {
     using type = uint8_t;
 };
 template <>
+struct RowType<DT_SQ4> {
+    using type = uint8_t;
+};
+template <>
+struct RowType<DT_SQ1> {
+    using type = uint8_t;
+};
+template <>
 struct RowType<DT_PQ> {
     using type = uint8_t;
 };
@@ -760,7 +926,9 @@ struct RowType<DT_PQ> {
 // `q` is the staged query: f32 for float rows, raw bytes for integer rows.
 template <int DT, int OP, bool PAIR, int DIM, typename QT>
 __device__ __forceinline__ float group_distance(const QT* q, const uint8_t* row, int dim, int v) {
-    if constexpr (DT == DT_U8 || DT == DT_I8 || DT == DT_SQ8) {
+    if constexpr (dt_is_packed(DT)) {
+        return group_distance_packed1<sq_bits(DT), OP>(reinterpret_cast<const uint8_t*>(q), row, dim, v);
+    } else if constexpr (DT == DT_U8 || DT == DT_I8 || DT == DT_SQ8) {
         return group_distance_int<OP, DT == DT_I8>(reinterpret_cast<const uint8_t*>(q), row, dim, v);
     } else {
         using RT = typename RowType<DT>::type;
@@ -772,7 +940,9 @@ __device__ __forceinline__ float group_distance(const QT* q, const uint8_t* row,
 // stored row x stored row with the prune-path association (Scheme<DT, OP, true>)
 template <int DT, int OP>
 __device__ __forceinline__ float group_distance_rows(const uint8_t* x, const uint8_t* y, int dim, int v) {
-    if constexpr (DT == DT_U8 || DT == DT_I8 || DT == DT_SQ8) {
+    if constexpr (dt_is_packed(DT)) {
+        return group_distance_packed1<sq_bits(DT), OP>(x, y, dim, v);
+    } else if constexpr (DT == DT_U8 || DT == DT_I8 || DT == DT_SQ8) {
         return group_distance_int<OP, DT == DT_I8>(x, y, dim, v);
     } else {
         using RT = typename RowType<DT>::type;
@@ -787,7 +957,9 @@ __device__ __forceinline__ float group_distance_rows(const uint8_t* x, const uin
 template <int DT, int OP, bool PAIR, int U, bool WIDE = true, typename QT>
 __device__ __forceinline__ void group_distance_many(const QT* q, const uint8_t* const (&rows)[U],
                                                     const bool (&active)[U], int dim, int v, float (&out)[U]) {
-    if constexpr (DT == DT_U8 || DT == DT_I8 || DT == DT_SQ8) {
+    if constexpr (dt_is_packed(DT)) {
+        group_distance_packed<sq_bits(DT), OP, U>(reinterpret_cast<const uint8_t*>(q), rows, dim, v, out);
+    } else if constexpr (DT == DT_U8 || DT == DT_I8 || DT == DT_SQ8) {
         group_distance_int_multi<OP, DT == DT_I8, U>(reinterpret_cast<const uint8_t*>(q), rows, active, dim, v, out);
     } else {
         using RT = typename RowType<DT>::type;
@@ -849,9 +1021,9 @@ __device__ float simd_op_seq(const float* x, const float* y, uint32_t len) {
 }
 
 
-// scalar-quantiser parameters of an SQ-8 index
+// scalar-quantiser parameters of an SQ-8 / SQ4 / SQ1 index
 struct SqParams {
-    float k;              // (1/255)^2 * scale^2, evaluated in f32 in the reference's order
+    float k;              // (1/(2^bits - 1))^2 * scale^2, evaluated in f32 in the reference's order
     float shift_norm_sq;  // ||shift||^2
 };
 
@@ -860,13 +1032,14 @@ __device__ __forceinline__ float load_f32_unaligned(const uint8_t* p) {
     return __builtin_bit_cast(float, u);
 }
 
-// raw kernel result -> SimilarityScore.  Full-precision rows: PostOp; SQ-8 rows: the compensated
+// raw kernel result -> SimilarityScore.  Full-precision rows: PostOp; scalar-quantised rows: the compensated
 // epilogues of diskann-quantization/src/scalar/vectors.rs:216-245 (L2), :306-370 (IP),
-// :403-465 (CosineNormalized); `x`, `y` are the two rows (code bytes + trailing f32 compensation).
+// :403-465 (CosineNormalized); `x`, `y` are the two rows (code bytes + trailing f32 compensation, which sits at
+// the code-byte count: `dim` for SQ-8, ceil(dim * bits / 8) for the packed widths).
 template <int DT, int OP, bool NORM>
 __device__ __forceinline__ float finish_distance(float raw, const uint8_t* x, const uint8_t* y, uint32_t dim,
                                                  const SqParams& sq) {
-    if constexpr (DT != DT_SQ8) {
+    if constexpr (!dt_is_sq(DT)) {
         return post_op<OP, NORM>(raw);
     } else if constexpr (OP == OP_L2) {
         const float l2 = sq.k * raw;
@@ -874,15 +1047,16 @@ __device__ __forceinline__ float finish_distance(float raw, const uint8_t* x, co
         const float sim = 1.0f - l2 / 2.0f;
         return 1.0f - sim;
     } else {
-        const float cx = load_f32_unaligned(x + dim), cy = load_f32_unaligned(y + dim);
+        const uint32_t cb = sq_code_bytes(DT, dim);
+        const float cx = load_f32_unaligned(x + cb), cy = load_f32_unaligned(y + cb);
         const float r = __builtin_fmaf(sq.k, raw, sq.shift_norm_sq) + (cy + cx);
         return -r;
     }
 }
 
 // (dtype, metric) -> (OP, NORMALIZED).  Integers treat CosineNormalized as Cosine
-// (distance_provider.rs:274-297, full.rs:470,499); SQ-8 CosineNormalized is L2-based.
-// Returns false for unsupported combinations (SQ-8 has no plain Cosine).
+// (distance_provider.rs:274-297, full.rs:470,499); SQ-8 / SQ4 / SQ1 CosineNormalized is L2-based.
+// Returns false for unsupported combinations (scalar-quantised rows have no plain Cosine).
 __host__ __device__ inline bool resolve_metric(int dtype, int metric, int* op, bool* norm) {
     *norm = false;
     if (dtype == DT_PQ) {
@@ -890,7 +1064,7 @@ __host__ __device__ inline bool resolve_metric(int dtype, int metric, int* op, b
         if (metric == M_IP) { *op = OP_IP; return true; }
         return false;
     }
-    if (dtype == DT_SQ8) {
+    if (dt_is_sq(dtype)) {
         if (metric == M_L2) { *op = OP_L2; return true; }
         if (metric == M_IP) { *op = OP_IP; return true; }
         if (metric == M_COSN) { *op = OP_L2; *norm = true; return true; }

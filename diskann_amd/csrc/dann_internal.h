@@ -66,8 +66,8 @@ struct IndexView {
     uint32_t nstart;
     int32_t dtype;
     int32_t metric;
-    uint32_t layer_bytes;  // bytes of one row's payload (dim * sizeof(T); SQ-8: dim + 4)
-    float sq_k;            // SQ-8: (1/255)^2 * scale^2
+    uint32_t layer_bytes;  // bytes of one row's payload (dim * sizeof(T); SQ-8 / SQ4 / SQ1: code bytes + 4)
+    float sq_k;            // SQ-8 / SQ4 / SQ1: (1/(2^bits - 1))^2 * scale^2
     float sq_shift_norm_sq;
     // PQ rows (DT_PQ): codes of pq_chunks bytes; pivots 256 x dim f32; chunk offsets pq_chunks + 1
     const float* pq_pivots;
@@ -232,6 +232,8 @@ DANN_DECL_LAUNCH(f16);
 DANN_DECL_LAUNCH(u8);
 DANN_DECL_LAUNCH(i8);
 DANN_DECL_LAUNCH(sq8);
+DANN_DECL_LAUNCH(sq4);
+DANN_DECL_LAUNCH(sq1);
 DANN_DECL_LAUNCH(pq);
 // search_diverse.hip: dann_diverse_search_batch on device-resident queries and outputs (host-synchronous on `stream`)
 int32_t diverse_search_device(dann_index* idx, hipStream_t stream, const void* d_queries, uint32_t nq, uint32_t l_value,

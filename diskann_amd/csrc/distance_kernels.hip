@@ -177,7 +177,7 @@ int32_t launch_rerank_t(const IndexView& ix, const void* q, uint32_t nq, const u
                         uint32_t k, uint32_t* oi, float* od, hipStream_t stream) {
     uint32_t pcap = 64;
     while (pcap < stride) pcap <<= 1;
-    const bool is_int = DT == DT_U8 || DT == DT_I8 || DT == DT_SQ8;
+    const bool is_int = DT == DT_U8 || DT == DT_I8 || dt_is_sq(DT);
     const size_t lds = (size_t)pcap * 16 + (((is_int ? ix.layer_bytes : ix.dim * 4u) + 15u) & ~15u);
     auto kern = rerank_kernel<DT, OP, NORM>;
     if (lds > 64 * 1024) {
@@ -198,7 +198,7 @@ int32_t launch_rerank_dt(const IndexView& ix, const void* q, uint32_t nq, const 
     bool norm;
     if (!resolve_metric(ix.dtype, ix.metric, &op, &norm)) return DANN_EUNSUPPORTED;
     if (op == OP_L2) {
-        if constexpr (DT == DT_SQ8) {
+        if constexpr (dt_is_sq(DT)) {
             if (norm) return launch_rerank_t<DT, OP_L2, true>(ix, q, nq, cand, stride, k, oi, od, stream);
         }
         return launch_rerank_t<DT, OP_L2, false>(ix, q, nq, cand, stride, k, oi, od, stream);
@@ -209,7 +209,7 @@ int32_t launch_rerank_dt(const IndexView& ix, const void* q, uint32_t nq, const 
         }
         return launch_rerank_t<DT, OP_IP, false>(ix, q, nq, cand, stride, k, oi, od, stream);
     }
-    if constexpr (DT != DT_SQ8) return launch_rerank_t<DT, OP_COS, false>(ix, q, nq, cand, stride, k, oi, od, stream);
+    if constexpr (!dt_is_sq(DT)) return launch_rerank_t<DT, OP_COS, false>(ix, q, nq, cand, stride, k, oi, od, stream);
     return DANN_EUNSUPPORTED;
 }
 
@@ -229,7 +229,9 @@ __global__ __launch_bounds__(256) void pair_kernel(const uint8_t* xbase, const u
     const uint8_t* x = xbase + (uint64_t)(a ? a[p] : p) * xstride;
     const uint8_t* y = ybase + (uint64_t)(b ? b[p] : p) * ystride;
     float d;
-    if constexpr (S::kInt) {
+    if constexpr (dt_is_packed(DT)) {
+        d = group_distance_packed1<sq_bits(DT), OP>(x, y, (int)dim, v);
+    } else if constexpr (S::kInt) {
         d = group_distance_int<OP, DT == DT_I8>(x, y, (int)dim, v);
     } else {
         d = group_distance_raw<S::NACC, OP, 0>(reinterpret_cast<const RT*>(x), reinterpret_cast<const RT*>(y), (int)dim,
@@ -262,7 +264,7 @@ int32_t launch_pairs_dt(int32_t metric, const uint8_t* xb, const uint8_t* yb, ui
         return DANN_EUNSUPPORTED;
     }
     if (op == OP_L2) {
-        if constexpr (DT == DT_SQ8) {
+        if constexpr (dt_is_sq(DT)) {
             if (norm) return launch_pairs_t<DT, OP_L2, true>(xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
         }
         return launch_pairs_t<DT, OP_L2, false>(xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
@@ -273,7 +275,7 @@ int32_t launch_pairs_dt(int32_t metric, const uint8_t* xb, const uint8_t* yb, ui
         }
         return launch_pairs_t<DT, OP_IP, false>(xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
     }
-    if constexpr (DT != DT_SQ8) return launch_pairs_t<DT, OP_COS, false>(xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
+    if constexpr (!dt_is_sq(DT)) return launch_pairs_t<DT, OP_COS, false>(xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
     return DANN_EUNSUPPORTED;
 }
 
@@ -287,6 +289,8 @@ int32_t launch_pairs_any(int32_t dtype, int32_t metric, const uint8_t* xb, const
         case DT_U8: return launch_pairs_dt<DT_U8>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
         case DT_I8: return launch_pairs_dt<DT_I8>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
         case DT_SQ8: return launch_pairs_dt<DT_SQ8>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
+        case DT_SQ4: return launch_pairs_dt<DT_SQ4>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
+        case DT_SQ1: return launch_pairs_dt<DT_SQ1>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
     }
     set_error("bad dtype %d", dtype);
     return DANN_EINVAL;
@@ -295,7 +299,7 @@ int32_t launch_pairs_any(int32_t dtype, int32_t metric, const uint8_t* xb, const
 template <int DT, int OP, bool NORM, int DIM>
 int32_t launch_eb_t(const IndexView& ix, const void* q, uint32_t nq, uint32_t chunks, const uint32_t* ids,
                     const uint64_t* offsets, float* out, hipStream_t stream) {
-    const bool is_int = DT == DT_U8 || DT == DT_I8 || DT == DT_SQ8;
+    const bool is_int = DT == DT_U8 || DT == DT_I8 || dt_is_sq(DT);
     size_t lds = ((is_int ? ix.layer_bytes : ix.dim * 4u) + 15u) & ~15u;
     hipLaunchKernelGGL((expand_beam_kernel<DT, OP, NORM, DIM>), dim3(nq, chunks), dim3(kWave), lds, stream, ix, q, ids,
                        offsets, out);
@@ -317,7 +321,7 @@ int32_t launch_eb_dt(const IndexView& ix, const void* q, uint32_t nq, uint32_t c
         if constexpr (DT == DT_F32) {
             if (ix.dim == 128) return launch_eb_t<DT, OP_L2, false, 128>(ix, q, nq, chunks, ids, offsets, out, stream);
         }
-        if constexpr (DT == DT_SQ8) {
+        if constexpr (dt_is_sq(DT)) {
             if (norm) return launch_eb_t<DT, OP_L2, true, 0>(ix, q, nq, chunks, ids, offsets, out, stream);
         }
         return launch_eb_t<DT, OP_L2, false, 0>(ix, q, nq, chunks, ids, offsets, out, stream);
@@ -328,7 +332,7 @@ int32_t launch_eb_dt(const IndexView& ix, const void* q, uint32_t nq, uint32_t c
         }
         return launch_eb_t<DT, OP_IP, false, 0>(ix, q, nq, chunks, ids, offsets, out, stream);
     }
-    if constexpr (DT != DT_SQ8) return launch_eb_t<DT, OP_COS, false, 0>(ix, q, nq, chunks, ids, offsets, out, stream);
+    if constexpr (!dt_is_sq(DT)) return launch_eb_t<DT, OP_COS, false, 0>(ix, q, nq, chunks, ids, offsets, out, stream);
     return DANN_EUNSUPPORTED;
 }
 
@@ -349,6 +353,8 @@ int32_t launch_expand_beam(const IndexView& ix, const void* d_queries, uint32_t 
         case DT_U8: return launch_eb_dt<DT_U8>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
         case DT_I8: return launch_eb_dt<DT_I8>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
         case DT_SQ8: return launch_eb_dt<DT_SQ8>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
+        case DT_SQ4: return launch_eb_dt<DT_SQ4>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
+        case DT_SQ1: return launch_eb_dt<DT_SQ1>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
     }
     set_error("bad dtype %d", ix.dtype);
     return DANN_EINVAL;
@@ -367,6 +373,8 @@ int32_t launch_rerank(const IndexView& ix, const void* d_queries, uint32_t nq, c
         case DT_U8: return launch_rerank_dt<DT_U8>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
         case DT_I8: return launch_rerank_dt<DT_I8>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
         case DT_SQ8: return launch_rerank_dt<DT_SQ8>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
+        case DT_SQ4: return launch_rerank_dt<DT_SQ4>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
+        case DT_SQ1: return launch_rerank_dt<DT_SQ1>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
     }
     return DANN_EINVAL;
 }

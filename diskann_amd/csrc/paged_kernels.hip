@@ -308,7 +308,7 @@ __global__ __launch_bounds__(kWave) void paged_kernel(PagedArgs a) {
 
 template <int DT, int OP, bool NORM>
 int32_t launch_paged_t(const PagedArgs& a, hipStream_t stream) {
-    const bool is_int = DT == DT_U8 || DT == DT_I8 || DT == DT_SQ8;
+    const bool is_int = DT == DT_U8 || DT == DT_I8 || dt_is_sq(DT);
     const uint32_t rc = (a.ix.max_degree + 63u) & ~63u;
     const size_t lds = (size_t)rc * 8 + (((is_int ? a.ix.layer_bytes : a.ix.dim * 4u) + 15u) & ~15u);
     auto kern = paged_kernel<DT, OP, NORM>;
@@ -329,7 +329,7 @@ int32_t launch_paged_dt(const PagedArgs& a, hipStream_t stream) {
     bool norm;
     if (!resolve_metric(a.ix.dtype, a.ix.metric, &op, &norm)) return DANN_EUNSUPPORTED;
     if (op == OP_L2) {
-        if constexpr (DT == DT_SQ8) {
+        if constexpr (dt_is_sq(DT)) {
             if (norm) return launch_paged_t<DT, OP_L2, true>(a, stream);
         }
         return launch_paged_t<DT, OP_L2, false>(a, stream);
@@ -340,7 +340,7 @@ int32_t launch_paged_dt(const PagedArgs& a, hipStream_t stream) {
         }
         return launch_paged_t<DT, OP_IP, false>(a, stream);
     }
-    if constexpr (DT != DT_SQ8) return launch_paged_t<DT, OP_COS, false>(a, stream);
+    if constexpr (!dt_is_sq(DT)) return launch_paged_t<DT, OP_COS, false>(a, stream);
     return DANN_EUNSUPPORTED;
 }
 
@@ -351,6 +351,8 @@ int32_t launch_paged(const PagedArgs& a, hipStream_t stream) {
         case DT_U8: return launch_paged_dt<DT_U8>(a, stream);
         case DT_I8: return launch_paged_dt<DT_I8>(a, stream);
         case DT_SQ8: return launch_paged_dt<DT_SQ8>(a, stream);
+        case DT_SQ4: return launch_paged_dt<DT_SQ4>(a, stream);
+        case DT_SQ1: return launch_paged_dt<DT_SQ1>(a, stream);
     }
     set_error("paged search is not defined for dtype %d", a.ix.dtype);
     return DANN_EUNSUPPORTED;

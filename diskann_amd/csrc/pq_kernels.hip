@@ -58,29 +58,42 @@ __global__ __launch_bounds__(256) void pq_scan_kernel(const float* lut, uint32_t
     }
 }
 
-// ScalarQuantizer::compress_into, 8 bits (quantizer.rs:189-236, 395-430); one thread per vector:
-// the compensation is a sequential FMA chain over the dimensions.
-__global__ void sq8_compress_kernel(const float* x, uint32_t n, uint32_t dim, const float* shift, float scale,
-                                    uint8_t* out) {
+// ScalarQuantizer::compress_into::<BITS> (quantizer.rs:189-238, 395-430); one thread per vector: the compensation
+// is a sequential FMA chain over the dimensions.  Codes are packed densely, element i at bits [i * BITS, (i + 1) * BITS)
+// of the code bytes, little-endian within a byte (scalar/vectors.rs:128-151); the padding bits of the last byte are zero.
+template <int BITS>
+__global__ void sq_compress_kernel(const float* x, uint32_t n, uint32_t dim, const float* shift, float scale,
+                                   uint8_t* out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float inverse_scale = 255.0f / scale;
+    constexpr float kMax = (float)((1 << BITS) - 1);
+    constexpr int PER = 8 / BITS;  // codes per byte
+    const float inverse_scale = kMax / scale;
+    const uint32_t cb = (dim * BITS + 7u) / 8u;
     const float* v = x + (uint64_t)i * dim;
-    uint8_t* o = out + (uint64_t)i * (dim + 4);
+    uint8_t* o = out + (uint64_t)i * (cb + 4);
     float dot = 0.0f;
-    for (uint32_t d = 0; d < dim; ++d) {
-        float c = (v[d] - shift[d]) * inverse_scale;
-        c = c < 0.0f ? 0.0f : (c > 255.0f ? 255.0f : c);  // NaN stays NaN -> code 0 (`as u8`)
-        c = roundf(c);
-        dot = __builtin_fmaf(c, shift[d], dot);
-        o[d] = (c != c) ? 0 : (uint8_t)c;
+    for (uint32_t b = 0; b < cb; ++b) {
+        uint32_t byte = 0;
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            const uint32_t d = b * PER + j;
+            if (d < dim) {
+                float c = (v[d] - shift[d]) * inverse_scale;
+                c = c < 0.0f ? 0.0f : (c > kMax ? kMax : c);  // NaN stays NaN -> code 0 (`as u8`)
+                c = roundf(c);
+                dot = __builtin_fmaf(c, shift[d], dot);
+                byte |= ((c != c) ? 0u : (uint32_t)c) << (j * BITS);
+            }
+        }
+        o[b] = (uint8_t)byte;
     }
-    const float comp = scale * (1.0f / 255.0f) * dot;
+    const float comp = scale * (1.0f / kMax) * dot;
     const uint32_t u = __builtin_bit_cast(uint32_t, comp);
-    o[dim] = (uint8_t)u;
-    o[dim + 1] = (uint8_t)(u >> 8);
-    o[dim + 2] = (uint8_t)(u >> 16);
-    o[dim + 3] = (uint8_t)(u >> 24);
+    o[cb] = (uint8_t)u;
+    o[cb + 1] = (uint8_t)(u >> 8);
+    o[cb + 2] = (uint8_t)(u >> 16);
+    o[cb + 3] = (uint8_t)(u >> 24);
 }
 
 // kmeans::square_norm (diskann-quantization/src/algorithms/kmeans/common.rs:8-62): four 8-lane accumulators over
@@ -1038,24 +1051,42 @@ extern "C" int32_t dann_sq8_train(int32_t device, const float* data, uint64_t n,
     return DANN_OK;
 } DANN_CATCH_ALL
 
-extern "C" int32_t dann_sq8_compress(int32_t device, const float* x, uint32_t n, uint32_t dim, const float* shift,
-                                     float scale, void* out) try {
+extern "C" int32_t dann_sq_compress(int32_t device, int32_t bits, const float* x, uint32_t n, uint32_t dim,
+                                    const float* shift, float scale, void* out) try {
     using namespace dann;
+    if (bits != 1 && bits != 4 && bits != 8) {
+        set_error("dann_sq_compress: bits must be 1, 4 or 8 (got %d)", bits);
+        return DANN_EINVAL;
+    }
     if (!x || !shift || !out || dim == 0 || !(scale > 0.0f)) return DANN_EINVAL;
     if (n == 0) return DANN_OK;
     if (device >= 0) DANN_HIP(hipSetDevice(device));
+    const size_t row = ((size_t)dim * (uint32_t)bits + 7u) / 8u + 4u;
     Buf dx, ds, dout;
     DANN_HIP(hipMalloc(&dx.p, (size_t)n * dim * 4));
     DANN_HIP(hipMalloc(&ds.p, (size_t)dim * 4));
-    DANN_HIP(hipMalloc(&dout.p, (size_t)n * (dim + 4)));
+    DANN_HIP(hipMalloc(&dout.p, (size_t)n * row));
     DANN_HIP(hipMemcpy(dx.p, x, (size_t)n * dim * 4, hipMemcpyHostToDevice));
     DANN_HIP(hipMemcpy(ds.p, shift, (size_t)dim * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(sq8_compress_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, (const float*)dx.p, n, dim,
-                       (const float*)ds.p, scale, (uint8_t*)dout.p);
+    const dim3 grid((n + 255) / 256), block(256);
+    if (bits == 8)
+        hipLaunchKernelGGL(sq_compress_kernel<8>, grid, block, 0, 0, (const float*)dx.p, n, dim, (const float*)ds.p, scale,
+                           (uint8_t*)dout.p);
+    else if (bits == 4)
+        hipLaunchKernelGGL(sq_compress_kernel<4>, grid, block, 0, 0, (const float*)dx.p, n, dim, (const float*)ds.p, scale,
+                           (uint8_t*)dout.p);
+    else
+        hipLaunchKernelGGL(sq_compress_kernel<1>, grid, block, 0, 0, (const float*)dx.p, n, dim, (const float*)ds.p, scale,
+                           (uint8_t*)dout.p);
     DANN_HIP(hipGetLastError());
-    DANN_HIP(hipMemcpy(out, dout.p, (size_t)n * (dim + 4), hipMemcpyDeviceToHost));
+    DANN_HIP(hipMemcpy(out, dout.p, (size_t)n * row, hipMemcpyDeviceToHost));
     return DANN_OK;
 } DANN_CATCH_ALL
+
+extern "C" int32_t dann_sq8_compress(int32_t device, const float* x, uint32_t n, uint32_t dim, const float* shift,
+                                     float scale, void* out) {
+    return dann_sq_compress(device, 8, x, n, dim, shift, scale, out);
+}
 
 // k-means++ for every chunk in lockstep: per centre one update launch over all (row, chunk) pairs, the sequential f64
 // totals, one host round trip for the caller's threshold draws, the sequential selection, the commit.

@@ -43,7 +43,7 @@ int32_t dispatch(const IndexView& ix, const Args& a, uint32_t grid, size_t lds, 
 #define DANN_CASE(DT)                                                                                  \
     case DT:                                                                                           \
         if (op == OP_L2) {                                                                             \
-            if constexpr (DT == DT_SQ8) {                                                              \
+            if constexpr (dt_is_sq(DT)) {                                                              \
                 if (norm) return Launcher<DT, OP_L2, true>::run(a, grid, lds, stream);                 \
             }                                                                                          \
             return Launcher<DT, OP_L2, false>::run(a, grid, lds, stream);                              \
@@ -54,7 +54,7 @@ int32_t dispatch(const IndexView& ix, const Args& a, uint32_t grid, size_t lds, 
             }                                                                                          \
             return Launcher<DT, OP_IP, false>::run(a, grid, lds, stream);                              \
         }                                                                                              \
-        if constexpr (DT != DT_SQ8) return Launcher<DT, OP_COS, false>::run(a, grid, lds, stream);     \
+        if constexpr (!dt_is_sq(DT)) return Launcher<DT, OP_COS, false>::run(a, grid, lds, stream);     \
         return DANN_EUNSUPPORTED;
     switch (ix.dtype) {
         DANN_CASE(DT_F32)
@@ -62,6 +62,8 @@ int32_t dispatch(const IndexView& ix, const Args& a, uint32_t grid, size_t lds, 
         DANN_CASE(DT_U8)
         DANN_CASE(DT_I8)
         DANN_CASE(DT_SQ8)
+        DANN_CASE(DT_SQ4)
+        DANN_CASE(DT_SQ1)
     }
 #undef DANN_CASE
     set_error("bad dtype %d", ix.dtype);

@@ -286,7 +286,7 @@ int32_t launch_dv_dt(const DiverseArgs& a, size_t lds, hipStream_t st) {
         return DANN_EUNSUPPORTED;
     }
     if (op == OP_L2) {
-        if constexpr (DT == DT_SQ8) {
+        if constexpr (dt_is_sq(DT)) {
             if (norm) return launch_dv<DT, OP_L2, true>(a, lds, st);
         }
         return launch_dv<DT, OP_L2, false>(a, lds, st);
@@ -297,7 +297,7 @@ int32_t launch_dv_dt(const DiverseArgs& a, size_t lds, hipStream_t st) {
         }
         return launch_dv<DT, OP_IP, false>(a, lds, st);
     }
-    if constexpr (DT != DT_SQ8) return launch_dv<DT, OP_COS, false>(a, lds, st);
+    if constexpr (!dt_is_sq(DT)) return launch_dv<DT, OP_COS, false>(a, lds, st);
     return DANN_EUNSUPPORTED;
 }
 
@@ -308,6 +308,8 @@ int32_t launch_dv_any(const DiverseArgs& a, size_t lds, hipStream_t st) {
         case DT_U8: return launch_dv_dt<DT_U8>(a, lds, st);
         case DT_I8: return launch_dv_dt<DT_I8>(a, lds, st);
         case DT_SQ8: return launch_dv_dt<DT_SQ8>(a, lds, st);
+        case DT_SQ4: return launch_dv_dt<DT_SQ4>(a, lds, st);
+        case DT_SQ1: return launch_dv_dt<DT_SQ1>(a, lds, st);
     }
     set_error("diverse search: rows of dtype %d are not supported", a.ix.dtype);
     return DANN_EUNSUPPORTED;

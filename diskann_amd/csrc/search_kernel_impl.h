@@ -58,7 +58,7 @@ __host__ __device__ inline uint32_t lds_queue_entries(const SearchArgs& a) {
 // bytes of the staged query: f32 vector (float rows), raw bytes (integer rows), lookup table (PQ rows)
 __host__ __device__ inline uint32_t query_lds_bytes(const IndexView& ix) {
     if (ix.dtype == DT_PQ) return ix.pq_chunks * 1024u;
-    if (ix.dtype == DT_U8 || ix.dtype == DT_I8 || ix.dtype == DT_SQ8) return ix.layer_bytes;
+    if (ix.dtype == DT_U8 || ix.dtype == DT_I8 || dt_is_sq(ix.dtype)) return ix.layer_bytes;
     return ix.dim * 4u;
 }
 
@@ -1042,7 +1042,8 @@ __device__ __forceinline__ void beam_search_one(const SearchArgs& a, const uint3
                                 : (((W * R + 63u) & ~63u) > ((ix.nstart + 63u) & ~63u) ? ((W * R + 63u) & ~63u)
                                                                                        : ((ix.nstart + 63u) & ~63u));
     // fixed-length instantiations know the staged query's size (f32 vector, raw bytes, SQ-8: bytes + compensation)
-    const uint32_t qbytes = DIM > 0 ? (kInt ? (uint32_t)DIM + (DT == DT_SQ8 ? 4u : 0u) : (uint32_t)DIM * 4u)
+    const uint32_t qbytes = DIM > 0 ? (dt_is_sq(DT) ? sq_code_bytes(DT, (uint32_t)DIM) + 4u
+                                                    : kInt ? (uint32_t)DIM : (uint32_t)DIM * 4u)
                                     : query_lds_bytes(ix);
     const SqParams sqp{ix.sq_k, ix.sq_shift_norm_sq};
     const SearchLds L = search_lds_layout(a.ht_entries, cmax, lds_queue_entries(a), qbytes, TEAM > 1);
@@ -1115,9 +1116,14 @@ __device__ __forceinline__ void beam_search_one(const SearchArgs& a, const uint3
     uint4 xqi = {0u, 0u, 0u, 0u};
     int xx_pre = 0;
     if constexpr (DIM > 0 && kInt) {
-        static_assert(!kInt || DIM == 0 || DIM == 128, "integer rows: only the 128-byte length is specialised");
-        xqi = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(qs) + 16 * v);
-        xx_pre = group_norm_int_pre<DT == DT_I8>(xqi);
+        static_assert(!kInt || DIM == 0 || DIM == 128, "integer rows: only the 128-element length is specialised");
+        if constexpr (dt_is_packed(DT)) {  // (64 or 16 code bytes over the group's 4 lanes)
+            xqi = packed_query_pre<sq_bits(DT)>(reinterpret_cast<const uint8_t*>(qs), v);
+            xx_pre = group_norm_packed_pre<sq_bits(DT)>(xqi);
+        } else {
+            xqi = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(qs) + 16 * v);
+            xx_pre = group_norm_int_pre<DT == DT_I8>(xqi);
+        }
     }
 
     // ---- queue state: entry p at lane p % 64, slot p / 64 ------------------------------
@@ -1273,7 +1279,8 @@ __device__ __forceinline__ void beam_search_one(const SearchArgs& a, const uint3
 #pragma unroll
                     for (int u = 0; u < U; ++u) tg[u] = (act[u] && v == 0) ? rows[u][tag_off] : (uint8_t)255;
                 }
-                group_distance_int_pre<OP, DT == DT_I8, U>(xqi, xx_pre, rows, v, out);
+                if constexpr (dt_is_packed(DT)) group_distance_packed_pre<sq_bits(DT), OP, U>(xqi, xx_pre, rows, v, out);
+                else group_distance_int_pre<OP, DT == DT_I8, U>(xqi, xx_pre, rows, v, out);
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     uint32_t c = c0 + u * GROUPS + g;
@@ -2483,7 +2490,7 @@ constexpr int kTeam = DANN_TEAM_WAVES;  // wavefronts per query in the latency r
 
 template <int DT, int OP, bool NORM, int QS, int DIM, int MODE, int LOOP = 0, int TEAM = 1, bool HT16 = false>
 int32_t launch_one(const SearchArgs& a, size_t lds, hipStream_t stream, int* regs_out) {
-    if constexpr (MODE == kModePlain && LOOP == 0 && TEAM == 1 && DIM > 0 && QS <= 4 && DT != DT_PQ) {
+    if constexpr (MODE == kModePlain && LOOP == 0 && TEAM == 1 && DIM > 0 && QS <= 4 && DT != DT_PQ && !dt_is_packed(DT)) {
         if (a.team && !a.srv.ring && !a.grid && !regs_out)
             return launch_one<DT, OP, NORM, QS, DIM, MODE, 0, kTeam>(a, lds, stream, regs_out);
     }
@@ -2565,6 +2572,13 @@ int32_t launch_dt(const SearchArgs& a, uint32_t qcap, size_t lds, hipStream_t st
                 return launch_qs<DT, OP_L2, true, 0>(a, qcap, lds, stream, regs_out);
             }
         }
+        if constexpr (dt_is_packed(DT)) {  // (packed rows: no team instantiations, team_shape)
+            if (norm) {
+                if (a.ix.dim == 128) return launch_qs<DT, OP_L2, true, 128>(a, qcap, lds, stream, regs_out);
+                return launch_qs<DT, OP_L2, true, 0>(a, qcap, lds, stream, regs_out);
+            }
+            if (a.ix.dim == 128) return launch_qs<DT, OP_L2, false, 128>(a, qcap, lds, stream, regs_out);
+        }
         if constexpr (DT == DT_U8 || DT == DT_I8 || DT == DT_SQ8) {  // 128-byte integer rows (C-int8)
             if (a.ix.dim == 128) return launch_qs<DT, OP_L2, false, 128>(a, qcap, lds, stream, regs_out);
         }
@@ -2574,7 +2588,7 @@ int32_t launch_dt(const SearchArgs& a, uint32_t qcap, size_t lds, hipStream_t st
         if constexpr (DT == DT_F32 || DT == DT_F16) {
             if (norm) return launch_qs<DT, OP_IP, true, 0>(a, qcap, lds, stream, regs_out);
         }
-        if constexpr (DT == DT_U8 || DT == DT_I8 || DT == DT_SQ8) {
+        if constexpr (DT == DT_U8 || DT == DT_I8 || dt_is_sq(DT)) {
             if (a.ix.dim == 128) return launch_qs<DT, OP_IP, false, 128>(a, qcap, lds, stream, regs_out);
         }
         return launch_qs<DT, OP_IP, false, 0>(a, qcap, lds, stream, regs_out);
@@ -2582,7 +2596,7 @@ int32_t launch_dt(const SearchArgs& a, uint32_t qcap, size_t lds, hipStream_t st
     if constexpr (DT == DT_U8 || DT == DT_I8) {
         if (a.ix.dim == 128) return launch_qs<DT, OP_COS, false, 128>(a, qcap, lds, stream, regs_out);
     }
-    if constexpr (DT != DT_SQ8 && DT != DT_PQ) return launch_qs<DT, OP_COS, false, 0>(a, qcap, lds, stream, regs_out);
+    if constexpr (!dt_is_sq(DT) && DT != DT_PQ) return launch_qs<DT, OP_COS, false, 0>(a, qcap, lds, stream, regs_out);
     return DANN_EUNSUPPORTED;
 }
 
@@ -2592,7 +2606,7 @@ inline bool team_shape(const SearchArgs& a) {
     int op;
     bool norm;
     const int dt = a.ix.dtype;
-    if (!plain_mode(a) || dt == DT_PQ || a.ix.dim != 128u || !resolve_metric(dt, a.ix.metric, &op, &norm)) return false;
+    if (!plain_mode(a) || dt == DT_PQ || dt_is_packed(dt) || a.ix.dim != 128u || !resolve_metric(dt, a.ix.metric, &op, &norm)) return false;
     if (std::max(a.l_value + a.ix.nstart, a.qcap_max) > 256u) return false;
     const bool ints = dt == DT_U8 || dt == DT_I8 || dt == DT_SQ8;
     if (op == OP_L2) return true;

@@ -245,6 +245,8 @@ int32_t launch_search(const SearchArgs& a, hipStream_t stream, int* regs_out) {
         case DT_U8: return launch_search_u8(a, qcap, lds, stream, regs_out);
         case DT_I8: return launch_search_i8(a, qcap, lds, stream, regs_out);
         case DT_SQ8: return launch_search_sq8(a, qcap, lds, stream, regs_out);
+        case DT_SQ4: return launch_search_sq4(a, qcap, lds, stream, regs_out);
+        case DT_SQ1: return launch_search_sq1(a, qcap, lds, stream, regs_out);
         case DT_PQ: return launch_search_pq(a, qcap, lds, stream, regs_out);
     }
     set_error("bad dtype %d", a.ix.dtype);

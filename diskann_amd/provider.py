@@ -14,10 +14,10 @@ import os
 import numpy as np
 
 from . import _ffi
-from ._ffi import (BuildConfig, Config, DannError, SearchStats, check, F32, F16, U8, I8, SQ8, PQ, COSINE, INNER_PRODUCT, L2,
+from ._ffi import (BuildConfig, Config, DannError, SearchStats, check, F32, F16, U8, I8, SQ8, SQ1, SQ4, PQ, COSINE, INNER_PRODUCT, L2,
                    COSINE_NORMALIZED, IBC_ALL, IBC_NONE)
 
-NP_DTYPE = {F32: np.float32, F16: np.float16, U8: np.uint8, I8: np.int8, SQ8: np.uint8, PQ: np.uint8}
+NP_DTYPE = {F32: np.float32, F16: np.float16, U8: np.uint8, I8: np.int8, SQ8: np.uint8, SQ1: np.uint8, SQ4: np.uint8, PQ: np.uint8}
 FILTER_INLINE, FILTER_MULTIHOP = 1, 2  # dann.h DANN_FILTER_*
 STATS_DTYPE = np.dtype([("cmps", np.uint32), ("hops", np.uint32), ("result_count", np.uint32), ("status", np.uint32),
                         ("written", np.uint32)])
@@ -85,7 +85,8 @@ class Provider:
                  sq_scale=0.0, sq_shift_norm_sq=0.0, pq_pivots=None, pq_offsets=None, inline_tags=False):
         self.dtype, self.metric, self.dim = dtype, metric, int(dim)
         self.capacity, self.max_degree = int(capacity), int(max_degree)
-        self.row_elems = self.dim + 4 if dtype == SQ8 else self.dim  # SQ-8 rows carry a trailing f32 compensation
+        # scalar-quantised rows are their payload bytes: the code bytes and a trailing f32 compensation
+        self.row_elems = int(_ffi.lib().dann_layer_bytes(dtype, self.dim)) if dtype in (SQ8, SQ4, SQ1) else self.dim
         self.query_dtype, self.query_elems = NP_DTYPE[dtype], self.row_elems
         pq_chunks = 0
         if dtype == PQ:  # rows are PQ codes, queries stay full-precision f32
@@ -648,6 +649,18 @@ def sq8_compress(x, shift, scale, device=-1):
     out = np.empty((x.shape[0], x.shape[1] + 4), np.uint8)
     check(_ffi.lib().dann_sq8_compress(device, _p(x), x.shape[0], x.shape[1], _p(shift), float(scale), _p(out)),
           "dann_sq8_compress")
+    return out
+
+
+def sq_compress(x, shift, scale, bits, device=-1):
+    """ScalarQuantizer::compress_into::<bits> on the GPU, bits in (1, 4, 8): rows of ceil(dim * bits / 8) packed code
+    bytes + f32 compensation (SQ1 / SQ4 / SQ8 rows)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    x = x.reshape(-1, x.shape[-1])
+    shift = np.ascontiguousarray(shift, dtype=np.float32)
+    out = np.empty((x.shape[0], (x.shape[1] * int(bits) + 7) // 8 + 4), np.uint8)
+    check(_ffi.lib().dann_sq_compress(device, int(bits), _p(x), x.shape[0], x.shape[1], _p(shift), float(scale), _p(out)),
+          "dann_sq_compress")
     return out
 
 

@@ -49,7 +49,14 @@ typedef enum {
      * The pivot table is attached with dann_set_pq_table(); search entry points only -- the fine-grained
      * seam for PQ rows is dann_pq_build_lut / dann_pq_scan, dann_expand_beam returns DANN_EINVAL -- (re-rank the
      * candidates on a full-precision index with dann_rerank_batch). */
-    DANN_PQ = 5
+    DANN_PQ = 5,
+    /* packed scalar-quantised rows, value 16 + bits (6 and 7 are not dtypes): ceil(dim * bits / 8) code bytes,
+     * element i at bits [i * bits, (i + 1) * bits) little-endian within a byte (4-bit 1,2,3,4 = 0x21 0x43), then the
+     * f32 compensation: CompensatedVector<1> / <4> in its canonical form, Dense permutation (scalar/vectors.rs:128-175).
+     * Metrics, queries and sq_scale / sq_shift_norm_sq as for DANN_SQ8; the epilogue's constant is
+     * (1/(2^bits - 1))^2 * scale^2.  Bits beyond dim never take part, whatever they hold. */
+    DANN_SQ1 = 17,
+    DANN_SQ4 = 20
 } dann_dtype;
 
 /* == `#[repr(C)] enum Metric`, diskann-vector/src/distance/metric.rs:8-20 */
@@ -89,8 +96,8 @@ typedef struct {
                                   to 16).  dann_inmem2_row_stride() gives the reference's
                                   own stride so a Store buffer can be uploaded verbatim    */
     int32_t device;            /* HIP device ordinal, -1 = current                         */
-    float sq_scale;            /* DANN_SQ8 only: ScalarQuantizer::scale()                   */
-    float sq_shift_norm_sq;    /* DANN_SQ8 only: ScalarQuantizer::shift_square_norm()       */
+    float sq_scale;            /* DANN_SQ8 / SQ4 / SQ1 only: ScalarQuantizer::scale()       */
+    float sq_shift_norm_sq;    /* DANN_SQ8 / SQ4 / SQ1 only: ScalarQuantizer::shift_square_norm() */
     uint32_t pq_chunks;        /* DANN_PQ only: code bytes per row (number of PQ chunks)    */
     uint32_t inline_tags;      /* 1: every row carries the reference's 1-byte concurrency tag right after its
                                   payload (Store layout, store.rs:133-158; needs row_stride > payload bytes, e.g.
@@ -415,6 +422,13 @@ int32_t dann_sq8_train(int32_t device, const float* data, uint64_t n, uint32_t d
  * out: n rows of dim + 4 bytes.  Host pointers. */
 int32_t dann_sq8_compress(int32_t device, const float* x, uint32_t n, uint32_t dim, const float* shift, float scale,
                           void* out);
+/* ScalarQuantizer::compress_into::<bits> for bits in {1, 4, 8} (anything else: DANN_EINVAL): code =
+ * round(clamp((x - shift) * (2^bits - 1)/scale, 0, 2^bits - 1)) (half away from zero, NaN -> 0), compensation =
+ * scale/(2^bits - 1) * sum(code * shift).  out: n rows of ceil(dim * bits / 8) + 4 bytes, codes packed as DANN_SQ1 /
+ * DANN_SQ4 rows, padding bits zero; bits = 8 is dann_sq8_compress byte for byte.  dann_sq8_train serves every width
+ * (the trained scale and shift do not depend on it, quantizer.rs:187-189).  Host pointers. */
+int32_t dann_sq_compress(int32_t device, int32_t bits, const float* x, uint32_t n, uint32_t dim, const float* shift,
+                         float scale, void* out);
 
 /* build-path options (never change the resulting graph).  The matrix-core path evaluates the pair similarities a
  * RobustPrune asks for (prune.rs:196-232) as the lower triangle of one Gram matrix per candidate list
