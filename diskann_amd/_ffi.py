@@ -12,6 +12,9 @@ LIB_PATH = os.environ.get("DANN_LIB_PATH") or os.path.join(_HERE, "libdann_hip.s
 
 F32, F16, U8, I8, SQ8, PQ = 0, 1, 2, 3, 4, 5
 SQ1, SQ4 = 17, 20  # packed scalar-quantised rows: 16 + bits
+SPH1, SPH2, SPH4 = 33, 34, 36  # spherically quantised rows (RaBitQ): 32 + bits
+# dann_query_layout (iface::QueryLayout): the byte image of a spherical index's queries
+QUERY_SAME_AS_DATA, QUERY_FOUR_BIT_TRANSPOSED, QUERY_SCALAR_QUANTIZED, QUERY_FULL_PRECISION = 0, 1, 2, 3
 COSINE, INNER_PRODUCT, L2, COSINE_NORMALIZED = 0, 1, 2, 3
 OK, EINVAL, ELENGTH, EBOUNDS, ETOOLONG, EHIP, ENOMEM, EOVERFLOW, EUNSUPPORTED, EINTERNAL, EBUSY = (
     0, -1, -2, -3, -4, -5, -6, -7, -8, -9, -10)
@@ -158,6 +161,9 @@ SYMBOLS = {
     "dann_load_vectors_bin": (_i32, [_vp, C.c_char_p, _u32, _P(_u32)]),
     "dann_set_pq_table": (_i32, [_vp, _vp, _vp]),
     "dann_pq_pack_neighbors": (_i32, [_vp]),
+    "dann_set_query_layout": (_i32, [_vp, _i32]),
+    "dann_get_query_layout": (_i32, [_vp]),
+    "dann_query_bytes": (_i32, [_vp]),
     "dann_sq8_train": (_i32, [_i32, _vp, _u64, _u32, C.c_double, _vp, _vp, _vp]),
     "dann_sq8_compress": (_i32, [_i32, _vp, _u32, _u32, _vp, _f32, _vp]),
     "dann_sq_compress": (_i32, [_i32, _i32, _vp, _u32, _u32, _vp, _f32, _vp]),

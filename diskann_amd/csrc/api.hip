@@ -36,9 +36,12 @@ int32_t hip_fail(hipError_t e, const char* what) {
 static uint32_t elem_size(int32_t dtype) { return dtype == DT_F32 ? 4u : dtype == DT_F16 ? 2u : 1u; }
 static uint32_t layer_bytes_of(int32_t dtype, uint32_t dim) {
     if (dt_is_sq(dtype)) return sq_code_bytes(dtype, dim) + 4u;  // code bytes + the f32 compensation
+    if (dt_is_sph(dtype)) return sq_code_bytes(dtype, dim) + kSphDataMeta;  // code bytes + DataMeta
     return dim * elem_size(dtype);
 }
-static bool valid_dtype(int32_t d) { return (d >= 0 && d <= 5) || d == DT_SQ1 || d == DT_SQ4; }
+static bool valid_dtype(int32_t d) {
+    return (d >= 0 && d <= 5) || d == DT_SQ1 || d == DT_SQ4 || d == DT_SPH1 || d == DT_SPH2 || d == DT_SPH4;
+}
 static bool valid_metric(int32_t m) { return m >= 0 && m <= 3; }
 
 // temporary device buffer with RAII
@@ -181,7 +184,7 @@ int32_t search_device(dann_index* idx, SearchCtx& ctx, const void* d_queries, co
         return DANN_EUNSUPPORTED;
     }
     SearchArgs a;
-    a.ix = idx->view();
+    a.ix = d_qslots ? idx->view() : idx->qview();  // (a stored row as the query: always the symmetric form)
     a.queries = d_queries;
     a.qslots = d_qslots;
     a.nq = nq;
@@ -266,6 +269,7 @@ dann::IndexView dann_index::view() const {
     v.dtype = cfg.dtype;
     v.metric = cfg.metric;
     v.layer_bytes = layer_bytes;
+    v.qbytes = layer_bytes;
     {   // (1/(2^bits - 1))^2 * scale^2 in f32, in the reference's order (scalar/mod.rs:129-135, vectors.rs:231-241,
         // quantizer.rs:316-320)
         const float ibs = 1.0f / (float)((1u << (dt_is_sq(cfg.dtype) ? sq_bits(cfg.dtype) : 8)) - 1u);
@@ -281,7 +285,27 @@ dann::IndexView dann_index::view() const {
     v.pq_pack_stride = pq_pack_stride;
     v.pq_pack_codes = pq_pack_codes;
     v.tag_off = cfg.inline_tags ? layer_bytes : 0u;
+    if (dt_is_sph(cfg.dtype)) v.sq_k = 0.0f;  // (no scale; non-zero marks a QueryMeta, see qview and SqParams)
     return v;
+}
+
+// The view of the entry points that take queries.  Spherical rows: the query's byte image follows the layout
+// (iface::QueryLayout) -- FOUR_BIT_TRANSPOSED has an inner-product routine of its own and therefore a row type of its
+// own inside the kernels (DT_SPH1T); SCALAR_QUANTIZED shares the symmetric routine and differs in the epilogue, which
+// SqParams::k != 0 selects at run time.
+dann::IndexView dann_index::qview(int32_t layout) const {
+    IndexView v = view();
+    if (!dt_is_sph(cfg.dtype)) return v;
+    v.qbytes = sph_query_bytes(cfg.dtype, cfg.dim, layout);
+    if (layout == QL_TRANSPOSED) v.dtype = DT_SPH1T;
+    if (layout == QL_SCALAR) v.sq_k = 1.0f;
+    return v;
+}
+dann::IndexView dann_index::qview() const { return qview(query_layout.load(std::memory_order_relaxed)); }
+uint32_t dann_index::query_bytes() const {
+    if (cfg.dtype == DT_PQ) return cfg.dim * 4u;  // PQ rows: f32 queries
+    if (dt_is_sph(cfg.dtype)) return sph_query_bytes(cfg.dtype, cfg.dim, query_layout.load(std::memory_order_relaxed));
+    return layer_bytes;
 }
 
 extern "C" {
@@ -324,6 +348,17 @@ int32_t dann_index_create(const dann_config* cfg, const void* start_rows, uint64
     if (cfg->dtype == DT_PQ && (cfg->pq_chunks == 0 || cfg->pq_chunks > 128 || cfg->pq_chunks > cfg->dim)) {
         set_error("DANN_PQ needs 1 <= pq_chunks <= min(dim, 128)");
         return DANN_EINVAL;
+    }
+    if (dt_is_sph(cfg->dtype)) {
+        // DataMeta::bit_sum is a u16 (spherical/vectors.rs:219-247); SupportedMetric has no CosineNormalized
+        if ((uint64_t)cfg->dim * ((1u << sq_bits(cfg->dtype)) - 1u) > 65535u) {
+            set_error("dim %u: the bit sum of a %d-bit spherical row does not fit its u16", cfg->dim, sq_bits(cfg->dtype));
+            return DANN_EINVAL;
+        }
+        if (cfg->metric == M_COSN) {
+            set_error("spherical rows: L2, inner product and cosine (CosineNormalized is not a SupportedMetric)");
+            return DANN_EINVAL;
+        }
     }
     const uint32_t lb = cfg->dtype == DT_PQ ? cfg->pq_chunks : layer_bytes_of(cfg->dtype, cfg->dim);
     {
@@ -620,6 +655,44 @@ int32_t dann_set_pq_table(dann_index* idx, const float* pivots, const uint32_t* 
     return DANN_OK;
 } DANN_CATCH_ALL
 
+// ---- query layout of spherical indexes (iface::QueryLayout) ---------------------------------------------------------
+int32_t dann_set_query_layout(dann_index* idx, int32_t layout) try {
+    CHECK_IDX(idx);
+    if (layout < QL_SAME || layout > QL_FULL) {
+        set_error("dann_set_query_layout: unknown layout %d", layout);
+        return DANN_EINVAL;
+    }
+    if (idx->server.load(std::memory_order_acquire)) {  // the resident kernel was sized and instantiated for a layout
+        set_error("dann_set_query_layout: stop the search server first");
+        return DANN_EBUSY;
+    }
+    const bool sph = dt_is_sph(idx->cfg.dtype);
+    if (layout != QL_SAME && (!sph || sph_query_bytes(idx->cfg.dtype, idx->cfg.dim, layout) == 0u)) {
+        // UnsupportedQueryLayout: FOUR_BIT_TRANSPOSED is the 1-bit rows', SCALAR_QUANTIZED the 2- and 4-bit rows',
+        // FULL_PRECISION is not served
+        set_error("query layout %d is not supported for dtype %d", layout, idx->cfg.dtype);
+        return DANN_EUNSUPPORTED;
+    }
+    idx->query_layout.store(layout, std::memory_order_relaxed);
+    return DANN_OK;
+} DANN_CATCH_ALL
+
+int32_t dann_get_query_layout(const dann_index* idx) try {
+    if (!idx) {
+        set_error("null index");
+        return DANN_EINVAL;
+    }
+    return idx->query_layout.load(std::memory_order_relaxed);
+} DANN_CATCH_ALL
+
+int32_t dann_query_bytes(const dann_index* idx) try {
+    if (!idx) {
+        set_error("null index");
+        return DANN_EINVAL;
+    }
+    return (int32_t)idx->query_bytes();
+} DANN_CATCH_ALL
+
 // ---- packed search layout of PQ indexes ----------------------------------------------------------------------------
 int32_t dann_pq_pack_neighbors(dann_index* idx) try {
     CHECK_IDX(idx);
@@ -818,13 +891,16 @@ int32_t dann_query_create(const dann_index* idx, const void* query, uint64_t len
     CHECK_IDX(idx);
     if (!query || !out) return DANN_EINVAL;
     *out = nullptr;
-    if (len != idx->layer_bytes) {  // Full::check_dim (full.rs:86-99)
-        set_error("query of %llu bytes does not match the layer's %u bytes", (unsigned long long)len, idx->layer_bytes);
+    const int32_t layout = idx->query_layout.load(std::memory_order_relaxed);
+    const uint32_t want = dt_is_sph(idx->cfg.dtype) ? sph_query_bytes(idx->cfg.dtype, idx->cfg.dim, layout) : idx->layer_bytes;
+    if (len != want) {  // Full::check_dim (full.rs:86-99)
+        set_error("query of %llu bytes does not match the layer's %u bytes", (unsigned long long)len, want);
         return DANN_ELENGTH;
     }
     dann_query* q = new (std::nothrow) dann_query();
     if (!q) return DANN_ENOMEM;
     q->idx = idx;
+    q->layout = layout;
     hipError_t e = hipMalloc(&q->d_query, (len + 15) & ~15ull);
     if (e != hipSuccess) {
         delete q;
@@ -880,7 +956,7 @@ int32_t dann_query_distance(const dann_query* q, const void* row, uint64_t len, 
     DevBuf rowbuf;
     DANN_HIP(rowbuf.alloc((len + 15) & ~15ull));
     DANN_HIP(hipMemcpyAsync(rowbuf.p, row, len, hipMemcpyHostToDevice, idx->main.stream));
-    IndexView v = idx->view();
+    IndexView v = idx->qview(q->layout);
     v.rows = rowbuf.as<uint8_t>();
     v.nslots = 1;
     uint32_t zero = 0;
@@ -904,7 +980,7 @@ int32_t dann_expand_beam(const dann_query* q, const uint32_t* ids, uint32_t n, u
         if (!idx->cfg.inline_tags || idx->h_tags[ids[i]] >= 254) out_ids[m++] = ids[i];
     *out_n = m;
     if (m == 0) return DANN_OK;
-    return expand_on_device(idx, idx->view(), q->d_query, out_ids, m, out_dists);
+    return expand_on_device(idx, idx->qview(q->layout), q->d_query, out_ids, m, out_dists);
 } DANN_CATCH_ALL
 
 int32_t dann_expand_beam_batch(const dann_index* cidx, const void* queries, uint32_t nq, const uint32_t* ids,
@@ -923,15 +999,15 @@ int32_t dann_expand_beam_batch(const dann_index* cidx, const void* queries, uint
         if (ids[i] >= idx->nslots) return DANN_EBOUNDS;
     if (total == 0) return DANN_OK;
     DevBuf bq, bo, bi, bd;
-    DANN_HIP(bq.alloc((size_t)nq * idx->layer_bytes + 16));
+    DANN_HIP(bq.alloc((size_t)nq * idx->query_bytes() + 16));
     DANN_HIP(bo.alloc((size_t)(nq + 1) * 8));
     DANN_HIP(bi.alloc(total * 4));
     DANN_HIP(bd.alloc(total * 4));
-    DANN_HIP(hipMemcpyAsync(bq.p, queries, (size_t)nq * idx->layer_bytes, hipMemcpyHostToDevice, idx->main.stream));
+    DANN_HIP(hipMemcpyAsync(bq.p, queries, (size_t)nq * idx->query_bytes(), hipMemcpyHostToDevice, idx->main.stream));
     DANN_HIP(hipMemcpyAsync(bo.p, offsets, (size_t)(nq + 1) * 8, hipMemcpyHostToDevice, idx->main.stream));
     DANN_HIP(hipMemcpyAsync(bi.p, ids, total * 4, hipMemcpyHostToDevice, idx->main.stream));
     int32_t rc = timed(idx, 1, [&] {
-        return launch_expand_beam(idx->view(), bq.p, nq, bi.as<uint32_t>(), bo.as<uint64_t>(), max_len, bd.as<float>(),
+        return launch_expand_beam(idx->qview(), bq.p, nq, bi.as<uint32_t>(), bo.as<uint64_t>(), max_len, bd.as<float>(),
                                   idx->main.stream);
     });
     if (rc != DANN_OK) return rc;
@@ -991,7 +1067,7 @@ int32_t dann_range_search_batch(dann_index* idx, const void* queries, uint32_t n
     cap = std::min<uint64_t>(cap, idx->nslots);
     cap = std::max<uint64_t>(cap, 1);
     if (int32_t prc = pq_ready(idx)) return prc;
-    const size_t qb = idx->cfg.dtype == DT_PQ ? (size_t)idx->cfg.dim * 4 : idx->layer_bytes;
+    const size_t qb = idx->query_bytes();
     // scratch of this call: one block of the context's grow-only arena (no hipMalloc / hipFree per call: a hipFree
     // synchronises the whole device and would serialise concurrent callers)
     Carve cv;
@@ -1003,7 +1079,7 @@ int32_t dann_range_search_batch(dann_index* idx, const void* queries, uint32_t n
         bri{ctx.stage[4], o_ri}, brd{ctx.stage[4], o_rd}, bsec{ctx.stage[4], o_sec};
     DANN_HIP(hipMemcpyAsync(bq.p, queries, (size_t)nq * qb, hipMemcpyHostToDevice, ctx.stream));
     SearchArgs a;
-    a.ix = idx->view();
+    a.ix = idx->qview();
     a.queries = bq.p;
     a.qslots = nullptr;
     a.nq = nq;
@@ -1114,10 +1190,10 @@ static int32_t filtered_search(dann_index* idx, SearchCtx& ctx, const FilteredCa
         return DANN_EINVAL;
     }
     hipStream_t st = ctx.stream;
-    const size_t qb = idx->cfg.dtype == DT_PQ ? (size_t)idx->cfg.dim * 4 : idx->layer_bytes;
+    const size_t qb = idx->query_bytes();
     const bool inl = f->mode == DANN_FILTER_INLINE;
     SearchArgs a;
-    a.ix = idx->view();
+    a.ix = idx->qview();
     a.l_value = c.l_value;
     a.beam_width = c.beam;
     a.k = c.k;
@@ -1365,7 +1441,7 @@ int32_t dann_diverse_search_batch(dann_index* idx, const void* queries, uint32_t
     if (nq == 0) return DANN_OK;
     if (!queries || !out_ids || !out_dists || k == 0) return DANN_EINVAL;
     hipStream_t st = ctx.stream;
-    const size_t qb = idx->layer_bytes;
+    const size_t qb = idx->query_bytes();
     const uint32_t chunk = std::min<uint32_t>(nq, 65536u);
     Carve cv;
     const size_t o_q = cv.take((size_t)chunk * qb + 16), o_i = cv.take((size_t)chunk * k * 4),
@@ -1395,7 +1471,7 @@ int32_t dann_rerank_batch_device(dann_index* idx, const void* d_queries, uint32_
     if (nq == 0) return DANN_OK;
     if (!d_queries || !d_cand_ids || !d_out_ids || !d_out_dists || k == 0) return DANN_EINVAL;
     int32_t rc = timed(idx, 1, [&] {
-        return launch_rerank(idx->view(), d_queries, nq, d_cand_ids, cand_stride, k, d_out_ids, d_out_dists,
+        return launch_rerank(idx->qview(), d_queries, nq, d_cand_ids, cand_stride, k, d_out_ids, d_out_dists,
                              idx->main.stream);
     });
     return rc;
@@ -1407,13 +1483,13 @@ int32_t dann_rerank_batch(dann_index* idx, const void* queries, uint32_t nq, con
     if (nq == 0) return DANN_OK;
     if (!queries || !cand_ids || !out_ids || !out_dists || k == 0) return DANN_EINVAL;
     DevBuf bq, bc, bi, bd;
-    DANN_HIP(bq.alloc((size_t)nq * idx->layer_bytes + 16));
+    DANN_HIP(bq.alloc((size_t)nq * idx->query_bytes() + 16));
     DANN_HIP(bc.alloc((size_t)nq * cand_stride * 4));
     DANN_HIP(bi.alloc((size_t)nq * k * 4));
     DANN_HIP(bd.alloc((size_t)nq * k * 4));
-    DANN_HIP(hipMemcpyAsync(bq.p, queries, (size_t)nq * idx->layer_bytes, hipMemcpyHostToDevice, idx->main.stream));
+    DANN_HIP(hipMemcpyAsync(bq.p, queries, (size_t)nq * idx->query_bytes(), hipMemcpyHostToDevice, idx->main.stream));
     DANN_HIP(hipMemcpyAsync(bc.p, cand_ids, (size_t)nq * cand_stride * 4, hipMemcpyHostToDevice, idx->main.stream));
-    int32_t rc = launch_rerank(idx->view(), bq.p, nq, bc.as<uint32_t>(), cand_stride, k, bi.as<uint32_t>(),
+    int32_t rc = launch_rerank(idx->qview(), bq.p, nq, bc.as<uint32_t>(), cand_stride, k, bi.as<uint32_t>(),
                                bd.as<float>(), idx->main.stream);
     if (rc != DANN_OK) return rc;
     DANN_HIP(hipMemcpyAsync(out_ids, bi.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, idx->main.stream));
@@ -1462,7 +1538,7 @@ int32_t dann_search_record_queries(dann_index* idx, const void* queries, uint32_
     CHECK_IDX(idx);
     if (nq == 0) return DANN_OK;
     if (!queries || !rec_ids || !rec_dists || !rec_n || rec_stride == 0) return DANN_EINVAL;
-    const size_t qb = idx->cfg.dtype == DT_PQ ? (size_t)idx->cfg.dim * 4 : idx->layer_bytes;
+    const size_t qb = idx->query_bytes();
     DevBuf bq, bri, brd, brn, bs;
     DANN_HIP(bq.alloc((size_t)nq * qb + 16));
     DANN_HIP(bri.alloc((size_t)nq * rec_stride * 4));
@@ -1603,7 +1679,7 @@ int32_t dann_save_vectors_bin(const dann_index* idx, const char* path, uint32_t 
         return DANN_EINVAL;
     }
     // `.bin`: dim counts elements of the stored type (scalar-quantised rows are written as their payload bytes)
-    const uint32_t dim = dt_is_sq(idx->cfg.dtype) ? idx->layer_bytes : idx->cfg.dim;
+    const uint32_t dim = dt_is_sq(idx->cfg.dtype) || dt_is_sph(idx->cfg.dtype) ? idx->layer_bytes : idx->cfg.dim;
     if (fwrite(&n, 4, 1, out.f) != 1 || fwrite(&dim, 4, 1, out.f) != 1 ||
         (rows.size() && fwrite(rows.data(), 1, rows.size(), out.f) != rows.size())) {
         set_error("short write to %s", path);
@@ -1624,7 +1700,7 @@ int32_t dann_load_vectors_bin(dann_index* idx, const char* path, uint32_t first_
     }
     uint32_t n = 0, dim = 0;
     if (fread(&n, 4, 1, in.f) != 1 || fread(&dim, 4, 1, in.f) != 1) return DANN_ELENGTH;
-    const uint32_t want_dim = dt_is_sq(idx->cfg.dtype) ? idx->layer_bytes : idx->cfg.dim;
+    const uint32_t want_dim = dt_is_sq(idx->cfg.dtype) || dt_is_sph(idx->cfg.dtype) ? idx->layer_bytes : idx->cfg.dim;
     if (dim != want_dim) {
         set_error("data of dimension %u does not match full precision layer's dimension %u", dim, want_dim);
         return DANN_ELENGTH;

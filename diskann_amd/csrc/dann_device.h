@@ -23,12 +23,24 @@
 
 namespace dann {
 
-enum : int { DT_F32 = 0, DT_F16 = 1, DT_U8 = 2, DT_I8 = 3, DT_SQ8 = 4, DT_PQ = 5, DT_SQ1 = 17, DT_SQ4 = 20 };
+enum : int {
+    DT_F32 = 0, DT_F16 = 1, DT_U8 = 2, DT_I8 = 3, DT_SQ8 = 4, DT_PQ = 5, DT_SQ1 = 17, DT_SQ4 = 20,
+    // spherically quantised rows (spherical::Data<NBITS>), dtype value 32 + bits
+    DT_SPH1 = 33, DT_SPH2 = 34, DT_SPH4 = 36,
+    // internal, never a dann_config::dtype: DT_SPH1 rows searched with a FOUR_BIT_TRANSPOSED query (IndexView::dtype
+    // of the query-taking entry points; the inner-product routine differs, so the layout is a template argument)
+    DT_SPH1T = 97
+};
 // scalar-quantised rows: SQ-8 (one byte per code) and the packed widths, whose dtype value is 16 + bits
 __host__ __device__ constexpr bool dt_is_sq(int dt) { return dt == DT_SQ8 || dt == DT_SQ4 || dt == DT_SQ1; }
-__host__ __device__ constexpr bool dt_is_packed(int dt) { return dt == DT_SQ4 || dt == DT_SQ1; }
-__host__ __device__ constexpr int sq_bits(int dt) { return dt == DT_SQ8 ? 8 : dt - 16; }
-// code bytes of a scalar-quantised row: ceil(dim * bits / 8); the f32 compensation follows them
+__host__ __device__ constexpr bool dt_is_sph(int dt) { return dt == DT_SPH1 || dt == DT_SPH2 || dt == DT_SPH4 || dt == DT_SPH1T; }
+__host__ __device__ constexpr bool dt_is_packed(int dt) { return dt == DT_SQ4 || dt == DT_SQ1 || dt_is_sph(dt); }
+__host__ __device__ constexpr int sq_bits(int dt) { return dt == DT_SQ8 ? 8 : dt_is_sph(dt) ? (dt & 7) : dt - 16; }
+// query layouts of spherical rows (iface::QueryLayout; dann.h DANN_QUERY_*)
+enum : int { QL_SAME = 0, QL_TRANSPOSED = 1, QL_SCALAR = 2, QL_FULL = 3 };
+constexpr uint32_t kSphDataMeta = 6u, kSphQueryMeta = 16u;  // bytes of DataMeta / QueryMeta
+// code bytes of a scalar- or spherically quantised row: ceil(dim * bits / 8); the f32 compensation resp. the DataMeta
+// follows them
 __host__ __device__ constexpr uint32_t sq_code_bytes(int dt, uint32_t dim) {
     return (uint32_t)(((uint64_t)dim * (uint32_t)sq_bits(dt) + 7u) >> 3);
 }
@@ -736,7 +748,7 @@ __device__ __forceinline__ int group_norm_int_pre(const uint4& x) {
 // compensation, whatever follows inside the load) are masked to zero before they are used, in both operands.
 template <int BITS>
 struct PackedShape {
-    static constexpr int NW = BITS == 4 ? 4 : 1;  // dwords per lane per step
+    static constexpr int NW = BITS == 4 ? 4 : BITS == 2 ? 2 : 1;  // dwords per lane per step
     static constexpr int LB = 4 * NW, G = 4, STEP = G * LB;
 };
 template <int NW>
@@ -748,6 +760,9 @@ __device__ __forceinline__ PWords<NW> packed_load(const uint8_t* p) {
     if constexpr (NW == 4) {
         const uint4 t = *reinterpret_cast<const uint4*>(p);
         return {{t.x, t.y, t.z, t.w}};
+    } else if constexpr (NW == 2) {
+        const uint2 t = *reinterpret_cast<const uint2*>(p);
+        return {{t.x, t.y}};
     } else {
         return {{*reinterpret_cast<const uint32_t*>(p)}};
     }
@@ -759,6 +774,21 @@ __device__ __forceinline__ void packed_mask(PWords<NW>& a, int valid) {
     for (int i = 0; i < NW; ++i) {
         const int nb = valid - 32 * i;
         a.w[i] &= nb >= 32 ? 0xFFFFFFFFu : nb <= 0 ? 0u : ((1u << nb) - 1u);
+    }
+}
+// acc + sum of the products of the BITS-wide fields of two dwords.  There is no dot instruction for 2-bit fields:
+// the even and the odd fields are widened to nibbles (and, shift, and) and go through v_dot8_u32_u4 twice -- three
+// operations per operand and two dots for 16 elements, where bit planes cost four ands, four popcounts and the
+// weighting; a query kept in registers is widened once (packed_query_pre).
+constexpr uint32_t kEven2 = 0x33333333u;
+template <int BITS>
+__device__ __forceinline__ uint32_t packed_dot(uint32_t x, uint32_t y, uint32_t acc) {
+    static_assert(BITS == 4 || BITS == 2, "dot instruction widths");
+    if constexpr (BITS == 4) {
+        return __builtin_amdgcn_udot8(x, y, acc, false);
+    } else {
+        acc = __builtin_amdgcn_udot8(x & kEven2, y & kEven2, acc, false);
+        return __builtin_amdgcn_udot8((x >> 2) & kEven2, (y >> 2) & kEven2, acc, false);
     }
 }
 __device__ __forceinline__ uint32_t group4_sum(uint32_t x) {
@@ -789,19 +819,19 @@ __device__ __forceinline__ void group_distance_packed(const uint8_t* __restrict_
         PWords<NW> x = packed_load<NW>(q + ol);
         packed_mask<NW>(x, valid);
         uint32_t xx = 0u;
-        if constexpr (BITS == 4 && OP == OP_L2) {
+        if constexpr (BITS != 1 && OP == OP_L2) {
 #pragma unroll
-            for (int i = 0; i < NW; ++i) xx = __builtin_amdgcn_udot8(x.w[i], x.w[i], xx, false);
+            for (int i = 0; i < NW; ++i) xx = packed_dot<BITS>(x.w[i], x.w[i], xx);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if constexpr (OP == OP_L2) packed_mask<NW>(y[u], valid);  // (inner product: x's zeros suffice)
-            if constexpr (BITS == 4) {
+            if constexpr (BITS != 1) {
                 uint32_t xy = 0u, yy = 0u;
 #pragma unroll
                 for (int i = 0; i < NW; ++i) {
-                    xy = __builtin_amdgcn_udot8(x.w[i], y[u].w[i], xy, false);
-                    if constexpr (OP == OP_L2) yy = __builtin_amdgcn_udot8(y[u].w[i], y[u].w[i], yy, false);
+                    xy = packed_dot<BITS>(x.w[i], y[u].w[i], xy);
+                    if constexpr (OP == OP_L2) yy = packed_dot<BITS>(y[u].w[i], y[u].w[i], yy);
                 }
                 t[u] += OP == OP_L2 ? xx + yy - 2u * xy : xy;
             } else {
@@ -872,6 +902,116 @@ __device__ __forceinline__ void group_distance_packed_pre(const uint4& x, int xx
     }
 }
 
+// ---- spherically quantised rows (spherical::Data<NBITS>, diskann-quantization/src/spherical/vectors.rs): the code
+// bytes of the packed rows above, then the 6-byte DataMeta.  Every metric needs the raw inner product of the codes
+// (the epilogue is finish_distance), so these entries take no OP.  Three query forms:
+//   the row image itself (SAME_AS_DATA) and Dense codes of the row's width (SCALAR_QUANTIZED): group_distance_packed's
+//     inner-product form at 1, 2 or 4 bits.  The query's bits at or beyond dim are masked; a zero in one operand
+//     removes the product, whatever the row holds there;
+//   FOUR_BIT_TRANSPOSED against 1-bit rows (bits/distances.rs:2123-2249): per block of 64 elements four u64 words,
+//     word j = bit j of the 64 four-bit values; <q, y> = sum_j 2^j popcount(y & plane_j).  A lane owns one data dword
+//     (32 dimensions) per step and the four matching plane dwords: block (o / 8), half (o / 4) & 1 of the data byte
+//     offset o.  The row's bits at or beyond dim are masked, the query's padding may hold anything.  The plane loads
+//     stay inside the ceil(dim / 64) * 32 plane bytes because o < ceil(dim / 8).
+__host__ __device__ constexpr uint32_t sph_plane_bytes(uint32_t dim) { return ((dim + 63u) >> 6) * 32u; }
+// bytes of one query under `layout` (0 = the layout is not defined for the row type)
+__host__ __device__ constexpr uint32_t sph_query_bytes(int dt, uint32_t dim, int layout) {
+    const int bits = sq_bits(dt);
+    const uint32_t cb = (uint32_t)(((uint64_t)dim * (uint32_t)bits + 7u) >> 3);
+    return layout == QL_SAME                       ? cb + kSphDataMeta
+           : layout == QL_TRANSPOSED && bits == 1 ? sph_plane_bytes(dim) + kSphQueryMeta
+           : layout == QL_SCALAR && bits != 1     ? cb + kSphQueryMeta
+                                                  : 0u;
+}
+__device__ __forceinline__ uint32_t transposed_dot(uint32_t y, const uint32_t (&p)[4]) {
+    return (uint32_t)__builtin_popcount(y & p[0]) + ((uint32_t)__builtin_popcount(y & p[1]) << 1) +
+           ((uint32_t)__builtin_popcount(y & p[2]) << 2) + ((uint32_t)__builtin_popcount(y & p[3]) << 3);
+}
+template <int U>
+__device__ __forceinline__ void group_ip_transposed(const uint8_t* __restrict__ q, const uint8_t* const (&rows)[U],
+                                                    int dim, int v, float (&out)[U]) {
+    const int cb = (dim + 7) >> 3;
+    uint32_t t[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) t[u] = 0u;
+    for (int o0 = 0; o0 < cb; o0 += 16) {
+        const int o = o0 + 4 * v;
+        const bool in = o < cb;
+        const int ol = in ? o : 0;  // clamped as in group_distance_packed: every request is issued, all in bounds
+        const int valid = in ? dim - 8 * o : 0;
+        PWords<1> y[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) y[u] = packed_load<1>(rows[u] + ol);
+        const uint8_t* pq = q + (ol >> 3) * 32 + ((ol >> 2) & 1) * 4;
+        uint32_t p[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) p[j] = *reinterpret_cast<const uint32_t*>(pq + 8 * j);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            packed_mask<1>(y[u], valid);
+            t[u] += transposed_dot(y[u].w[0], p);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) out[u] = (float)(int)group4_sum(t[u]);
+}
+template <int DT, int U>
+__device__ __forceinline__ void group_ip_sph(const uint8_t* q, const uint8_t* const (&rows)[U], int dim, int v,
+                                             float (&out)[U]) {
+    if constexpr (DT == DT_SPH1T) group_ip_transposed<U>(q, rows, dim, v, out);
+    else group_distance_packed<sq_bits(DT), OP_IP, U>(q, rows, dim, v, out);
+}
+template <int DT>
+__device__ __forceinline__ float group_ip_sph1(const uint8_t* q, const uint8_t* row, int dim, int v) {
+    const uint8_t* const rows[1] = {row};
+    float out[1];
+    group_ip_sph<DT, 1>(q, rows, dim, v, out);
+    return out[0];
+}
+// Fixed 128 dimensions, the lane's query words in registers: the four plane dwords (transposed), the two code dwords
+// widened to four nibble dwords (2 bit), the code dwords as they are (4 bit: four, 1 bit: one).
+template <int DT>
+__device__ __forceinline__ uint4 sph_query_pre(const uint8_t* qs, int v) {
+    if constexpr (DT == DT_SPH1T) {
+        const uint8_t* pq = qs + (v >> 1) * 32 + (v & 1) * 4;
+        return uint4{*reinterpret_cast<const uint32_t*>(pq), *reinterpret_cast<const uint32_t*>(pq + 8),
+                     *reinterpret_cast<const uint32_t*>(pq + 16), *reinterpret_cast<const uint32_t*>(pq + 24)};
+    } else if constexpr (sq_bits(DT) == 2) {
+        const uint2 x = *reinterpret_cast<const uint2*>(qs + 8 * v);
+        return uint4{x.x & kEven2, (x.x >> 2) & kEven2, x.y & kEven2, (x.y >> 2) & kEven2};
+    } else {
+        return packed_query_pre<sq_bits(DT)>(qs, v);
+    }
+}
+template <int DT, int U>
+__device__ __forceinline__ void group_ip_sph_pre(const uint4& x, const uint8_t* const (&rows)[U], int v, float (&out)[U]) {
+    constexpr int BITS = sq_bits(DT);
+    constexpr int NW = PackedShape<BITS>::NW;
+    PWords<NW> y[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) y[u] = packed_load<NW>(rows[u] + PackedShape<BITS>::LB * v);
+    const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        uint32_t t = 0u;
+        if constexpr (DT == DT_SPH1T) {
+            t = transposed_dot(y[u].w[0], xs);
+        } else if constexpr (BITS == 1) {
+            t = (uint32_t)__builtin_popcount(xs[0] & y[u].w[0]);
+        } else if constexpr (BITS == 2) {
+#pragma unroll
+            for (int i = 0; i < NW; ++i) {
+                t = __builtin_amdgcn_udot8(xs[2 * i], y[u].w[i] & kEven2, t, false);
+                t = __builtin_amdgcn_udot8(xs[2 * i + 1], (y[u].w[i] >> 2) & kEven2, t, false);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NW; ++i) t = __builtin_amdgcn_udot8(xs[i], y[u].w[i], t, false);
+        }
+        out[u] = (float)(int)group4_sum(t);
+    }
+}
+
 // ---- dtype dispatch ------------------------------------------------------------------
 // Query-side staging type and group width for the *search* path
 // (Full<T>::query_distance, diskann-inmem/src/layers/full.rs:351-504):
@@ -882,7 +1022,7 @@ __device__ __forceinline__ void group_distance_packed_pre(const uint4& x, int xx
 //   f16 x f16: L2/IP/cosine all Strategy2x4 (NACC 2)  (simd.rs:989,1752,2591)
 template <int DT, int OP, bool PAIR>
 struct Scheme {
-    static constexpr bool kInt = (DT == DT_U8 || DT == DT_I8 || DT == DT_PQ || dt_is_sq(DT));
+    static constexpr bool kInt = (DT == DT_U8 || DT == DT_I8 || DT == DT_PQ || dt_is_sq(DT) || dt_is_sph(DT));
     static constexpr int NACC = (OP == OP_COS) ? 2 : ((DT == DT_F16 && PAIR) ? 2 : 4);
     static constexpr int G = dt_is_packed(DT) ? 4 : kInt ? 8 : 2 * NACC;  // (packed rows: PackedShape::G)
     // search-path gather: 2-byte rows use the wide layout (one lane per accumulator)
@@ -919,6 +1059,22 @@ struct RowType<DT_SQ1> {
     using type = uint8_t;
 };
 template <>
+struct RowType<DT_SPH1> {
+    using type = uint8_t;
+};
+template <>
+struct RowType<DT_SPH2> {
+    using type = uint8_t;
+};
+template <>
+struct RowType<DT_SPH4> {
+    using type = uint8_t;
+};
+template <>
+struct RowType<DT_SPH1T> {
+    using type = uint8_t;
+};
+template <>
 struct RowType<DT_PQ> {
     using type = uint8_t;
 };
@@ -926,7 +1082,9 @@ struct RowType<DT_PQ> {
 // `q` is the staged query: f32 for float rows, raw bytes for integer rows.
 template <int DT, int OP, bool PAIR, int DIM, typename QT>
 __device__ __forceinline__ float group_distance(const QT* q, const uint8_t* row, int dim, int v) {
-    if constexpr (dt_is_packed(DT)) {
+    if constexpr (dt_is_sph(DT)) {
+        return group_ip_sph1<DT>(reinterpret_cast<const uint8_t*>(q), row, dim, v);
+    } else if constexpr (dt_is_packed(DT)) {
         return group_distance_packed1<sq_bits(DT), OP>(reinterpret_cast<const uint8_t*>(q), row, dim, v);
     } else if constexpr (DT == DT_U8 || DT == DT_I8 || DT == DT_SQ8) {
         return group_distance_int<OP, DT == DT_I8>(reinterpret_cast<const uint8_t*>(q), row, dim, v);
@@ -940,7 +1098,10 @@ __device__ __forceinline__ float group_distance(const QT* q, const uint8_t* row,
 // stored row x stored row with the prune-path association (Scheme<DT, OP, true>)
 template <int DT, int OP>
 __device__ __forceinline__ float group_distance_rows(const uint8_t* x, const uint8_t* y, int dim, int v) {
-    if constexpr (dt_is_packed(DT)) {
+    if constexpr (dt_is_sph(DT)) {  // (a stored row as the query is always the symmetric form)
+        static_assert(DT != DT_SPH1T, "row x row distances have no query layout");
+        return group_ip_sph1<DT>(x, y, dim, v);
+    } else if constexpr (dt_is_packed(DT)) {
         return group_distance_packed1<sq_bits(DT), OP>(x, y, dim, v);
     } else if constexpr (DT == DT_U8 || DT == DT_I8 || DT == DT_SQ8) {
         return group_distance_int<OP, DT == DT_I8>(x, y, dim, v);
@@ -957,7 +1118,9 @@ __device__ __forceinline__ float group_distance_rows(const uint8_t* x, const uin
 template <int DT, int OP, bool PAIR, int U, bool WIDE = true, typename QT>
 __device__ __forceinline__ void group_distance_many(const QT* q, const uint8_t* const (&rows)[U],
                                                     const bool (&active)[U], int dim, int v, float (&out)[U]) {
-    if constexpr (dt_is_packed(DT)) {
+    if constexpr (dt_is_sph(DT)) {
+        group_ip_sph<DT, U>(reinterpret_cast<const uint8_t*>(q), rows, dim, v, out);
+    } else if constexpr (dt_is_packed(DT)) {
         group_distance_packed<sq_bits(DT), OP, U>(reinterpret_cast<const uint8_t*>(q), rows, dim, v, out);
     } else if constexpr (DT == DT_U8 || DT == DT_I8 || DT == DT_SQ8) {
         group_distance_int_multi<OP, DT == DT_I8, U>(reinterpret_cast<const uint8_t*>(q), rows, active, dim, v, out);
@@ -1023,13 +1186,50 @@ __device__ float simd_op_seq(const float* x, const float* y, uint32_t len) {
 
 // scalar-quantiser parameters of an SQ-8 / SQ4 / SQ1 index
 struct SqParams {
-    float k;              // (1/(2^bits - 1))^2 * scale^2, evaluated in f32 in the reference's order
-    float shift_norm_sq;  // ||shift||^2
+    float k;              // (1/(2^bits - 1))^2 * scale^2, evaluated in f32 in the reference's order.  Spherical rows
+                          // have no scale: non-zero says the query ends in a QueryMeta (SCALAR_QUANTIZED layout)
+    float shift_norm_sq;  // ||shift||^2; spherical rows: CompensatedIP::squared_shift_norm
 };
 
 __device__ __forceinline__ float load_f32_unaligned(const uint8_t* p) {
     uint32_t u = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
     return __builtin_bit_cast(float, u);
+}
+__device__ __forceinline__ uint32_t load_u16_unaligned(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
+__device__ __forceinline__ float load_f16_unaligned(const uint8_t* p) {  // f16 -> f32 is exact
+    return __half2float(__ushort_as_half((unsigned short)load_u16_unaligned(p)));
+}
+
+// Spherical rows: the raw inner product of the codes -> SimilarityScore, each f32 operation in the reference's
+// association (spherical/vectors.rs: kernel :494-528, query x data :612-636 and :776-801; L2 :584-594, IP :744-758,
+// Cosine :867-892; no fused multiply-add).  `x` is the query -- a row image (DataMeta at the code-byte count) or
+// codes / planes followed by a QueryMeta of four f32 (inner_product_correction, bit_sum, offset, metric_specific,
+// vectors.rs:381-399) -- and `y` the row.  The metadata sits at any byte offset and is read bytewise.
+template <int DT, int OP>
+__device__ __forceinline__ float finish_spherical(float ip, const uint8_t* x, const uint8_t* y, uint32_t dim,
+                                                  const SqParams& sq) {
+    constexpr float off = (float)((1 << sq_bits(DT)) - 1) / 2.0f;
+    const uint32_t cb = sq_code_bytes(DT, dim);
+    const float D = (float)dim;
+    const float cy = load_f16_unaligned(y + cb), my = load_f16_unaligned(y + cb + 2);
+    const float sy = (float)load_u16_unaligned(y + cb + 4);
+    float k, ms;
+    if (DT == DT_SPH1T || sq.k != 0.0f) {
+        const uint8_t* m = x + (DT == DT_SPH1T ? sph_plane_bytes(dim) : cb);
+        const float cq = load_f32_unaligned(m), sq_sum = load_f32_unaligned(m + 4), qoff = load_f32_unaligned(m + 8),
+                    mq = load_f32_unaligned(m + 12);
+        k = (cy * cq) * (((ip - off * sq_sum) + qoff * sy) - (off * qoff) * D);
+        if constexpr (OP == OP_L2) return (my + mq) - 2.0f * k;
+        ms = (k + my) + mq;
+    } else {
+        const float cx = load_f16_unaligned(x + cb), mx = load_f16_unaligned(x + cb + 2);
+        const float sx = (float)load_u16_unaligned(x + cb + 4);
+        k = (cx * cy) * ((ip - off * (sx + sy)) + (off * off) * D);
+        if constexpr (OP == OP_L2) return (mx + my) - 2.0f * k;
+        ms = (mx + my) + k;
+    }
+    const float r = ms + sq.shift_norm_sq;
+    return OP == OP_IP ? -r : 1.0f - r;
 }
 
 // raw kernel result -> SimilarityScore.  Full-precision rows: PostOp; scalar-quantised rows: the compensated
@@ -1039,7 +1239,9 @@ __device__ __forceinline__ float load_f32_unaligned(const uint8_t* p) {
 template <int DT, int OP, bool NORM>
 __device__ __forceinline__ float finish_distance(float raw, const uint8_t* x, const uint8_t* y, uint32_t dim,
                                                  const SqParams& sq) {
-    if constexpr (!dt_is_sq(DT)) {
+    if constexpr (dt_is_sph(DT)) {
+        return finish_spherical<DT, OP>(raw, x, y, dim, sq);
+    } else if constexpr (!dt_is_sq(DT)) {
         return post_op<OP, NORM>(raw);
     } else if constexpr (OP == OP_L2) {
         const float l2 = sq.k * raw;
@@ -1062,6 +1264,12 @@ __host__ __device__ inline bool resolve_metric(int dtype, int metric, int* op, b
     if (dtype == DT_PQ) {
         if (metric == M_L2) { *op = OP_L2; return true; }
         if (metric == M_IP) { *op = OP_IP; return true; }
+        return false;
+    }
+    if (dt_is_sph(dtype)) {  // SupportedMetric (spherical/mod.rs): SquaredL2, InnerProduct, Cosine
+        if (metric == M_L2) { *op = OP_L2; return true; }
+        if (metric == M_IP) { *op = OP_IP; return true; }
+        if (metric == M_COSINE) { *op = OP_COS; return true; }
         return false;
     }
     if (dt_is_sq(dtype)) {

@@ -66,7 +66,9 @@ struct IndexView {
     uint32_t nstart;
     int32_t dtype;
     int32_t metric;
-    uint32_t layer_bytes;  // bytes of one row's payload (dim * sizeof(T); SQ-8 / SQ4 / SQ1: code bytes + 4)
+    uint32_t layer_bytes;  // bytes of one row's payload (dim * sizeof(T); SQ-8 / SQ4 / SQ1: code bytes + 4; spherical: + 6)
+    uint32_t qbytes;       // integer rows: bytes of one query as the kernels read and stage it -- layer_bytes, except under
+                           // a spherical query layout (dann_set_query_layout; dtype is then the layout's, see DT_SPH1T)
     float sq_k;            // SQ-8 / SQ4 / SQ1: (1/(2^bits - 1))^2 * scale^2
     float sq_shift_norm_sq;
     // PQ rows (DT_PQ): codes of pq_chunks bytes; pivots 256 x dim f32; chunk offsets pq_chunks + 1
@@ -234,6 +236,10 @@ DANN_DECL_LAUNCH(i8);
 DANN_DECL_LAUNCH(sq8);
 DANN_DECL_LAUNCH(sq4);
 DANN_DECL_LAUNCH(sq1);
+DANN_DECL_LAUNCH(sph1);
+DANN_DECL_LAUNCH(sph1t);
+DANN_DECL_LAUNCH(sph2);
+DANN_DECL_LAUNCH(sph4);
 DANN_DECL_LAUNCH(pq);
 // search_diverse.hip: dann_diverse_search_batch on device-resident queries and outputs (host-synchronous on `stream`)
 int32_t diverse_search_device(dann_index* idx, hipStream_t stream, const void* d_queries, uint32_t nq, uint32_t l_value,
@@ -412,7 +418,12 @@ struct dann_index {
     dann::ShardedCounter srv_users;
     dann::ShardedCounter srv_outstanding;
     std::atomic<uint32_t> mutating{0};
-    dann::IndexView view() const;
+    // spherical rows: iface::QueryLayout of the queries the entry points take (dann_set_query_layout)
+    std::atomic<int32_t> query_layout{0};
+    uint32_t query_bytes() const;  // bytes of one query of the query-taking entry points under the current layout
+    dann::IndexView view() const;  // row x row work: a stored row as the query is always the symmetric form
+    dann::IndexView qview() const;               // the query-taking entry points: the current layout
+    dann::IndexView qview(int32_t layout) const;
 };
 
 namespace dann {
@@ -505,5 +516,6 @@ int32_t grow_stage(SearchCtx& ctx, int i, size_t need);
 
 struct dann_query {
     const dann_index* idx;
+    int32_t layout = 0;  // the index's query layout when the query was created (its byte image is of that layout)
     void* d_query = nullptr;
 };

@@ -31,9 +31,9 @@ __global__ __launch_bounds__(kWave) void expand_beam_kernel(IndexView ix, const 
     const uint64_t hi = lo + kChunk < hi_all ? lo + kChunk : hi_all;
     QT* qs = reinterpret_cast<QT*>(smem);
     const SqParams sqp{ix.sq_k, ix.sq_shift_norm_sq};
-    const uint8_t* qsrc = reinterpret_cast<const uint8_t*>(queries) + (uint64_t)qi * ix.layer_bytes;
+    const uint8_t* qsrc = reinterpret_cast<const uint8_t*>(queries) + (uint64_t)qi * ix.qbytes;
     if constexpr (kInt) {
-        for (uint32_t i = lane; i < ix.layer_bytes; i += kWave) reinterpret_cast<uint8_t*>(qs)[i] = qsrc[i];
+        for (uint32_t i = lane; i < ix.qbytes; i += kWave) reinterpret_cast<uint8_t*>(qs)[i] = qsrc[i];
     } else {
         const RT* src = reinterpret_cast<const RT*>(qsrc);
         for (uint32_t i = lane; i < ix.dim; i += kWave) reinterpret_cast<float*>(qs)[i] = load1(src + i);
@@ -95,9 +95,9 @@ __global__ __launch_bounds__(kWave) void rerank_kernel(IndexView ix, const void*
     float* cd = reinterpret_cast<float*>(smem + (size_t)pcap * 12);
     QT* qs = reinterpret_cast<QT*>(smem + (size_t)pcap * 16);
     const SqParams sqp{ix.sq_k, ix.sq_shift_norm_sq};
-    const uint8_t* qsrc = reinterpret_cast<const uint8_t*>(queries) + (uint64_t)qi * ix.layer_bytes;
+    const uint8_t* qsrc = reinterpret_cast<const uint8_t*>(queries) + (uint64_t)qi * ix.qbytes;
     if constexpr (kInt) {
-        for (uint32_t i = lane; i < ix.layer_bytes; i += kWave) reinterpret_cast<uint8_t*>(qs)[i] = qsrc[i];
+        for (uint32_t i = lane; i < ix.qbytes; i += kWave) reinterpret_cast<uint8_t*>(qs)[i] = qsrc[i];
     } else {
         const RT* src = reinterpret_cast<const RT*>(qsrc);
         for (uint32_t i = lane; i < ix.dim; i += kWave) reinterpret_cast<float*>(qs)[i] = load1(src + i);
@@ -177,8 +177,8 @@ int32_t launch_rerank_t(const IndexView& ix, const void* q, uint32_t nq, const u
                         uint32_t k, uint32_t* oi, float* od, hipStream_t stream) {
     uint32_t pcap = 64;
     while (pcap < stride) pcap <<= 1;
-    const bool is_int = DT == DT_U8 || DT == DT_I8 || dt_is_sq(DT);
-    const size_t lds = (size_t)pcap * 16 + (((is_int ? ix.layer_bytes : ix.dim * 4u) + 15u) & ~15u);
+    const bool is_int = Scheme<DT, OP, false>::kInt;
+    const size_t lds = (size_t)pcap * 16 + (((is_int ? ix.qbytes : ix.dim * 4u) + 15u) & ~15u);
     auto kern = rerank_kernel<DT, OP, NORM>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(256) void pair_kernel(const uint8_t* xbase, const u
     const uint8_t* y = ybase + (uint64_t)(b ? b[p] : p) * ystride;
     float d;
     if constexpr (dt_is_packed(DT)) {
-        d = group_distance_packed1<sq_bits(DT), OP>(x, y, (int)dim, v);
+        d = group_distance_rows<DT, OP>(x, y, (int)dim, v);
     } else if constexpr (S::kInt) {
         d = group_distance_int<OP, DT == DT_I8>(x, y, (int)dim, v);
     } else {
@@ -291,6 +291,9 @@ int32_t launch_pairs_any(int32_t dtype, int32_t metric, const uint8_t* xb, const
         case DT_SQ8: return launch_pairs_dt<DT_SQ8>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
         case DT_SQ4: return launch_pairs_dt<DT_SQ4>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
         case DT_SQ1: return launch_pairs_dt<DT_SQ1>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
+        case DT_SPH1: return launch_pairs_dt<DT_SPH1>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
+        case DT_SPH2: return launch_pairs_dt<DT_SPH2>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
+        case DT_SPH4: return launch_pairs_dt<DT_SPH4>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
     }
     set_error("bad dtype %d", dtype);
     return DANN_EINVAL;
@@ -299,8 +302,8 @@ int32_t launch_pairs_any(int32_t dtype, int32_t metric, const uint8_t* xb, const
 template <int DT, int OP, bool NORM, int DIM>
 int32_t launch_eb_t(const IndexView& ix, const void* q, uint32_t nq, uint32_t chunks, const uint32_t* ids,
                     const uint64_t* offsets, float* out, hipStream_t stream) {
-    const bool is_int = DT == DT_U8 || DT == DT_I8 || dt_is_sq(DT);
-    size_t lds = ((is_int ? ix.layer_bytes : ix.dim * 4u) + 15u) & ~15u;
+    const bool is_int = Scheme<DT, OP, false>::kInt;
+    size_t lds = ((is_int ? ix.qbytes : ix.dim * 4u) + 15u) & ~15u;
     hipLaunchKernelGGL((expand_beam_kernel<DT, OP, NORM, DIM>), dim3(nq, chunks), dim3(kWave), lds, stream, ix, q, ids,
                        offsets, out);
     hipError_t e = hipGetLastError();
@@ -355,6 +358,10 @@ int32_t launch_expand_beam(const IndexView& ix, const void* d_queries, uint32_t 
         case DT_SQ8: return launch_eb_dt<DT_SQ8>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
         case DT_SQ4: return launch_eb_dt<DT_SQ4>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
         case DT_SQ1: return launch_eb_dt<DT_SQ1>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
+        case DT_SPH1: return launch_eb_dt<DT_SPH1>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
+        case DT_SPH1T: return launch_eb_dt<DT_SPH1T>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
+        case DT_SPH2: return launch_eb_dt<DT_SPH2>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
+        case DT_SPH4: return launch_eb_dt<DT_SPH4>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
     }
     set_error("bad dtype %d", ix.dtype);
     return DANN_EINVAL;
@@ -375,6 +382,10 @@ int32_t launch_rerank(const IndexView& ix, const void* d_queries, uint32_t nq, c
         case DT_SQ8: return launch_rerank_dt<DT_SQ8>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
         case DT_SQ4: return launch_rerank_dt<DT_SQ4>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
         case DT_SQ1: return launch_rerank_dt<DT_SQ1>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
+        case DT_SPH1: return launch_rerank_dt<DT_SPH1>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
+        case DT_SPH1T: return launch_rerank_dt<DT_SPH1T>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
+        case DT_SPH2: return launch_rerank_dt<DT_SPH2>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
+        case DT_SPH4: return launch_rerank_dt<DT_SPH4>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
     }
     return DANN_EINVAL;
 }

@@ -397,7 +397,7 @@ int32_t dann_search_batch(dann_index* idx, const void* queries, uint32_t nq, uin
     DeviceGuard _guard(idx->device);
     if (nq == 0) return DANN_OK;
     if (!queries || !out_ids || !out_dists) return DANN_EINVAL;
-    const size_t qb = idx->cfg.dtype == DANN_PQ ? (size_t)idx->cfg.dim * 4 : idx->layer_bytes;  // PQ: f32 queries
+    const size_t qb = idx->query_bytes();  // PQ: f32 queries
     const HostArgs a{idx, queries, nq, l_value, beam_width, k, out_ids, out_dists, out_stats, qb};
     HostPlanIn in{idx->cfg.dtype, idx->dbg_u32(DANN_DBG_HOST_PIPELINE, 1u), idx->dbg_u32(DANN_DBG_HOST_CHUNK, kHostChunk),
                   nq, k, qb, false, false, false, false};

@@ -75,9 +75,9 @@ __global__ __launch_bounds__(kWave) void paged_kernel(PagedArgs a) {
     QT* qs = reinterpret_cast<QT*>(smem + (size_t)rc * 8);
     const SqParams sqp{ix.sq_k, ix.sq_shift_norm_sq};
     {
-        const uint8_t* qsrc = reinterpret_cast<const uint8_t*>(a.queries) + (uint64_t)qi * ix.layer_bytes;
+        const uint8_t* qsrc = reinterpret_cast<const uint8_t*>(a.queries) + (uint64_t)qi * ix.qbytes;
         if constexpr (kInt) {
-            for (uint32_t i = lane; i < ix.layer_bytes; i += kWave) reinterpret_cast<uint8_t*>(qs)[i] = qsrc[i];
+            for (uint32_t i = lane; i < ix.qbytes; i += kWave) reinterpret_cast<uint8_t*>(qs)[i] = qsrc[i];
         } else {
             const RT* src = reinterpret_cast<const RT*>(qsrc);
             for (uint32_t i = lane; i < ix.dim; i += kWave) reinterpret_cast<float*>(qs)[i] = load1(src + i);
@@ -308,9 +308,9 @@ __global__ __launch_bounds__(kWave) void paged_kernel(PagedArgs a) {
 
 template <int DT, int OP, bool NORM>
 int32_t launch_paged_t(const PagedArgs& a, hipStream_t stream) {
-    const bool is_int = DT == DT_U8 || DT == DT_I8 || dt_is_sq(DT);
+    const bool is_int = Scheme<DT, OP, false>::kInt;
     const uint32_t rc = (a.ix.max_degree + 63u) & ~63u;
-    const size_t lds = (size_t)rc * 8 + (((is_int ? a.ix.layer_bytes : a.ix.dim * 4u) + 15u) & ~15u);
+    const size_t lds = (size_t)rc * 8 + (((is_int ? a.ix.qbytes : a.ix.dim * 4u) + 15u) & ~15u);
     auto kern = paged_kernel<DT, OP, NORM>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -353,6 +353,10 @@ int32_t launch_paged(const PagedArgs& a, hipStream_t stream) {
         case DT_SQ8: return launch_paged_dt<DT_SQ8>(a, stream);
         case DT_SQ4: return launch_paged_dt<DT_SQ4>(a, stream);
         case DT_SQ1: return launch_paged_dt<DT_SQ1>(a, stream);
+        case DT_SPH1: return launch_paged_dt<DT_SPH1>(a, stream);
+        case DT_SPH1T: return launch_paged_dt<DT_SPH1T>(a, stream);
+        case DT_SPH2: return launch_paged_dt<DT_SPH2>(a, stream);
+        case DT_SPH4: return launch_paged_dt<DT_SPH4>(a, stream);
     }
     set_error("paged search is not defined for dtype %d", a.ix.dtype);
     return DANN_EUNSUPPORTED;
@@ -414,13 +418,13 @@ int32_t dann_paged_begin(dann_index* idx, const void* queries, uint32_t nq, uint
     while ((1ull << vbits) * 3 / 4 < (uint64_t)cap + idx->cfg.num_start_points + idx->cfg.max_degree + 64 && vbits < 31)
         ++vbits;
     PagedArgs& a = s->a;
-    a.ix = idx->view();
+    a.ix = idx->qview();
     a.nq = nq;
     a.l_value = l_value;
     a.k = 0;
     a.cap = cap;
     a.vt_bits = vbits;
-    const size_t qb = idx->layer_bytes;
+    const size_t qb = a.ix.qbytes;
     auto fail = [&](hipError_t e) {
         delete s;
         return hip_fail(e, "paged session allocation");
@@ -500,7 +504,13 @@ int32_t dann_paged_next(dann_paged* s, uint32_t k, uint32_t* out_ids, float* out
         if (!s->out_n.p) DANN_HIP(hipMalloc(&s->out_n.p, (size_t)nq * 4));
         s->out_k = k;
     }
-    s->a.ix = idx->view();
+    {   // (the session's queries keep the layout they were staged with)
+        const IndexView started = s->a.ix;
+        s->a.ix = idx->view();
+        s->a.ix.dtype = started.dtype;
+        s->a.ix.qbytes = started.qbytes;
+        s->a.ix.sq_k = started.sq_k;
+    }
     s->a.k = k;
     s->a.out_ids = (uint32_t*)s->out_ids.p;
     s->a.out_d = (float*)s->out_d.p;

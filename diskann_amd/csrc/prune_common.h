@@ -64,6 +64,9 @@ int32_t dispatch(const IndexView& ix, const Args& a, uint32_t grid, size_t lds, 
         DANN_CASE(DT_SQ8)
         DANN_CASE(DT_SQ4)
         DANN_CASE(DT_SQ1)
+        DANN_CASE(DT_SPH4)
+        DANN_CASE(DT_SPH2)
+        DANN_CASE(DT_SPH1)
     }
 #undef DANN_CASE
     set_error("bad dtype %d", ix.dtype);

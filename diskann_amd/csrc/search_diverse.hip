@@ -103,9 +103,9 @@ __global__ __launch_bounds__(kWave) void diverse_search_kernel(DiverseArgs a) {
 
     // ---- stage the query (f16 widened to f32 once, integer rows as raw bytes) --------------------------------------
     {
-        const uint8_t* qsrc = reinterpret_cast<const uint8_t*>(a.queries) + (uint64_t)qi * ix.layer_bytes;
+        const uint8_t* qsrc = reinterpret_cast<const uint8_t*>(a.queries) + (uint64_t)qi * ix.qbytes;
         if constexpr (kInt) {
-            for (uint32_t i = lane; i < ix.layer_bytes; i += kWave) reinterpret_cast<uint8_t*>(qs)[i] = qsrc[i];
+            for (uint32_t i = lane; i < ix.qbytes; i += kWave) reinterpret_cast<uint8_t*>(qs)[i] = qsrc[i];
         } else {
             const RT* src = reinterpret_cast<const RT*>(qsrc);
             for (uint32_t i = lane; i < ix.dim; i += kWave) reinterpret_cast<float*>(qs)[i] = load1(src + i);
@@ -310,6 +310,10 @@ int32_t launch_dv_any(const DiverseArgs& a, size_t lds, hipStream_t st) {
         case DT_SQ8: return launch_dv_dt<DT_SQ8>(a, lds, st);
         case DT_SQ4: return launch_dv_dt<DT_SQ4>(a, lds, st);
         case DT_SQ1: return launch_dv_dt<DT_SQ1>(a, lds, st);
+        case DT_SPH1: return launch_dv_dt<DT_SPH1>(a, lds, st);
+        case DT_SPH1T: return launch_dv_dt<DT_SPH1T>(a, lds, st);
+        case DT_SPH2: return launch_dv_dt<DT_SPH2>(a, lds, st);
+        case DT_SPH4: return launch_dv_dt<DT_SPH4>(a, lds, st);
     }
     set_error("diverse search: rows of dtype %d are not supported", a.ix.dtype);
     return DANN_EUNSUPPORTED;
@@ -334,7 +338,7 @@ int32_t diverse_search_device(dann_index* idx, hipStream_t st, const void* d_que
                               float* d_dists, dann_search_stats* d_stats) {
     if (nq == 0) return DANN_OK;
     DiverseArgs a{};
-    a.ix = idx->view();
+    a.ix = idx->qview();
     a.queries = d_queries;
     a.qmap = nullptr;
     a.attr = idx->d_attr;

@@ -58,7 +58,7 @@ __host__ __device__ inline uint32_t lds_queue_entries(const SearchArgs& a) {
 // bytes of the staged query: f32 vector (float rows), raw bytes (integer rows), lookup table (PQ rows)
 __host__ __device__ inline uint32_t query_lds_bytes(const IndexView& ix) {
     if (ix.dtype == DT_PQ) return ix.pq_chunks * 1024u;
-    if (ix.dtype == DT_U8 || ix.dtype == DT_I8 || dt_is_sq(ix.dtype)) return ix.layer_bytes;
+    if (ix.dtype == DT_U8 || ix.dtype == DT_I8 || dt_is_sq(ix.dtype) || dt_is_sph(ix.dtype)) return ix.qbytes;
     return ix.dim * 4u;
 }
 
@@ -1042,9 +1042,10 @@ __device__ __forceinline__ void beam_search_one(const SearchArgs& a, const uint3
                                 : (((W * R + 63u) & ~63u) > ((ix.nstart + 63u) & ~63u) ? ((W * R + 63u) & ~63u)
                                                                                        : ((ix.nstart + 63u) & ~63u));
     // fixed-length instantiations know the staged query's size (f32 vector, raw bytes, SQ-8: bytes + compensation)
-    const uint32_t qbytes = DIM > 0 ? (dt_is_sq(DT) ? sq_code_bytes(DT, (uint32_t)DIM) + 4u
-                                                    : kInt ? (uint32_t)DIM : (uint32_t)DIM * 4u)
-                                    : query_lds_bytes(ix);
+    // (spherical rows: the query's size follows its layout, a run-time property)
+    const uint32_t qbytes = DIM > 0 && !dt_is_sph(DT) ? (dt_is_sq(DT) ? sq_code_bytes(DT, (uint32_t)DIM) + 4u
+                                                                      : kInt ? (uint32_t)DIM : (uint32_t)DIM * 4u)
+                                                      : query_lds_bytes(ix);
     const SqParams sqp{ix.sq_k, ix.sq_shift_norm_sq};
     const SearchLds L = search_lds_layout(a.ht_entries, cmax, lds_queue_entries(a), qbytes, TEAM > 1);
     QT* qs = reinterpret_cast<QT*>(smem + L.q_off);
@@ -1076,9 +1077,9 @@ __device__ __forceinline__ void beam_search_one(const SearchArgs& a, const uint3
             }
         } else {
         const uint8_t* qsrc = a.qslots ? ix.rows + (uint64_t)a.qslots[qi] * ix.row_stride
-                                       : reinterpret_cast<const uint8_t*>(a.queries) + (uint64_t)qi * ix.layer_bytes;
+                                       : reinterpret_cast<const uint8_t*>(a.queries) + (uint64_t)qi * ix.qbytes;
         if constexpr (kInt) {
-            for (uint32_t i = lane; i < ix.layer_bytes; i += kWave) reinterpret_cast<uint8_t*>(qs)[i] = qsrc[i];
+            for (uint32_t i = lane; i < ix.qbytes; i += kWave) reinterpret_cast<uint8_t*>(qs)[i] = qsrc[i];
         } else {
             const RT* src = reinterpret_cast<const RT*>(qsrc);
             for (uint32_t i = lane; i < ix.dim; i += kWave) reinterpret_cast<float*>(qs)[i] = load1(src + i);
@@ -1117,7 +1118,9 @@ __device__ __forceinline__ void beam_search_one(const SearchArgs& a, const uint3
     int xx_pre = 0;
     if constexpr (DIM > 0 && kInt) {
         static_assert(!kInt || DIM == 0 || DIM == 128, "integer rows: only the 128-element length is specialised");
-        if constexpr (dt_is_packed(DT)) {  // (64 or 16 code bytes over the group's 4 lanes)
+        if constexpr (dt_is_sph(DT)) {  // (code dwords, widened 2-bit codes or the four plane dwords)
+            xqi = sph_query_pre<DT>(reinterpret_cast<const uint8_t*>(qs), v);
+        } else if constexpr (dt_is_packed(DT)) {  // (64 or 16 code bytes over the group's 4 lanes)
             xqi = packed_query_pre<sq_bits(DT)>(reinterpret_cast<const uint8_t*>(qs), v);
             xx_pre = group_norm_packed_pre<sq_bits(DT)>(xqi);
         } else {
@@ -1279,7 +1282,8 @@ __device__ __forceinline__ void beam_search_one(const SearchArgs& a, const uint3
 #pragma unroll
                     for (int u = 0; u < U; ++u) tg[u] = (act[u] && v == 0) ? rows[u][tag_off] : (uint8_t)255;
                 }
-                if constexpr (dt_is_packed(DT)) group_distance_packed_pre<sq_bits(DT), OP, U>(xqi, xx_pre, rows, v, out);
+                if constexpr (dt_is_sph(DT)) group_ip_sph_pre<DT, U>(xqi, rows, v, out);
+                else if constexpr (dt_is_packed(DT)) group_distance_packed_pre<sq_bits(DT), OP, U>(xqi, xx_pre, rows, v, out);
                 else group_distance_int_pre<OP, DT == DT_I8, U>(xqi, xx_pre, rows, v, out);
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
@@ -2588,12 +2592,12 @@ int32_t launch_dt(const SearchArgs& a, uint32_t qcap, size_t lds, hipStream_t st
         if constexpr (DT == DT_F32 || DT == DT_F16) {
             if (norm) return launch_qs<DT, OP_IP, true, 0>(a, qcap, lds, stream, regs_out);
         }
-        if constexpr (DT == DT_U8 || DT == DT_I8 || dt_is_sq(DT)) {
+        if constexpr (DT == DT_U8 || DT == DT_I8 || dt_is_sq(DT) || dt_is_sph(DT)) {
             if (a.ix.dim == 128) return launch_qs<DT, OP_IP, false, 128>(a, qcap, lds, stream, regs_out);
         }
         return launch_qs<DT, OP_IP, false, 0>(a, qcap, lds, stream, regs_out);
     }
-    if constexpr (DT == DT_U8 || DT == DT_I8) {
+    if constexpr (DT == DT_U8 || DT == DT_I8 || dt_is_sph(DT)) {
         if (a.ix.dim == 128) return launch_qs<DT, OP_COS, false, 128>(a, qcap, lds, stream, regs_out);
     }
     if constexpr (!dt_is_sq(DT) && DT != DT_PQ) return launch_qs<DT, OP_COS, false, 0>(a, qcap, lds, stream, regs_out);

@@ -247,6 +247,10 @@ int32_t launch_search(const SearchArgs& a, hipStream_t stream, int* regs_out) {
         case DT_SQ8: return launch_search_sq8(a, qcap, lds, stream, regs_out);
         case DT_SQ4: return launch_search_sq4(a, qcap, lds, stream, regs_out);
         case DT_SQ1: return launch_search_sq1(a, qcap, lds, stream, regs_out);
+        case DT_SPH1: return launch_search_sph1(a, qcap, lds, stream, regs_out);
+        case DT_SPH1T: return launch_search_sph1t(a, qcap, lds, stream, regs_out);
+        case DT_SPH2: return launch_search_sph2(a, qcap, lds, stream, regs_out);
+        case DT_SPH4: return launch_search_sph4(a, qcap, lds, stream, regs_out);
         case DT_PQ: return launch_search_pq(a, qcap, lds, stream, regs_out);
     }
     set_error("bad dtype %d", a.ix.dtype);

@@ -133,7 +133,7 @@ int32_t launch_locked(dann_index* idx, dann_server* s) {
     __atomic_store_n(&s->hv.h_ctl[0], 0u, __ATOMIC_RELAXED);
     __atomic_store_n(&s->hv.h_ctl[1], 0u, __ATOMIC_RELEASE);
     SearchArgs a;
-    a.ix = idx->view();
+    a.ix = idx->qview();
     a.queries = s->sv.d_q;
     a.nq = s->cfg.workers;
     a.l_value = s->cfg.l_value;
@@ -229,7 +229,7 @@ int32_t dann_server_start(dann_index* idx, const dann_server_config* cfg) try {
         set_error("dann_server_start: l_value, k must be non-zero and 1 <= workers <= 8192");
         return DANN_EINVAL;
     }
-    const uint32_t qbytes = idx->cfg.dtype == DT_PQ ? idx->cfg.dim * 4u : idx->layer_bytes;
+    const uint32_t qbytes = idx->query_bytes();
     if (qbytes % 16u) {
         set_error("dann_server_start: query rows of %u bytes (the server stages 16-byte units)", qbytes);
         return DANN_EUNSUPPORTED;
@@ -574,7 +574,7 @@ int32_t dann_debug_concurrent_callers(dann_index* idx, const void* queries, uint
         }
     }
     if (depth == 0) depth = 1;
-    const size_t qb = idx->cfg.dtype == DT_PQ ? (size_t)idx->cfg.dim * 4 : idx->layer_bytes;
+    const size_t qb = idx->query_bytes();
     std::atomic<int32_t> status{DANN_OK};
     std::atomic<uint32_t> ready{0};
     std::atomic<bool> go{false};

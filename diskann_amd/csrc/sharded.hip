@@ -485,7 +485,7 @@ static int32_t search_sharded_impl(dann_index* idx, dann_comm* comm, const void*
     *past_args = true;  // (from here on an error may be this rank's alone: AbortOnError releases the peers)
     if (!idx) return DANN_EINVAL;
     const uint32_t world = comm->world, rank = comm->rank;
-    const size_t qb = idx->cfg.dtype == DT_PQ ? (size_t)idx->cfg.dim * 4 : idx->layer_bytes;
+    const size_t qb = idx->query_bytes();
     uint32_t lo, hi, l0, h0;
     partition(nq, world, rank, &lo, &hi);
     partition(nq, world, 0, &l0, &h0);
@@ -655,7 +655,7 @@ int32_t dann_multi_search_batch(dann_multi* m, const void* queries, uint32_t nq,
     if (!queries || !out_ids || !out_dists) return DANN_EINVAL;
     const uint32_t world = (uint32_t)m->replica.size();
     const dann_index* i0 = m->replica[0];
-    const size_t qb = i0->cfg.dtype == DT_PQ ? (size_t)i0->cfg.dim * 4 : i0->layer_bytes;
+    const size_t qb = i0->query_bytes();
     // the query block is partitioned over the replicas (async_tools.rs:289-365); every slice lands in place
     return for_each_rank(world, [&](uint32_t r) -> int32_t {
         uint32_t lo, hi;

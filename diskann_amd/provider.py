@@ -14,10 +14,11 @@ import os
 import numpy as np
 
 from . import _ffi
-from ._ffi import (BuildConfig, Config, DannError, SearchStats, check, F32, F16, U8, I8, SQ8, SQ1, SQ4, PQ, COSINE, INNER_PRODUCT, L2,
+from ._ffi import (BuildConfig, Config, DannError, SearchStats, check, F32, F16, U8, I8, SQ8, SQ1, SQ4, SPH1, SPH2, SPH4, PQ, COSINE, INNER_PRODUCT, L2,
                    COSINE_NORMALIZED, IBC_ALL, IBC_NONE)
 
-NP_DTYPE = {F32: np.float32, F16: np.float16, U8: np.uint8, I8: np.int8, SQ8: np.uint8, SQ1: np.uint8, SQ4: np.uint8, PQ: np.uint8}
+NP_DTYPE = {F32: np.float32, F16: np.float16, U8: np.uint8, I8: np.int8, SQ8: np.uint8, SQ1: np.uint8, SQ4: np.uint8, SPH1: np.uint8, SPH2: np.uint8,
+            SPH4: np.uint8, PQ: np.uint8}
 FILTER_INLINE, FILTER_MULTIHOP = 1, 2  # dann.h DANN_FILTER_*
 STATS_DTYPE = np.dtype([("cmps", np.uint32), ("hops", np.uint32), ("result_count", np.uint32), ("status", np.uint32),
                         ("written", np.uint32)])
@@ -82,11 +83,13 @@ class Provider:
     """diskann_inmem::Provider<Full<T>, u32> + DiskANNIndex, resident in one GPU's HBM."""
 
     def __init__(self, dtype, metric, dim, capacity, max_degree, start_points, row_stride=0, device=-1,
-                 sq_scale=0.0, sq_shift_norm_sq=0.0, pq_pivots=None, pq_offsets=None, inline_tags=False):
+                 sq_scale=0.0, sq_shift_norm_sq=0.0, pq_pivots=None, pq_offsets=None, inline_tags=False, query_layout=0):
         self.dtype, self.metric, self.dim = dtype, metric, int(dim)
         self.capacity, self.max_degree = int(capacity), int(max_degree)
-        # scalar-quantised rows are their payload bytes: the code bytes and a trailing f32 compensation
-        self.row_elems = int(_ffi.lib().dann_layer_bytes(dtype, self.dim)) if dtype in (SQ8, SQ4, SQ1) else self.dim
+        # quantised rows are their payload bytes: the code bytes and a trailing f32 compensation (scalar) or DataMeta
+        # (spherical)
+        self.row_elems = (int(_ffi.lib().dann_layer_bytes(dtype, self.dim))
+                          if dtype in (SQ8, SQ4, SQ1, SPH1, SPH2, SPH4) else self.dim)
         self.query_dtype, self.query_elems = NP_DTYPE[dtype], self.row_elems
         pq_chunks = 0
         if dtype == PQ:  # rows are PQ codes, queries stay full-precision f32
@@ -110,6 +113,8 @@ class Provider:
             piv = np.ascontiguousarray(pq_pivots, dtype=np.float32)
             assert piv.shape == (256, self.dim)
             check(_ffi.lib().dann_set_pq_table(self._h, _p(piv), _p(pq_offsets)), "dann_set_pq_table")
+        if query_layout:
+            self.set_query_layout(query_layout)
         # developer convenience for A/B scripts (scratch/, profiles/): DANN_<SWITCH>=<value> in the environment of the
         # *Python* process is applied to every Provider it creates; the library itself reads no environment variable
         for name in _ffi.DBG_KEYS:
@@ -127,6 +132,19 @@ class Provider:
             self.close()
         except Exception:
             pass
+
+    # -- spherical rows: iface::QueryLayout ----------------------------------
+    def set_query_layout(self, layout):
+        """the byte image of the queries every query-taking method reads from now on (_ffi.QUERY_*)"""
+        check(_ffi.lib().dann_set_query_layout(self._h, int(layout)), "dann_set_query_layout")
+        self.query_elems = self.query_bytes() // np.dtype(self.query_dtype).itemsize
+
+    def query_layout(self):
+        return int(_ffi.lib().dann_get_query_layout(self._h))
+
+    def query_bytes(self):
+        """bytes of one query under the current layout"""
+        return int(_ffi.lib().dann_query_bytes(self._h))
 
     # -- SetElement ---------------------------------------------------------
     def set_element(self, slot, vector):

@@ -56,8 +56,33 @@ typedef enum {
      * Metrics, queries and sq_scale / sq_shift_norm_sq as for DANN_SQ8; the epilogue's constant is
      * (1/(2^bits - 1))^2 * scale^2.  Bits beyond dim never take part, whatever they hold. */
     DANN_SQ1 = 17,
-    DANN_SQ4 = 20
+    DANN_SQ4 = 20,
+    /* spherically quantised rows (RaBitQ), value 32 + bits: the back-canonical byte image of spherical::Data<NBITS>
+     * (diskann-quantization/src/spherical/vectors.rs) -- ceil(dim * bits / 8) code bytes in the Dense permutation,
+     * packed as DANN_SQ1 / DANN_SQ4, then the 6-byte DataMeta (:219-247): f16 inner_product_correction, f16
+     * metric_specific, u16 bit_sum.  `dim` is the quantiser's output dimension (SphericalQuantizer::output_dim(); a
+     * padding transform makes it differ from the data's) and dim * (2^bits - 1) must fit the u16 (else DANN_EINVAL).
+     * Metrics: DANN_L2, DANN_INNER_PRODUCT, DANN_COSINE (SupportedMetric; DANN_COSINE_NORMALIZED: DANN_EINVAL).
+     * Distances are CompensatedSquaredL2 / CompensatedIP / CompensatedCosine (:494-528 the kernel, :584-636 L2,
+     * :744-801 inner product, :867-892 cosine), bit for bit.  sq_shift_norm_sq carries CompensatedIP::squared_shift_norm
+     * (inner product and cosine), sq_scale is ignored.  The host keeps the SphericalQuantizer and hands over byte images
+     * of rows and queries; the form of a query is set with dann_set_query_layout().  Elements at or beyond dim never
+     * take part, whatever the padding bits hold. */
+    DANN_SPH1 = 33,
+    DANN_SPH2 = 34,
+    DANN_SPH4 = 36
 } dann_dtype;
+
+/* iface::QueryLayout: the byte image of a query of a spherical index.  QueryMeta is four f32: inner_product_correction,
+ * bit_sum, offset, metric_specific (spherical/vectors.rs:381-399). */
+typedef enum {
+    DANN_QUERY_SAME_AS_DATA = 0,        /* a row image, code bytes + 6 (every width; the default)                      */
+    DANN_QUERY_FOUR_BIT_TRANSPOSED = 1, /* 1-bit rows: per block of 64 elements four u64 words, word j = bit j of the
+                                           64 four-bit values (bits/distances.rs:2123-2249): ceil(dim / 64) * 32 plane
+                                           bytes, then the QueryMeta                                                   */
+    DANN_QUERY_SCALAR_QUANTIZED = 2,    /* 2- and 4-bit rows: Dense codes of the rows' width, then the QueryMeta        */
+    DANN_QUERY_FULL_PRECISION = 3       /* reserved: DANN_EUNSUPPORTED                                                  */
+} dann_query_layout;
 
 /* == `#[repr(C)] enum Metric`, diskann-vector/src/distance/metric.rs:8-20 */
 typedef enum {
@@ -399,6 +424,16 @@ int32_t dann_load_vectors_bin(dann_index* idx, const char* path, uint32_t first_
 /* attach the PQ schema of a DANN_PQ index: pivots 256 x dim f32 row-major, chunk_offsets pq_chunks + 1
  * (FixedChunkPQTable::new, fixed_chunk_pq_table.rs:105-140) */
 int32_t dann_set_pq_table(dann_index* idx, const float* pivots, const uint32_t* chunk_offsets);
+/* Spherical indexes: the layout of the queries that every entry point taking `queries`, `query` or `d_queries` reads
+ * (dann_query_bytes() each).  Read on every call; a dann_query keeps the layout it was created under.  Whatever uses a
+ * stored row as the query -- build and insert searches, dann_search_record_batch, prunes, dann_distance_pairs,
+ * consolidation, in-place deletes -- is always the symmetric row x row form.  A layout the row width does not have:
+ * DANN_EUNSUPPORTED (UnsupportedQueryLayout); while the search server runs: DANN_EBUSY; any other index accepts only
+ * DANN_QUERY_SAME_AS_DATA. */
+int32_t dann_set_query_layout(dann_index* idx, int32_t layout);
+int32_t dann_get_query_layout(const dann_index* idx);
+/* bytes of one query under the current layout (every row type: f32 vectors for DANN_PQ, else the row's payload) */
+int32_t dann_query_bytes(const dann_index* idx);
 /* Optional GPU-private search layout of a DANN_PQ index (at most 64 chunks, no inline tags): for every slot one
  * 64-byte-aligned row holding its adjacency list AND the code rows of its neighbours, so that a hop of the beam search
  * (expand_beam over PQ rows: diskann-providers/src/model/pq/fixed_chunk_pq_table.rs:82-100 per neighbour) is one
