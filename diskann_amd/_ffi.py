@@ -212,6 +212,7 @@ SYMBOLS = {
     "dann_debug_get": (_i32, [_vp, _i32, _P(C.c_double)]),
     "dann_debug_search_families": (_i32, [_vp, _P(_u64), _P(C.c_double)]),
     "dann_debug_small_call_stats": (_i32, [_vp, _P(_u64)]),
+    "dann_debug_sched_pivots": (_i32, [_vp, _vp, _u32, _P(_u32), _P(_u32), _P(_f32)]),
     "dann_debug_family_name": (C.c_char_p, [_i32]),
     "dann_debug_pq_rolling_sum_stats": (_i32, [_i32, _P(_u64), _i32]),
 }
@@ -221,7 +222,7 @@ DBG_KEYS = {"tune_off": 0, "tune_on": 1, "pair_min_queries": 2, "team_max_querie
             "sweep_one_by_one": 5, "pool_gram": 6, "gram_cols": 7, "gram_escale": 8, "backedge_gram_rows": 9,
             "server_max_resident_us": 10, "verbose": 11, "ht16_open_eighths": 12, "backedge_single_pool": 13,
             "ht16_max_probes": 14, "host_chunk": 15, "gram_f16_widen": 16, "time_small_launches": 17,
-            "sched_min_queries": 18, "diverse_pool": 19}
+            "sched_min_queries": 18, "diverse_pool": 19, "sched_lloyd_iters": 20}
 FAMILIES = ("one_wave", "team", "pair", "persistent", "server", "pq_lut", "diverse")
 
 _lib = None

@@ -1756,6 +1756,14 @@ int32_t dann_debug_get(const dann_index* idx, int32_t key, double* value) try {
     return DANN_OK;
 } DANN_CATCH_ALL
 
+int32_t dann_debug_sched_pivots(dann_index* idx, float* out, uint32_t cap_floats, uint32_t* np, uint32_t* stride_halfs,
+                                float* scale) try {
+    if (!idx) return DANN_EINVAL;
+    ::dann::ExclusiveGuard lock(idx);  // no search is building them meanwhile
+    DeviceGuard guard(idx->device);
+    return sched_copy_pivots(idx, out, cap_floats, np, stride_halfs, scale);
+} DANN_CATCH_ALL
+
 int32_t dann_debug_small_call_stats(dann_index* idx, uint64_t* out2) try {
     if (!idx || !out2) return DANN_EINVAL;
     out2[0] = idx->comb.stats[0].load(std::memory_order_relaxed);

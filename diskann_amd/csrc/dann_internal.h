@@ -224,6 +224,9 @@ int32_t launch_search(const SearchArgs& a, hipStream_t stream, int* regs_out = n
 uint32_t sched_pivot_count(uint32_t dim);
 size_t sched_scratch_words(uint32_t dim, uint32_t nq);
 int32_t sched_build_pivots(dann_index* idx, hipStream_t st);
+// dann_debug_sched_pivots: the pivot slab as unscaled f32 (DANN_EINVAL before the first scheduled search)
+int32_t sched_copy_pivots(const dann_index* idx, float* out, uint32_t cap_floats, uint32_t* out_np, uint32_t* out_stride,
+                          float* out_scale);
 int32_t sched_build_map(const dann_index* idx, hipStream_t st, const void* queries, uint32_t nq, uint32_t parts,
                         uint32_t* scratch, uint32_t* qmap);
 // one translation unit per row type (search_<type>.hip) holds the kernel instantiations
@@ -364,8 +367,9 @@ struct dann_index {
     size_t pq_pack_bytes = 0;
     uint32_t pq_pack_stride = 0, pq_pack_codes = 0;
     bool pq_pack_valid = false;
-    // locality scheduling of large search launches (query_schedule.hip): the pivot rows in the key kernel's layout, built
-    // on the first scheduled search and again on the first one after a mutation (sched_mu; they only ever affect speed)
+    // locality scheduling of large search launches (query_schedule.hip): the pivots (centres trained from rows taken at a
+    // fixed stride) in the key kernel's layout, built on the first scheduled search and again on the first one after a
+    // mutation (sched_mu; they only ever affect speed)
     _Float16* d_sched_piv = nullptr;
     bool sched_stale = true;
     std::mutex sched_mu;

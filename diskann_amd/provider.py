@@ -549,6 +549,17 @@ class Provider:
             v = float("nan") if value is None else float(value)
             check(_ffi.lib().dann_debug_set(self._h, _ffi.DBG_KEYS[name], v), "dann_debug_set")
 
+    def sched_pivots(self):
+        """(pivots as unscaled f32 [np, dim], scale) of the locality scheduling, as the key pass sees them; raises before
+        the first scheduled search has built them"""
+        npv, stride, scale = C.c_uint32(), C.c_uint32(), C.c_float()
+        L = _ffi.lib()
+        check(L.dann_debug_sched_pivots(self._h, None, 0, C.byref(npv), C.byref(stride), C.byref(scale)), "dann_debug_sched_pivots")
+        out = np.empty((npv.value, stride.value), np.float32)
+        check(L.dann_debug_sched_pivots(self._h, out.ctypes.data_as(C.c_void_p), out.size, C.byref(npv), C.byref(stride),
+                                        C.byref(scale)), "dann_debug_sched_pivots")
+        return out[:, :self.dim].copy(), float(scale.value)
+
     def search_families(self):
         """{family: (launches, HIP-event ms)} of the beam-search launches since the last kernel_time_reset()"""
         n = len(_ffi.FAMILIES)

@@ -72,7 +72,10 @@ enum {
                                             16384) */
     DANN_DBG_DIVERSE_POOL = 19,          /* test hook: entries of the LDS pool of the diverse search's local queues (default
                                             2 L + 64); a smaller pool sends more queries to the exact global-memory re-run */
-    DANN_DBG_COUNT = 20
+    DANN_DBG_SCHED_LLOYD_ITERS = 20,     /* Lloyd iterations that move the scheduling pivots from rows taken at a fixed stride
+                                            to centres of a row sample, when the pivots are (re)built (0: the rows
+                                            themselves; at most 64; default 4) */
+    DANN_DBG_COUNT = 21
 };
 int32_t dann_debug_set(dann_index* idx, int32_t key, double value);
 int32_t dann_debug_get(const dann_index* idx, int32_t key, double* value);
@@ -93,6 +96,13 @@ enum {
 int32_t dann_debug_search_families(const dann_index* idx, uint64_t* out_launches, double* out_ms);
 /* family name for logs ("one_wave", "team", "pair", "persistent", "server", "pq_lut", "diverse"); null for an unknown family */
 const char* dann_debug_family_name(int32_t family);
+
+/* the pivots of the locality scheduling as the key pass sees them, unscaled: *np rows of *stride_halfs floats into out
+ * (the first dim of each row are coordinates, the rest padding), *scale = the power of two they are stored with.  Any
+ * pointer may be null; DANN_EINVAL before the first scheduled search has built them, DANN_ELENGTH when cap_floats is
+ * less than *np x *stride_halfs. */
+int32_t dann_debug_sched_pivots(dann_index* idx, float* out, uint32_t cap_floats, uint32_t* np, uint32_t* stride_halfs,
+                                float* scale);
 
 /* small dann_search_batch calls (host pointers, at most 16 queries) of several threads share launches: out2 = {launches,
  * calls served by them} since the index was created -- calls / launches is the mean number of calls per launch */
