@@ -21,20 +21,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "row_types.h"  // DT_* / M_* / OP_*, dt_is_*, resolve_metric, kEmpty
+
 namespace dann {
 
-enum : int {
-    DT_F32 = 0, DT_F16 = 1, DT_U8 = 2, DT_I8 = 3, DT_SQ8 = 4, DT_PQ = 5, DT_SQ1 = 17, DT_SQ4 = 20,
-    // spherically quantised rows (spherical::Data<NBITS>), dtype value 32 + bits
-    DT_SPH1 = 33, DT_SPH2 = 34, DT_SPH4 = 36,
-    // internal, never a dann_config::dtype: DT_SPH1 rows searched with a FOUR_BIT_TRANSPOSED query (IndexView::dtype
-    // of the query-taking entry points; the inner-product routine differs, so the layout is a template argument)
-    DT_SPH1T = 97
-};
-// scalar-quantised rows: SQ-8 (one byte per code) and the packed widths, whose dtype value is 16 + bits
-__host__ __device__ constexpr bool dt_is_sq(int dt) { return dt == DT_SQ8 || dt == DT_SQ4 || dt == DT_SQ1; }
-__host__ __device__ constexpr bool dt_is_sph(int dt) { return dt == DT_SPH1 || dt == DT_SPH2 || dt == DT_SPH4 || dt == DT_SPH1T; }
-__host__ __device__ constexpr bool dt_is_packed(int dt) { return dt == DT_SQ4 || dt == DT_SQ1 || dt_is_sph(dt); }
 __host__ __device__ constexpr int sq_bits(int dt) { return dt == DT_SQ8 ? 8 : dt_is_sph(dt) ? (dt & 7) : dt - 16; }
 // query layouts of spherical rows (iface::QueryLayout; dann.h DANN_QUERY_*)
 enum : int { QL_SAME = 0, QL_TRANSPOSED = 1, QL_SCALAR = 2, QL_FULL = 3 };
@@ -44,10 +34,6 @@ constexpr uint32_t kSphDataMeta = 6u, kSphQueryMeta = 16u;  // bytes of DataMeta
 __host__ __device__ constexpr uint32_t sq_code_bytes(int dt, uint32_t dim) {
     return (uint32_t)(((uint64_t)dim * (uint32_t)sq_bits(dt) + 7u) >> 3);
 }
-enum : int { M_COSINE = 0, M_IP = 1, M_L2 = 2, M_COSN = 3 };
-enum : int { OP_L2 = 0, OP_IP = 1, OP_COS = 2 };
-
-constexpr uint32_t kEmpty = 0xFFFFFFFFu;
 constexpr uint32_t kVisitedBit = 0x80000000u;
 
 // DPP controls (cdna4 ISA: quad_perm = 0x00-0xFF, row_shl:n = 0x100+n)
@@ -1254,37 +1240,6 @@ __device__ __forceinline__ float finish_distance(float raw, const uint8_t* x, co
         const float r = __builtin_fmaf(sq.k, raw, sq.shift_norm_sq) + (cy + cx);
         return -r;
     }
-}
-
-// (dtype, metric) -> (OP, NORMALIZED).  Integers treat CosineNormalized as Cosine
-// (distance_provider.rs:274-297, full.rs:470,499); SQ-8 / SQ4 / SQ1 CosineNormalized is L2-based.
-// Returns false for unsupported combinations (scalar-quantised rows have no plain Cosine).
-__host__ __device__ inline bool resolve_metric(int dtype, int metric, int* op, bool* norm) {
-    *norm = false;
-    if (dtype == DT_PQ) {
-        if (metric == M_L2) { *op = OP_L2; return true; }
-        if (metric == M_IP) { *op = OP_IP; return true; }
-        return false;
-    }
-    if (dt_is_sph(dtype)) {  // SupportedMetric (spherical/mod.rs): SquaredL2, InnerProduct, Cosine
-        if (metric == M_L2) { *op = OP_L2; return true; }
-        if (metric == M_IP) { *op = OP_IP; return true; }
-        if (metric == M_COSINE) { *op = OP_COS; return true; }
-        return false;
-    }
-    if (dt_is_sq(dtype)) {
-        if (metric == M_L2) { *op = OP_L2; return true; }
-        if (metric == M_IP) { *op = OP_IP; return true; }
-        if (metric == M_COSN) { *op = OP_L2; *norm = true; return true; }
-        return false;
-    }
-    if (metric == M_L2) { *op = OP_L2; return true; }
-    if (metric == M_IP) { *op = OP_IP; return true; }
-    if (metric == M_COSINE) { *op = OP_COS; return true; }
-    if (dtype == DT_U8 || dtype == DT_I8) { *op = OP_COS; return true; }
-    *op = OP_IP;
-    *norm = true;  // CosineNormalized on float rows = 1 - <x, y>
-    return true;
 }
 
 }  // namespace dann

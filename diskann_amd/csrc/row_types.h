@@ -1,0 +1,62 @@
+// The row-type and metric vocabulary shared by the kernels (dann_device.h) and the host-side launch planning
+// (launch_plan.h).  No HIP here: tests/test_launch_plan_host.py compiles it with g++.
+#pragma once
+#include <stdint.h>
+
+#ifdef __HIPCC__
+#define DANN_HD __host__ __device__
+#else
+#define DANN_HD
+#endif
+
+namespace dann {
+
+enum : int {
+    DT_F32 = 0, DT_F16 = 1, DT_U8 = 2, DT_I8 = 3, DT_SQ8 = 4, DT_PQ = 5, DT_SQ1 = 17, DT_SQ4 = 20,
+    // spherically quantised rows (spherical::Data<NBITS>), dtype value 32 + bits
+    DT_SPH1 = 33, DT_SPH2 = 34, DT_SPH4 = 36,
+    // internal, never a dann_config::dtype: DT_SPH1 rows searched with a FOUR_BIT_TRANSPOSED query (IndexView::dtype
+    // of the query-taking entry points; the inner-product routine differs, so the layout is a template argument)
+    DT_SPH1T = 97
+};
+// scalar-quantised rows: SQ-8 (one byte per code) and the packed widths, whose dtype value is 16 + bits
+DANN_HD constexpr bool dt_is_sq(int dt) { return dt == DT_SQ8 || dt == DT_SQ4 || dt == DT_SQ1; }
+DANN_HD constexpr bool dt_is_sph(int dt) { return dt == DT_SPH1 || dt == DT_SPH2 || dt == DT_SPH4 || dt == DT_SPH1T; }
+DANN_HD constexpr bool dt_is_packed(int dt) { return dt == DT_SQ4 || dt == DT_SQ1 || dt_is_sph(dt); }
+enum : int { M_COSINE = 0, M_IP = 1, M_L2 = 2, M_COSN = 3 };
+enum : int { OP_L2 = 0, OP_IP = 1, OP_COS = 2 };
+
+constexpr uint32_t kEmpty = 0xFFFFFFFFu;
+
+// (dtype, metric) -> (OP, NORMALIZED).  Integers treat CosineNormalized as Cosine
+// (distance_provider.rs:274-297, full.rs:470,499); SQ-8 / SQ4 / SQ1 CosineNormalized is L2-based.
+// Returns false for unsupported combinations (scalar-quantised rows have no plain Cosine).
+DANN_HD inline bool resolve_metric(int dtype, int metric, int* op, bool* norm) {
+    *norm = false;
+    if (dtype == DT_PQ) {
+        if (metric == M_L2) { *op = OP_L2; return true; }
+        if (metric == M_IP) { *op = OP_IP; return true; }
+        return false;
+    }
+    if (dt_is_sph(dtype)) {  // SupportedMetric (spherical/mod.rs): SquaredL2, InnerProduct, Cosine
+        if (metric == M_L2) { *op = OP_L2; return true; }
+        if (metric == M_IP) { *op = OP_IP; return true; }
+        if (metric == M_COSINE) { *op = OP_COS; return true; }
+        return false;
+    }
+    if (dt_is_sq(dtype)) {
+        if (metric == M_L2) { *op = OP_L2; return true; }
+        if (metric == M_IP) { *op = OP_IP; return true; }
+        if (metric == M_COSN) { *op = OP_L2; *norm = true; return true; }
+        return false;
+    }
+    if (metric == M_L2) { *op = OP_L2; return true; }
+    if (metric == M_IP) { *op = OP_IP; return true; }
+    if (metric == M_COSINE) { *op = OP_COS; return true; }
+    if (dtype == DT_U8 || dtype == DT_I8) { *op = OP_COS; return true; }
+    *op = OP_IP;
+    *norm = true;  // CosineNormalized on float rows = 1 - <x, y>
+    return true;
+}
+
+}  // namespace dann

@@ -1,6 +1,39 @@
 // Beam-search kernel, its device helpers and the launch dispatch.  Included by one translation unit per row type
-// (search_f32.hip ... search_pq.hip) so the instantiations compile in parallel, and by search_kernels.hip for the
-// host-side sizing helpers.  Everything lives in an anonymous namespace: each includer gets its own copy.
+// (search_f32.hip ... search_pq.hip) so the instantiations compile in parallel; the sizing helpers the host shares
+// with the kernels are in launch_shape.h.  Everything lives in an anonymous namespace: each includer gets its own copy.
+//
+// Batched Vamana beam search, one wavefront per query.
+//
+// Replaces, for a batch of independent queries, the reference call chain
+//   DiskANNIndex::search_internal          diskann/src/graph/index.rs:1933-2000
+//     NeighborPriorityQueue                diskann/src/neighbor/queue.rs:130-318
+//     SearchAccessor::expand_beam          diskann-inmem/src/provider.rs:436-480
+//       Neighbors::get                     diskann-inmem/src/neighbors.rs:124-163
+//       NotInMut (visited set)             diskann/src/graph/glue.rs:524-561
+//       expand_beam_inner + QueryDistance  diskann-inmem/src/provider.rs:620-690, layers/full.rs:317-336
+//   Translate::post_process                diskann-inmem/src/provider.rs:899-950
+// with results identical to the CPU path (ids, distances, cmps, hops).
+//
+// Design (MI355X): the whole beam loop of one query runs inside one 64-lane wavefront
+// (workgroup = 1 wave, so the only barriers are wave-local).  Per hop:
+//   1. pop the W closest unexpanded queue entries (ballot + readlane; the sorted L-queue
+//      lives in registers, entry p in lane p%64 slot p/64);
+//   2. read their adjacency rows (one coalesced 4*(R+1)-byte read each), test-and-insert
+//      every neighbour id into an exact open-addressing visited table in LDS
+//      (ds_cmpst), compact the survivors in adjacency order (ballot + mbcnt);
+//   3. gather: G lanes per surviving candidate row, 16-byte loads, 64/G rows per
+//      wave-instruction, U rows in flight per lane group -- random 512-byte rows are
+//      read as whole 128-byte lines; FMA chains in the reference's association order;
+//   4. merge the (id, dist) batch into the queue by rank: the sequential
+//      `insert` calls of index.rs:1986-1988 keep the best `capacity` elements under the
+//      total order (distance asc, insertion time desc) -- queue.rs:142-170: lower-bound
+//      insertion puts a new element *before* equal-distance ones, a full queue drops its
+//      last element, and an element worse than the last is rejected -- so inserting a
+//      batch one by one equals taking the top-`capacity` of old ∪ new under that order.
+//      Ranks are computed with wave-uniform readlane broadcasts, the permutation goes
+//      through an LDS staging buffer.
+// HBM traffic per query = cmps * row bytes + hops * adjacency row; everything else stays
+// in registers/LDS.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -10,12 +43,11 @@
 #include "dann_device.h"
 #include "rust_order.h"
 #include "dann_internal.h"
+#include "launch_shape.h"  // kWave, kMaxBeam, kTune*, the LDS layouts, plain_mode / team_shape / pair_shape / pq_lut_shape
 
 namespace dann {
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kMaxBeam = 16;
 constexpr int kGatherRows = 4;
 #ifndef DANN_WIDE_ROWS
 #define DANN_WIDE_ROWS 2
@@ -29,9 +61,6 @@ constexpr uint32_t kRegMerge = DANN_REG_MERGE;  // survivors handled by the in-r
 #define DANN_SEQ_INSERT 2
 #endif
 constexpr uint32_t kSeqInsert = DANN_SEQ_INSERT;  // survivors inserted one by one, the queue never leaving its registers
-constexpr uint32_t kTuneRowPrefetch = 1u;  // SearchArgs::tune bits
-constexpr uint32_t kTuneNoSpeculation = 2u;  // teams: no speculative expansion of the predicted next node
-constexpr uint32_t kTuneNoSelfStart = 4u;    // teams: the visited wave always waits for the control wave's words
 constexpr uint8_t kTagPublished = 254;  // Tag::can_read: tag >= PUBLISHED (diskann-inmem/src/tag.rs:86-133)
 
 // optional per-phase cycle accounting (compile with -DDANN_PHASE_CYCLES; debug only)
@@ -42,71 +71,6 @@ constexpr uint8_t kTagPublished = 254;  // Tag::can_read: tag >= PUBLISHED (disk
 #define PH_T(var)
 #define PH_ADD(idx, t0, t1)
 #endif  // rows in flight per lane group in the fixed-length gather
-
-constexpr uint32_t kAdjLandBytes = 256u;
-struct SearchLds {
-    uint32_t ht_off, cand_id_off, cand_d_off, cand2_id_off, cand2_d_off, adj_off, slots_off, mscr_off, mail_off, stage_off, snew_off, beam_off, q_off, total;
-};
-
-__host__ __device__ inline uint32_t round16(uint32_t x) { return (x + 15u) & ~15u; }
-// entries of the queue image in LDS: the largest capacity the queue can have during the search
-__host__ __device__ inline uint32_t lds_queue_entries(const SearchArgs& a) {
-    const uint32_t q = a.l_value + a.ix.nstart;
-    return q > a.qcap_max ? q : a.qcap_max;
-}
-
-// bytes of the staged query: f32 vector (float rows), raw bytes (integer rows), lookup table (PQ rows)
-__host__ __device__ inline uint32_t query_lds_bytes(const IndexView& ix) {
-    if (ix.dtype == DT_PQ) return ix.pq_chunks * 1024u;
-    if (ix.dtype == DT_U8 || ix.dtype == DT_I8 || dt_is_sq(ix.dtype) || dt_is_sph(ix.dtype)) return ix.qbytes;
-    return ix.dim * 4u;
-}
-
-// The queue image and the visited table come last, in that order: every other region then sits at an offset that
-// depends only on (cmax, query bytes) -- compile-time constants in the plain fixed-length instantiations, where the
-// region pointers cost no SGPRs and the LDS instructions carry immediate offsets; the image is sized by the queue's
-// real capacity `qcap` (L + start points, or what AdaptiveL may grow it to), not by its register slots, so the table's
-// offset is the one run-time offset.  (Every byte counts: at 1 M x 128-byte rows the table caps the queries per CU.)
-__host__ __device__ inline SearchLds search_lds_layout(uint32_t ht_entries, uint32_t cmax, uint32_t qcap,
-                                                       uint32_t qbytes, bool team = false) {
-    SearchLds l;
-    uint32_t off = 0;
-    l.q_off = off;
-    off += round16(qbytes);
-    l.cand_id_off = off;
-    off += round16(cmax * 4u);
-    l.cand_d_off = off;
-    off += round16(cmax * 4u);
-    // teams: a second candidate buffer -- the visited wave fills it with the next hop's candidates while the gather wave
-    // still evaluates the current hop's (the speculative expansion of the predicted next node, §3.5 of DESIGN.md)
-    l.cand2_id_off = off;
-    if (team) off += round16(cmax * 4u);
-    l.cand2_d_off = off;
-    if (team) off += round16(cmax * 4u);
-    // teams: two landing buffers of 64 dwords for adjacency rows requested ahead of their use (length + at most 63
-    // neighbours each; the loads write LDS directly, see adj_fetch_lds)
-    l.adj_off = off;
-    if (team) off += 2u * kAdjLandBytes;
-    // teams: the table slots of the visited wave's speculative inserts (wave 0 takes them back through these), and 64
-    // (id, distance) words of scratch for wave 0's merge (the candidate buffer it merges from is already being refilled)
-    l.slots_off = off;
-    if (team) off += 256u;
-    l.mscr_off = off;
-    if (team) off += 512u;
-    l.mail_off = off;  // teams: the mailbox the four waves of a team talk through (64 words, see kMb*)
-    if (team) off += 256u;
-    l.beam_off = off;
-    off += round16(kMaxBeam * 4u);
-    l.stage_off = off;  // the queue image, (id, distance bits) pairs: every merge scatters the register-resident queue
-    off += round16(qcap * 8u);  // here and reloads it (one 8-byte LDS access per entry).  One buffer is enough: nothing
-                                // is read from it between the first scatter write and the reload (ranks come from
-                                // registers or were taken before), and one wave's LDS operations retire in order.
-    l.snew_off = l.cand_id_off;  // (unused: the slow merge keeps its sorted survivors in the candidates' own buffer)
-    l.ht_off = off;        // 16-byte aligned (wiped with 16-byte stores)
-    off += ht_entries * 4u;  // any multiple of 64
-    l.total = off;
-    return l;
-}
 
 // exact visited set: open addressing, linear probing, ds_cmpst.  == hashbrown::HashSet::insert
 // (glue.rs:542-549).  Two levels: the LDS table takes ids until it is 75 % full ("open");
@@ -2481,12 +2445,6 @@ __global__ __launch_bounds__(kWave * TEAM) DANN_SEARCH_KERNEL_ATTR void beam_sea
     }
 }
 
-// what kModePlain assumes (checked by the host for every launch)
-inline bool plain_mode(const SearchArgs& a) {
-    return !a.filter_mode && a.beam_width == 1 && a.ix.tag_off == 0 && a.ix.max_degree <= (uint32_t)kWave &&
-           a.ix.nstart <= (uint32_t)kWave;
-}
-
 #ifndef DANN_TEAM_WAVES
 #define DANN_TEAM_WAVES 5
 #endif
@@ -2603,26 +2561,6 @@ int32_t launch_dt(const SearchArgs& a, uint32_t qcap, size_t lds, hipStream_t st
     if constexpr (!dt_is_sq(DT) && DT != DT_PQ) return launch_qs<DT, OP_COS, false, 0>(a, qcap, lds, stream, regs_out);
     return DANN_EUNSUPPORTED;
 }
-
-// does a team instantiation exist for this launch?  (launch_one: plain mode, a fixed-length kernel -- 128-element rows
-// of the metric's specialised form --, at most 256 queue entries, not PQ rows; launch_dt's case analysis)
-inline bool team_shape(const SearchArgs& a) {
-    int op;
-    bool norm;
-    const int dt = a.ix.dtype;
-    if (!plain_mode(a) || dt == DT_PQ || dt_is_packed(dt) || a.ix.dim != 128u || !resolve_metric(dt, a.ix.metric, &op, &norm)) return false;
-    if (std::max(a.l_value + a.ix.nstart, a.qcap_max) > 256u) return false;
-    const bool ints = dt == DT_U8 || dt == DT_I8 || dt == DT_SQ8;
-    if (op == OP_L2) return true;
-    if (op == OP_IP) return ints;  // (float rows: inner product and CosineNormalized run the generic-length kernel)
-    return dt == DT_U8 || dt == DT_I8;
-}
-
-uint32_t cmax_of(const SearchArgs& a) {
-    uint32_t c1 = (a.beam_width * a.ix.max_degree + 63u) & ~63u, c2 = (a.ix.nstart + 63u) & ~63u;
-    return c1 > c2 ? c1 : c2;
-}
-uint32_t qs_of(uint32_t qcap) { return qcap <= 64 ? 1 : qcap <= 128 ? 2 : qcap <= 256 ? 4 : qcap <= 512 ? 8 : 16; }
 
 }  // namespace
 }  // namespace dann

@@ -32,51 +32,6 @@
 namespace dann {
 namespace {
 
-constexpr uint32_t kPairHalf = 32;
-// LDS of one half: candidates (ids, distances), the scatter buffer of the merge ((id, distance) pairs), the queue's
-// distances in order (what the lower-bound searches read), the survivors' distances of one merge, a sink for the
-// stores of lanes that have nothing to store, the visited table.  QE = queue entries per lane (1: L + start points <=
-// 32, 2: <= 64), RE = adjacency ids per lane (1: degree <= 32, 2: <= 64).
-struct PairLds {
-    uint32_t cand_id_off, cand_d_off, stage_off, qimg_off, qpiv_off, sd_off, sink_off, ht_off, ov_off, half_bytes;
-};
-// keys of the queue image: a power of two beyond the queue's entries (the lower-bound search needs no bound check)
-__host__ __device__ inline uint32_t pair_qimg_keys(uint32_t qe) { return qe == 1u ? 64u : 128u; }
-__host__ __device__ inline PairLds pair_lds_layout(uint32_t qe, uint32_t re, uint32_t ht_words, uint32_t ov_words) {
-    PairLds l;
-    l.cand_id_off = 0;
-    l.cand_d_off = 128u * re;
-    uint32_t off = 256u * re;
-    if (re == 1u) {
-        // one pass per hop: the scatter buffer of the merge takes the candidates' place -- they are in registers by then
-        l.stage_off = 0;
-        off = 256u * qe > off ? 256u * qe : off;
-    } else {
-        // two passes per hop: the second pass's candidates are still in their buffer when the first pass is merged
-        l.stage_off = off;
-        off += 256u * qe;
-    }
-    l.qimg_off = off;  // the entries beyond the queue stay "empty" = larger than every distance
-    off += 4u * pair_qimg_keys(qe);
-    l.qpiv_off = off;  // one queue entry per lane: the last key of each eighth of the queue image (first level of the
-    off += 32u;        // lower-bound search); 32 bytes
-    l.sd_off = off;
-    off += 128u;
-    l.sink_off = off;  // one dword per lane (stores of many lanes to ONE address serialise like a bank conflict); the
-    off += 128u;       // 8-byte stores of the merge's scatter sink into [sd, sink + 128): the survivors' keys are dead by then
-    l.ht_off = off;
-    l.ov_off = l.ht_off + ht_words * 4u;  // the overflow table of the 16-bit table (ov_insert; 0 words: none)
-    l.half_bytes = l.ov_off + ov_words * 4u;
-    return l;
-}
-// the instantiation a launch takes: queue entries per lane = ceil((L + start points) / 32) (1 .. 3), two adjacency ids per
-// lane beyond degree 32 (which comes with at least two queue entries per lane: five instantiations per metric, not six)
-__host__ __device__ inline uint32_t pair_re(const SearchArgs& a) { return a.ix.max_degree > kPairHalf ? 2u : 1u; }
-__host__ __device__ inline uint32_t pair_qe(const SearchArgs& a) {
-    const uint32_t q = (a.l_value + a.ix.nstart + kPairHalf - 1u) / kPairHalf;
-    return (q < 2u && pair_re(a) == 2u) ? 2u : (q ? q : 1u);
-}
-
 __device__ __forceinline__ uint32_t rl_u32(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
 
 // Insert into the open 16-bit table, written without a per-lane branch: the hop is bound by instruction issue (every
@@ -588,14 +543,6 @@ __global__ __launch_bounds__(kWave) void pair_search_kernel(SearchArgs a) {
             if (stv && a.fail_flag) __hip_atomic_store(a.fail_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
-}
-
-// what the pair kernel serves (host side; the table geometry is checked by the caller)
-inline bool pair_shape(const SearchArgs& a) {
-    const int dt = a.ix.dtype;
-    return plain_mode(a) && !a.team && !a.grid && !a.srv.ring && !a.rec_ids && !a.range_ids && !a.qslots && a.out_ids &&
-           (dt == DT_U8 || dt == DT_I8 || dt == DT_SQ8) && a.ix.dim == 128u && a.l_value + a.ix.nstart <= 3u * kPairHalf &&
-           a.ix.max_degree <= 2u * kPairHalf && a.ix.nstart >= 1u && a.ix.nstart <= kPairHalf && a.ix.row_stride % 16u == 0u;
 }
 
 template <int DT>

@@ -30,26 +30,6 @@
 namespace dann {
 namespace {
 
-constexpr uint32_t kPqLutChunks = 64;  // chunks the register-resident table covers at most (4 registers each)
-// groups of 16 chunks = code-row dwordx4 loads = 64 table registers: the instantiation a chunk count takes
-__host__ __device__ inline uint32_t pq_lut_groups(uint32_t chunks) { return (chunks + 15u) / 16u; }
-
-// LDS of one query: the queue image ((id, distance) pairs: the merge scatters the register-resident queue here and
-// reloads it), two 64-word buffers of the merge's slow path, the visited table
-struct PqLds {
-    uint32_t stage_off, cbi_off, cbd_off, ht_off, total;
-};
-// (ov_words: the overflow table of the 16-bit table directly behind it -- ov_insert, search_pair_impl.h)
-__host__ __device__ inline PqLds pq_lds_layout(uint32_t qs, uint32_t ht_words, uint32_t ov_words) {
-    PqLds l;
-    l.stage_off = 0;
-    l.cbi_off = qs * 64u * 8u;
-    l.cbd_off = l.cbi_off + 256u;
-    l.ht_off = l.cbd_off + 256u;
-    l.total = l.ht_off + (ht_words + ov_words) * 4u;
-    return l;
-}
-
 // one table entry: populate_chunk_distances_impl (fixed_chunk_pq_table.rs:152-192) -- the arithmetic of the LDS form
 // (simd_op_seq: the reference's f32 kernel, four accumulators of eight lanes, then (a0 + a1) + (a2 + a3) and the sum
 // tree).  Chunks of exactly eight elements -- 128 dimensions in 16 chunks -- are one block of accumulator 0: the other
@@ -602,24 +582,6 @@ __global__ __launch_bounds__(kWave) DANN_PQ_KERNEL_ATTR(2) void pq_search_kernel
 template <int OP, int QS, bool PACK>
 __global__ __launch_bounds__(kWave) DANN_PQ_KERNEL_ATTR(1) void pq_search_kernel_g4(SearchArgs a) {
     pq_search_body<OP, QS, PACK, 4>(a);
-}
-
-// what the kernel serves (host side; the table geometry is checked by the caller)
-inline bool pq_lut_shape(const SearchArgs& a) {
-    return a.ix.dtype == DT_PQ && plain_mode(a) && !a.team && !a.grid && !a.srv.ring && !a.rec_ids && !a.range_ids &&
-           !a.qslots && a.out_ids && a.ix.pq_chunks <= kPqLutChunks && a.ix.row_stride % 16u == 0u &&
-           a.ix.row_stride >= 16u * pq_lut_groups(a.ix.pq_chunks) &&
-           std::max(a.l_value + a.ix.nstart, a.qcap_max) <= 4u * (uint32_t)kWave && a.ix.nstart >= 1u &&
-           (a.ix.metric == M_L2 || a.ix.metric == M_IP);
-}
-inline uint32_t pq_lut_qs(const SearchArgs& a) {
-    const uint32_t q = a.l_value + a.ix.nstart;
-    return q <= 64u ? 1u : q <= 128u ? 2u : 4u;
-}
-// queries per CU the registers of a table size allow
-inline uint32_t pq_lut_waves_per_cu(uint32_t chunks) {
-    const uint32_t g = pq_lut_groups(chunks);
-    return g <= 1u ? 16u : g <= 3u ? 8u : 4u;
 }
 
 template <int NG>
