@@ -7,28 +7,14 @@ import pytest
 
 import oracle
 from helpers import bits, random_graph, small_calls_from_threads
+from search_builders import orc_sq8_compress as _orc_compress, sq_setup
 
 pytestmark = pytest.mark.gpu
 da = pytest.importorskip("diskann_amd")
 
 
-def _orc_compress(x, shift, scale):
-    L = oracle.lib()
-    out = np.zeros((x.shape[0], x.shape[1] + 4), np.uint8)
-    for i in range(x.shape[0]):
-        c = np.zeros(1, np.float32)
-        L.orc_sq8_compress(x[i].ctypes.data, x.shape[1], shift.ctypes.data, C.c_float(scale),
-                           out[i].ctypes.data, c.ctypes.data)
-        out[i, x.shape[1]:] = c.view(np.uint8)
-    return out
-
-
 def _sq_setup(rng, n, dim):
-    data = rng.normal(0.3, 0.5, (n, dim)).astype(np.float32)
-    # ScalarQuantizer parameters as train.rs would produce them: shift = mean - 2 std, scale = 4 std
-    shift = (data.mean(0) - 2.0 * data.std(0)).astype(np.float32)
-    scale = float(np.float32(4.0 * data.std()))
-    return data, shift, scale
+    return sq_setup(rng, n, dim)[:3]
 
 
 def test_sq8_compress_matches_oracle():

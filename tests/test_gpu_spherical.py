@@ -11,8 +11,9 @@ import oracle
 import spherical_model as m
 from consolidate_model import consolidate
 from diverse_model import diverse_search
-from helpers import bits as fbits, random_graph
+from helpers import bits as fbits
 from inplace_delete_model import TIE_RUST, inplace_delete
+from search_builders import SphModelCase as ModelCase, SphTwin as Twin
 
 pytestmark = pytest.mark.gpu
 da = pytest.importorskip("diskann_amd")
@@ -162,25 +163,6 @@ KNN_CASES = ([(1, lay, metric) for lay in LAYOUTS[1] for metric in METRICS] +
              [(b, lay, m.L2) for b in (2, 4) for lay in LAYOUTS[b]] + [(2, m.SCALAR_QUANTIZED, m.IP), (4, m.SAME_AS_DATA, m.IP)])
 
 
-class ModelCase:
-    """realistic rows (the model's compressor) under a random graph, the GPU provider over them"""
-
-    def __init__(self, bits, metric, n, dim, R, seed, tags=False):
-        rng = np.random.default_rng(seed)
-        self.bits, self.metric, self.n, self.dim, self.R, self.rng = bits, metric, n, dim, R, rng
-        self.data = rng.normal(0.2, 1.0, (n, dim)).astype(np.float32)
-        self.qz = m.Quantizer(self.data, bits, metric)
-        self.rows = self.qz.rows(self.data)
-        self.start = self.qz.rows(self.data.mean(0, keepdims=True))
-        self.adj = random_graph(rng, n, R)
-        stride = da.lib().dann_inmem2_row_stride(DT[bits], dim) if tags else 0
-        self.gix = da.Provider(DT[bits], metric, dim, n, R, self.start, sq_shift_norm_sq=self.qz.ssn, row_stride=stride,
-                               inline_tags=tags)
-        self.gix.set_elements(0, self.rows)
-        self.gix.upload_graph(self.adj)
-        self.all_rows = np.concatenate([self.rows, self.start])
-
-
 def _check_knn(c, layout, nq, tags=None):
     q = c.qz.queries(c.rng.normal(0.2, 1.0, (nq, c.dim)).astype(np.float32), layout)
     c.gix.set_query_layout(layout)
@@ -227,28 +209,6 @@ def test_knn_search_with_unpublished_slots():
 
 
 # ---- 3. the oracle's U8 L2 twin over flat rows --------------------------------------------------------------------------
-class Twin:
-    def __init__(self, bits, dim, n, R, seed, adj=True, maxdeg=None):
-        rng = np.random.default_rng(seed)
-        self.bits, self.dim, self.n, self.R, self.rng = bits, dim, n, R, rng
-        self.codes = rng.integers(0, 1 << bits, (n, dim), dtype=np.uint8)
-        self.rows = m.flat_rows(self.codes, bits)
-        scodes = rng.integers(0, 1 << bits, (1, dim), dtype=np.uint8)
-        self.adj = random_graph(rng, n, R) if adj else None
-        md = maxdeg or R
-        self.oix = oracle.Index(oracle.U8, oracle.L2, dim, n, md, scodes)
-        self.oix.set_rows(0, self.codes)
-        self.gix = da.Provider(DT[bits], da.L2, dim, n, md, m.flat_rows(scodes, bits))
-        self.gix.set_elements(0, self.rows)
-        if adj:
-            self.oix.adj[:] = self.adj
-            self.gix.upload_graph(self.adj)
-
-    def queries(self, nq):
-        qc = self.rng.integers(0, 1 << self.bits, (nq, self.dim), dtype=np.uint8)
-        return m.flat_rows(qc, self.bits), qc
-
-
 TWINS = [(1, 128), (1, 100), (2, 64), (4, 32)]
 
 

@@ -10,8 +10,9 @@ import oracle
 import sq_bits_model as m
 from consolidate_model import consolidate
 from diverse_model import diverse_search
-from helpers import bits as fbits, random_graph, small_calls_from_threads
+from helpers import bits as fbits, small_calls_from_threads
 from inplace_delete_model import TIE_RUST, inplace_delete
+from search_builders import SqBitsCase as Case, sq_setup as _setup
 
 pytestmark = pytest.mark.gpu
 da = pytest.importorskip("diskann_amd")
@@ -22,14 +23,6 @@ METRICS = (oracle.L2, oracle.INNER_PRODUCT, oracle.COSINE_NORMALIZED)
 # 4-lane group 128 dimensions; a dword holds 8 (SQ4) / 32 (SQ1) codes, a byte 2 / 8
 DIMS = {4: (1, 2, 3, 7, 8, 9, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257),
         1: (1, 7, 8, 9, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1023, 1024, 1025)}
-
-
-def _setup(rng, n, dim):
-    data = rng.normal(0.3, 0.5, (n, dim)).astype(np.float32)
-    shift = (data.mean(0) - 2.0 * data.std(0)).astype(np.float32)
-    scale = float(np.float32(4.0 * data.std()))
-    snorm = float(np.float32((shift ** 2).sum(dtype=np.float32)))
-    return data, shift, scale, snorm
 
 
 # ---- compression --------------------------------------------------------------------------------------------------------
@@ -111,34 +104,6 @@ def test_distances_match_model(bits, variant):
 
 
 # ---- a shared index per bit width: compressed rows, the GPU provider and the oracle's twin -----------------------------------
-class Case:
-    def __init__(self, bits, metric, n, dim, R, seed, adj=True, maxdeg=None, tags=False):
-        rng = np.random.default_rng(seed)
-        self.bits, self.metric, self.n, self.dim, self.R = bits, metric, n, dim, R
-        data, self.shift, scale, self.snorm = _setup(rng, n, dim)
-        self.data = data
-        self.scale, self.scale8 = m.matched_scale8(bits, scale)
-        self.rows = da.sq_compress(data, self.shift, self.scale, bits)
-        self.start = da.sq_compress(data.mean(0, keepdims=True).astype(np.float32), self.shift, self.scale, bits)
-        self.adj = random_graph(rng, n, R) if adj else None
-        md = maxdeg or R
-        self.oix = m.oracle_twin(metric, dim, n, md, bits, self.rows, self.start, self.scale8, self.snorm, self.adj)
-        # tags: the Store layout on the GPU side (stride of the reference, a tag byte after the payload); every slot is
-        # published, so the twin without tags returns the same results
-        stride = da.lib().dann_inmem2_row_stride(DT[bits], dim) if tags else 0
-        self.gix = da.Provider(DT[bits], metric, dim, n, md, self.start, sq_scale=self.scale, sq_shift_norm_sq=self.snorm,
-                               row_stride=stride, inline_tags=tags)
-        self.gix.set_elements(0, self.rows)
-        if adj:
-            self.gix.upload_graph(self.adj)
-        self.rng = rng
-
-    def queries(self, nq):
-        qf = self.rng.normal(0.3, 0.5, (nq, self.dim)).astype(np.float32)
-        q = da.sq_compress(qf, self.shift, self.scale, self.bits)
-        return qf, q, m.twin_rows(q, self.bits, self.dim)
-
-
 @pytest.fixture(scope="module")
 def sq4_l2():
     return Case(4, oracle.L2, 3000, 128, 24, 41)
