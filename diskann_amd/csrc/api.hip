@@ -37,10 +37,26 @@ static uint32_t elem_size(int32_t dtype) { return dtype == DT_F32 ? 4u : dtype =
 static uint32_t layer_bytes_of(int32_t dtype, uint32_t dim) {
     if (dt_is_sq(dtype)) return sq_code_bytes(dtype, dim) + 4u;  // code bytes + the f32 compensation
     if (dt_is_sph(dtype)) return sq_code_bytes(dtype, dim) + kSphDataMeta;  // code bytes + DataMeta
+    if (dt_is_mm(dtype)) return kMmHeader + sq_code_bytes(dtype, dim);     // MinMaxCompensation + code bytes
     return dim * elem_size(dtype);
 }
 static bool valid_dtype(int32_t d) {
-    return (d >= 0 && d <= 5) || d == DT_SQ1 || d == DT_SQ4 || d == DT_SPH1 || d == DT_SPH2 || d == DT_SPH4;
+    return (d >= 0 && d <= 5) || d == DT_SQ1 || d == DT_SQ4 || d == DT_SPH1 || d == DT_SPH2 || d == DT_SPH4 ||
+           dt_is_mm(d);
+}
+// MinMax rows written through host pointers: the image's leading u32 is the quantiser's output_dim() and must be the
+// index's dim (minmax::Data::from_raw panics on a mismatch).  Device-pointer and verbatim paths do not look.
+static bool mm_headers_ok(const dann_index* idx, const void* rows, uint64_t n, uint64_t stride) {
+    if (!dt_is_mm(idx->cfg.dtype)) return true;
+    for (uint64_t i = 0; i < n; ++i) {
+        uint32_t d;
+        memcpy(&d, static_cast<const uint8_t*>(rows) + i * stride, 4);
+        if (d != idx->cfg.dim) {
+            set_error("MinMax image %llu: header dim %u does not match the index's dim %u", (unsigned long long)i, d, idx->cfg.dim);
+            return false;
+        }
+    }
+    return true;
 }
 static bool valid_metric(int32_t m) { return m >= 0 && m <= 3; }
 
@@ -286,6 +302,7 @@ dann::IndexView dann_index::view() const {
     v.pq_pack_codes = pq_pack_codes;
     v.tag_off = cfg.inline_tags ? layer_bytes : 0u;
     if (dt_is_sph(cfg.dtype)) v.sq_k = 0.0f;  // (no scale; non-zero marks a QueryMeta, see qview and SqParams)
+    if (dt_is_mm(cfg.dtype)) v.sq_k = v.sq_shift_norm_sq = 0.0f;  // (every row carries its own scale and offset)
     return v;
 }
 
@@ -360,6 +377,13 @@ int32_t dann_index_create(const dann_config* cfg, const void* start_rows, uint64
             return DANN_EINVAL;
         }
     }
+    if (dt_is_mm(cfg->dtype)) {  // the inner product of two rows' codes is a u32 (minmax/vectors.rs:206-229)
+        const uint64_t top = (1u << sq_bits(cfg->dtype)) - 1u;
+        if ((uint64_t)cfg->dim * top * top > 0xFFFFFFFFull) {
+            set_error("dim %u: the inner product of two %d-bit MinMax rows does not fit a u32", cfg->dim, sq_bits(cfg->dtype));
+            return DANN_EINVAL;
+        }
+    }
     const uint32_t lb = cfg->dtype == DT_PQ ? cfg->pq_chunks : layer_bytes_of(cfg->dtype, cfg->dim);
     {
         int op;
@@ -386,6 +410,10 @@ int32_t dann_index_create(const dann_config* cfg, const void* start_rows, uint64
     if (!idx) return DANN_ENOMEM;
     idx->cfg = *cfg;
     idx->layer_bytes = lb;
+    if (!mm_headers_ok(idx, start_rows, cfg->num_start_points, lb)) {
+        delete idx;
+        return DANN_EINVAL;
+    }
     for (auto& d : idx->dbg) d.store(__builtin_nan(""), std::memory_order_relaxed);
     if (idx->cfg.row_stride == 0) idx->cfg.row_stride = (lb + 15u) & ~15u;
     if (idx->cfg.row_stride < lb || (idx->cfg.row_stride & 15u)) {
@@ -505,6 +533,7 @@ int32_t dann_set_elements(dann_index* idx, uint32_t first_slot, uint32_t n, cons
                   idx->cfg.capacity);
         return DANN_EBOUNDS;
     }
+    if (!mm_headers_ok(idx, rows, n, idx->layer_bytes)) return DANN_EINVAL;
     DANN_HIP(hipMemcpy2DAsync(idx->d_rows + (size_t)first_slot * idx->cfg.row_stride, idx->cfg.row_stride, rows,
                               idx->layer_bytes, idx->layer_bytes, n, hipMemcpyHostToDevice, idx->main.stream));
     if (idx->cfg.inline_tags) {  // Slot::publish (store.rs:776-782)
@@ -658,6 +687,10 @@ int32_t dann_set_pq_table(dann_index* idx, const float* pivots, const uint32_t* 
 // ---- query layout of spherical indexes (iface::QueryLayout) ---------------------------------------------------------
 int32_t dann_set_query_layout(dann_index* idx, int32_t layout) try {
     CHECK_IDX(idx);
+    if (layout == QL_EIGHT_BIT) {  // MinMaxQuery::EightBit (an MM8 image against narrower MinMax rows): not served
+        set_error("query layout %d is not supported for dtype %d", layout, idx->cfg.dtype);
+        return DANN_EUNSUPPORTED;
+    }
     if (layout < QL_SAME || layout > QL_FULL) {
         set_error("dann_set_query_layout: unknown layout %d", layout);
         return DANN_EINVAL;
@@ -897,6 +930,7 @@ int32_t dann_query_create(const dann_index* idx, const void* query, uint64_t len
         set_error("query of %llu bytes does not match the layer's %u bytes", (unsigned long long)len, want);
         return DANN_ELENGTH;
     }
+    if (!mm_headers_ok(idx, query, 1, len)) return DANN_EINVAL;
     dann_query* q = new (std::nothrow) dann_query();
     if (!q) return DANN_ENOMEM;
     q->idx = idx;
@@ -1679,7 +1713,7 @@ int32_t dann_save_vectors_bin(const dann_index* idx, const char* path, uint32_t 
         return DANN_EINVAL;
     }
     // `.bin`: dim counts elements of the stored type (scalar-quantised rows are written as their payload bytes)
-    const uint32_t dim = dt_is_sq(idx->cfg.dtype) || dt_is_sph(idx->cfg.dtype) ? idx->layer_bytes : idx->cfg.dim;
+    const uint32_t dim = dt_is_sq(idx->cfg.dtype) || dt_is_sph(idx->cfg.dtype) || dt_is_mm(idx->cfg.dtype) ? idx->layer_bytes : idx->cfg.dim;
     if (fwrite(&n, 4, 1, out.f) != 1 || fwrite(&dim, 4, 1, out.f) != 1 ||
         (rows.size() && fwrite(rows.data(), 1, rows.size(), out.f) != rows.size())) {
         set_error("short write to %s", path);
@@ -1700,7 +1734,7 @@ int32_t dann_load_vectors_bin(dann_index* idx, const char* path, uint32_t first_
     }
     uint32_t n = 0, dim = 0;
     if (fread(&n, 4, 1, in.f) != 1 || fread(&dim, 4, 1, in.f) != 1) return DANN_ELENGTH;
-    const uint32_t want_dim = dt_is_sq(idx->cfg.dtype) || dt_is_sph(idx->cfg.dtype) ? idx->layer_bytes : idx->cfg.dim;
+    const uint32_t want_dim = dt_is_sq(idx->cfg.dtype) || dt_is_sph(idx->cfg.dtype) || dt_is_mm(idx->cfg.dtype) ? idx->layer_bytes : idx->cfg.dim;
     if (dim != want_dim) {
         set_error("data of dimension %u does not match full precision layer's dimension %u", dim, want_dim);
         return DANN_ELENGTH;

@@ -25,9 +25,11 @@
 
 namespace dann {
 
-__host__ __device__ constexpr int sq_bits(int dt) { return dt == DT_SQ8 ? 8 : dt_is_sph(dt) ? (dt & 7) : dt - 16; }
+__host__ __device__ constexpr int sq_bits(int dt) {
+    return dt == DT_SQ8 ? 8 : dt_is_sph(dt) ? (dt & 7) : dt_is_mm(dt) ? dt - 48 : dt - 16;
+}
 // query layouts of spherical rows (iface::QueryLayout; dann.h DANN_QUERY_*)
-enum : int { QL_SAME = 0, QL_TRANSPOSED = 1, QL_SCALAR = 2, QL_FULL = 3 };
+enum : int { QL_SAME = 0, QL_TRANSPOSED = 1, QL_SCALAR = 2, QL_FULL = 3, QL_EIGHT_BIT = 8 };
 constexpr uint32_t kSphDataMeta = 6u, kSphQueryMeta = 16u;  // bytes of DataMeta / QueryMeta
 // code bytes of a scalar- or spherically quantised row: ceil(dim * bits / 8); the f32 compensation resp. the DataMeta
 // follows them
@@ -998,6 +1000,140 @@ __device__ __forceinline__ void group_ip_sph_pre(const uint4& x, const uint8_t* 
     }
 }
 
+// ---- MinMax-quantised rows (minmax::Data<NBITS>, diskann-quantization/src/minmax/vectors.rs), front-canonical: the
+// 20-byte MinMaxCompensation (u32 dim, f32 b, n, a, norm_squared), then the Dense code bytes of the packed rows above
+// (MM8: one byte per code).  Every metric needs the raw inner product of the codes only (the epilogue is
+// finish_minmax), an exact u32 sum, so any lane assignment is bit-identical.  `x` and the rows are image pointers; the
+// codes start at byte 20 of an image:
+//   global rows (strides are multiples of 16): 4-byte aligned.  The loads say so (mm_load copies from a pointer of
+//     stated alignment, never through a uint4*), and the compiler may emit one wide load or dword loads for them;
+//   a query staged in LDS sits at slot + 12 (launch_shape.h), its codes 16-byte aligned: XA = the lane's load width.
+// Lane shapes: MM8 the u8 path's 8 lanes x 16 bytes (v_dot4_u32_u8), MM4 / MM2 / MM1 PackedShape's 4 lanes x 16 / 8 / 4
+// bytes.  Steps that lie wholly below dim * bits use the wide loads; the one tail step reads dword by dword, each dword
+// only where it starts below the code-byte count (else the row's first code dword, whose product is masked away), so no
+// load ends beyond the image rounded up to 4 bytes -- inside the row's stride, the 16-byte rounded query buffers and the
+// LDS slot.  x's bits at or beyond dim * bits are masked in the tail; a zero in one operand removes the product.
+template <int BITS>
+struct MmShape {
+    static constexpr int NW = BITS >= 4 ? 4 : BITS == 2 ? 2 : 1;  // dwords per lane per step
+    static constexpr int LB = 4 * NW, G = BITS == 8 ? 8 : 4, STEP = G * LB;
+};
+template <int NW, int ALIGN>
+__device__ __forceinline__ PWords<NW> mm_load(const uint8_t* p) {
+    PWords<NW> r;
+    __builtin_memcpy(r.w, __builtin_assume_aligned(p, ALIGN), 4 * NW);
+    return r;
+}
+template <int NW>
+__device__ __forceinline__ PWords<NW> mm_load_tail(const uint8_t* codes, int o, int cb) {
+    PWords<NW> r;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        const int oi = o + 4 * i;
+        r.w[i] = *reinterpret_cast<const uint32_t*>(codes + (oi < cb ? oi : 0));
+    }
+    return r;
+}
+template <int BITS>
+__device__ __forceinline__ uint32_t mm_dot(uint32_t x, uint32_t y, uint32_t acc) {
+    if constexpr (BITS == 8) return __builtin_amdgcn_udot4(x, y, acc, false);
+    else if constexpr (BITS == 1) return acc + (uint32_t)__builtin_popcount(x & y);
+    else return packed_dot<BITS>(x, y, acc);
+}
+template <int BITS>
+__device__ __forceinline__ float mm_group_sum(uint32_t t) {  // (u32 -> f32 rounds to nearest even, as `raw as f32`)
+    if constexpr (BITS == 8) return (float)(uint32_t)group8_sum((int)t);  // valid in lane v == 0
+    else return (float)group4_sum(t);
+}
+template <int BITS, int U, int XA>
+__device__ __forceinline__ void group_ip_mm(const uint8_t* __restrict__ x, const uint8_t* const (&rows)[U], int dim, int v,
+                                            float (&out)[U]) {
+    using P = MmShape<BITS>;
+    constexpr int NW = P::NW;
+    const int total_bits = dim * BITS, cb = (total_bits + 7) >> 3;
+    const uint8_t* xc = x + kMmHeader;
+    uint32_t t[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) t[u] = 0u;
+    int o0 = 0;
+    for (; 8 * (o0 + P::STEP) <= total_bits; o0 += P::STEP) {
+        const int o = o0 + P::LB * v;
+        PWords<NW> y[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) y[u] = mm_load<NW, 4>(rows[u] + kMmHeader + o);
+        const PWords<NW> xw = mm_load<NW, XA>(xc + o);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+            for (int i = 0; i < NW; ++i) t[u] = mm_dot<BITS>(xw.w[i], y[u].w[i], t[u]);
+        }
+    }
+    if (8 * o0 < total_bits) {
+        const int o = o0 + P::LB * v;
+        const bool in = o < cb;
+        const int ol = in ? o : 0;  // clamped: every request is issued, none behind a branch
+        const int valid = in ? total_bits - 8 * o : 0;
+        PWords<NW> y[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) y[u] = mm_load_tail<NW>(rows[u] + kMmHeader, ol, cb);
+        PWords<NW> xw = mm_load_tail<NW>(xc, ol, cb);
+        packed_mask<NW>(xw, valid);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+            for (int i = 0; i < NW; ++i) t[u] = mm_dot<BITS>(xw.w[i], y[u].w[i], t[u]);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) out[u] = mm_group_sum<BITS>(t[u]);
+}
+template <int BITS, int XA>
+__device__ __forceinline__ float group_ip_mm1(const uint8_t* x, const uint8_t* row, int dim, int v) {
+    const uint8_t* const rows[1] = {row};
+    float out[1];
+    group_ip_mm<BITS, 1, XA>(x, rows, dim, v, out);
+    return out[0];
+}
+// Fixed 128 dimensions -- exactly one full step (128 / 64 / 32 / 16 code bytes), nothing to mask and no load beyond the
+// image.  The lane's query words stay in registers (2 bit: widened to nibbles once, as sph_query_pre); `qs` is the
+// staged image.
+template <int BITS>
+__device__ __forceinline__ uint4 mm_query_pre(const uint8_t* qs, int v) {
+    const uint8_t* c = qs + kMmHeader + MmShape<BITS>::LB * v;
+    if constexpr (BITS >= 4) {
+        const PWords<4> t = mm_load<4, 16>(c);
+        return uint4{t.w[0], t.w[1], t.w[2], t.w[3]};
+    } else if constexpr (BITS == 2) {
+        const PWords<2> t = mm_load<2, 8>(c);
+        return uint4{t.w[0] & kEven2, (t.w[0] >> 2) & kEven2, t.w[1] & kEven2, (t.w[1] >> 2) & kEven2};
+    } else {
+        return uint4{mm_load<1, 4>(c).w[0], 0u, 0u, 0u};
+    }
+}
+template <int BITS, int U>
+__device__ __forceinline__ void group_ip_mm_pre(const uint4& x, const uint8_t* const (&rows)[U], int v, float (&out)[U]) {
+    constexpr int NW = MmShape<BITS>::NW;
+    PWords<NW> y[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) y[u] = mm_load<NW, 4>(rows[u] + kMmHeader + MmShape<BITS>::LB * v);
+    const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        uint32_t t = 0u;
+        if constexpr (BITS == 2) {
+#pragma unroll
+            for (int i = 0; i < NW; ++i) {
+                t = __builtin_amdgcn_udot8(xs[2 * i], y[u].w[i] & kEven2, t, false);
+                t = __builtin_amdgcn_udot8(xs[2 * i + 1], (y[u].w[i] >> 2) & kEven2, t, false);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NW; ++i) t = mm_dot<BITS>(xs[i], y[u].w[i], t);
+        }
+        out[u] = mm_group_sum<BITS>(t);
+    }
+}
+
 // ---- dtype dispatch ------------------------------------------------------------------
 // Query-side staging type and group width for the *search* path
 // (Full<T>::query_distance, diskann-inmem/src/layers/full.rs:351-504):
@@ -1008,7 +1144,7 @@ __device__ __forceinline__ void group_ip_sph_pre(const uint4& x, const uint8_t* 
 //   f16 x f16: L2/IP/cosine all Strategy2x4 (NACC 2)  (simd.rs:989,1752,2591)
 template <int DT, int OP, bool PAIR>
 struct Scheme {
-    static constexpr bool kInt = (DT == DT_U8 || DT == DT_I8 || DT == DT_PQ || dt_is_sq(DT) || dt_is_sph(DT));
+    static constexpr bool kInt = (DT == DT_U8 || DT == DT_I8 || DT == DT_PQ || dt_is_sq(DT) || dt_is_sph(DT) || dt_is_mm(DT));
     static constexpr int NACC = (OP == OP_COS) ? 2 : ((DT == DT_F16 && PAIR) ? 2 : 4);
     static constexpr int G = dt_is_packed(DT) ? 4 : kInt ? 8 : 2 * NACC;  // (packed rows: PackedShape::G)
     // search-path gather: 2-byte rows use the wide layout (one lane per accumulator)
@@ -1061,6 +1197,22 @@ struct RowType<DT_SPH1T> {
     using type = uint8_t;
 };
 template <>
+struct RowType<DT_MM1> {
+    using type = uint8_t;
+};
+template <>
+struct RowType<DT_MM2> {
+    using type = uint8_t;
+};
+template <>
+struct RowType<DT_MM4> {
+    using type = uint8_t;
+};
+template <>
+struct RowType<DT_MM8> {
+    using type = uint8_t;
+};
+template <>
 struct RowType<DT_PQ> {
     using type = uint8_t;
 };
@@ -1068,7 +1220,9 @@ struct RowType<DT_PQ> {
 // `q` is the staged query: f32 for float rows, raw bytes for integer rows.
 template <int DT, int OP, bool PAIR, int DIM, typename QT>
 __device__ __forceinline__ float group_distance(const QT* q, const uint8_t* row, int dim, int v) {
-    if constexpr (dt_is_sph(DT)) {
+    if constexpr (dt_is_mm(DT)) {  // (q: the image staged at slot + 12, codes 16-byte aligned)
+        return group_ip_mm1<sq_bits(DT), MmShape<sq_bits(DT)>::LB>(reinterpret_cast<const uint8_t*>(q), row, dim, v);
+    } else if constexpr (dt_is_sph(DT)) {
         return group_ip_sph1<DT>(reinterpret_cast<const uint8_t*>(q), row, dim, v);
     } else if constexpr (dt_is_packed(DT)) {
         return group_distance_packed1<sq_bits(DT), OP>(reinterpret_cast<const uint8_t*>(q), row, dim, v);
@@ -1084,7 +1238,9 @@ __device__ __forceinline__ float group_distance(const QT* q, const uint8_t* row,
 // stored row x stored row with the prune-path association (Scheme<DT, OP, true>)
 template <int DT, int OP>
 __device__ __forceinline__ float group_distance_rows(const uint8_t* x, const uint8_t* y, int dim, int v) {
-    if constexpr (dt_is_sph(DT)) {  // (a stored row as the query is always the symmetric form)
+    if constexpr (dt_is_mm(DT)) {  // (both operands are rows in global memory: 4-byte aligned codes)
+        return group_ip_mm1<sq_bits(DT), 4>(x, y, dim, v);
+    } else if constexpr (dt_is_sph(DT)) {  // (a stored row as the query is always the symmetric form)
         static_assert(DT != DT_SPH1T, "row x row distances have no query layout");
         return group_ip_sph1<DT>(x, y, dim, v);
     } else if constexpr (dt_is_packed(DT)) {
@@ -1104,7 +1260,9 @@ __device__ __forceinline__ float group_distance_rows(const uint8_t* x, const uin
 template <int DT, int OP, bool PAIR, int U, bool WIDE = true, typename QT>
 __device__ __forceinline__ void group_distance_many(const QT* q, const uint8_t* const (&rows)[U],
                                                     const bool (&active)[U], int dim, int v, float (&out)[U]) {
-    if constexpr (dt_is_sph(DT)) {
+    if constexpr (dt_is_mm(DT)) {
+        group_ip_mm<sq_bits(DT), U, MmShape<sq_bits(DT)>::LB>(reinterpret_cast<const uint8_t*>(q), rows, dim, v, out);
+    } else if constexpr (dt_is_sph(DT)) {
         group_ip_sph<DT, U>(reinterpret_cast<const uint8_t*>(q), rows, dim, v, out);
     } else if constexpr (dt_is_packed(DT)) {
         group_distance_packed<sq_bits(DT), OP, U>(reinterpret_cast<const uint8_t*>(q), rows, dim, v, out);
@@ -1218,6 +1376,24 @@ __device__ __forceinline__ float finish_spherical(float ip, const uint8_t* x, co
     return OP == OP_IP ? -r : 1.0f - r;
 }
 
+// MinMax rows: the raw inner product of the codes -> SimilarityScore (minmax/vectors.rs: kernel :206-229, MinMaxL2Squared /
+// MinMaxIP / MinMaxCosine / MinMaxCosineNormalized :231-473), each f32 operation on its own and in the reference's
+// association.  NOT symmetric in its arguments: (t0 + x.n * y.b) + y.n * x.b rounds differently when x and y swap, so
+// `x` must be the reference's first argument (the query; in prunes the candidate under test) and `y` its second.  The
+// headers are 4-byte aligned (image starts are 16-byte aligned in global memory, slot + 12 in LDS).
+template <int OP, bool NORM>
+__device__ __forceinline__ float finish_minmax(float raw, const uint8_t* x, const uint8_t* y, uint32_t dim) {
+    const float* hx = reinterpret_cast<const float*>(x);
+    const float* hy = reinterpret_cast<const float*>(y);
+    const float xb = hx[1], xn = hx[2], xa = hx[3], xs = hx[4];
+    const float yb = hy[1], yn = hy[2], ya = hy[3], ys = hy[4];
+    const float t0 = (xa * ya) * raw;
+    const float vv = ((t0 + xn * yb) + yn * xb) + (xb * yb) * (float)dim;
+    if constexpr (OP == OP_L2) return (-2.0f * vv + xs) + ys;
+    else if constexpr (OP == OP_COS) return 1.0f - vv / (__builtin_sqrtf(xs) * __builtin_sqrtf(ys));  // no zero-norm guard
+    else return NORM ? 1.0f - vv : -vv;
+}
+
 // raw kernel result -> SimilarityScore.  Full-precision rows: PostOp; scalar-quantised rows: the compensated
 // epilogues of diskann-quantization/src/scalar/vectors.rs:216-245 (L2), :306-370 (IP),
 // :403-465 (CosineNormalized); `x`, `y` are the two rows (code bytes + trailing f32 compensation, which sits at
@@ -1225,7 +1401,9 @@ __device__ __forceinline__ float finish_spherical(float ip, const uint8_t* x, co
 template <int DT, int OP, bool NORM>
 __device__ __forceinline__ float finish_distance(float raw, const uint8_t* x, const uint8_t* y, uint32_t dim,
                                                  const SqParams& sq) {
-    if constexpr (dt_is_sph(DT)) {
+    if constexpr (dt_is_mm(DT)) {
+        return finish_minmax<OP, NORM>(raw, x, y, dim);
+    } else if constexpr (dt_is_sph(DT)) {
         return finish_spherical<DT, OP>(raw, x, y, dim, sq);
     } else if constexpr (!dt_is_sq(DT)) {
         return post_op<OP, NORM>(raw);

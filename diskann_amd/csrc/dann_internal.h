@@ -109,6 +109,10 @@ DANN_DECL_LAUNCH(sph1);
 DANN_DECL_LAUNCH(sph1t);
 DANN_DECL_LAUNCH(sph2);
 DANN_DECL_LAUNCH(sph4);
+DANN_DECL_LAUNCH(mm1);
+DANN_DECL_LAUNCH(mm2);
+DANN_DECL_LAUNCH(mm4);
+DANN_DECL_LAUNCH(mm8);
 DANN_DECL_LAUNCH(pq);
 // search_diverse.hip: dann_diverse_search_batch on device-resident queries and outputs (host-synchronous on `stream`)
 int32_t diverse_search_device(dann_index* idx, hipStream_t stream, const void* d_queries, uint32_t nq, uint32_t l_value,

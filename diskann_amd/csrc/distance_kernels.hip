@@ -29,7 +29,7 @@ __global__ __launch_bounds__(kWave) void expand_beam_kernel(IndexView ix, const 
     const uint64_t hi_all = offsets[qi + 1];
     if (lo >= hi_all) return;
     const uint64_t hi = lo + kChunk < hi_all ? lo + kChunk : hi_all;
-    QT* qs = reinterpret_cast<QT*>(smem);
+    QT* qs = reinterpret_cast<QT*>(smem + query_stage_off(DT));
     const SqParams sqp{ix.sq_k, ix.sq_shift_norm_sq};
     const uint8_t* qsrc = reinterpret_cast<const uint8_t*>(queries) + (uint64_t)qi * ix.qbytes;
     if constexpr (kInt) {
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(kWave) void rerank_kernel(IndexView ix, const void*
     uint64_t* keys = reinterpret_cast<uint64_t*>(smem);
     uint32_t* cid = reinterpret_cast<uint32_t*>(smem + (size_t)pcap * 8);
     float* cd = reinterpret_cast<float*>(smem + (size_t)pcap * 12);
-    QT* qs = reinterpret_cast<QT*>(smem + (size_t)pcap * 16);
+    QT* qs = reinterpret_cast<QT*>(smem + (size_t)pcap * 16 + query_stage_off(DT));
     const SqParams sqp{ix.sq_k, ix.sq_shift_norm_sq};
     const uint8_t* qsrc = reinterpret_cast<const uint8_t*>(queries) + (uint64_t)qi * ix.qbytes;
     if constexpr (kInt) {
@@ -178,7 +178,7 @@ int32_t launch_rerank_t(const IndexView& ix, const void* q, uint32_t nq, const u
     uint32_t pcap = 64;
     while (pcap < stride) pcap <<= 1;
     const bool is_int = Scheme<DT, OP, false>::kInt;
-    const size_t lds = (size_t)pcap * 16 + (((is_int ? ix.qbytes : ix.dim * 4u) + 15u) & ~15u);
+    const size_t lds = (size_t)pcap * 16 + (((is_int ? int_query_slot_bytes(DT, ix.qbytes) : ix.dim * 4u) + 15u) & ~15u);
     auto kern = rerank_kernel<DT, OP, NORM>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -204,7 +204,7 @@ int32_t launch_rerank_dt(const IndexView& ix, const void* q, uint32_t nq, const 
         return launch_rerank_t<DT, OP_L2, false>(ix, q, nq, cand, stride, k, oi, od, stream);
     }
     if (op == OP_IP) {
-        if constexpr (DT == DT_F32 || DT == DT_F16) {
+        if constexpr (DT == DT_F32 || DT == DT_F16 || dt_is_mm(DT)) {
             if (norm) return launch_rerank_t<DT, OP_IP, true>(ix, q, nq, cand, stride, k, oi, od, stream);
         }
         return launch_rerank_t<DT, OP_IP, false>(ix, q, nq, cand, stride, k, oi, od, stream);
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(256) void pair_kernel(const uint8_t* xbase, const u
     const uint8_t* x = xbase + (uint64_t)(a ? a[p] : p) * xstride;
     const uint8_t* y = ybase + (uint64_t)(b ? b[p] : p) * ystride;
     float d;
-    if constexpr (dt_is_packed(DT)) {
+    if constexpr (dt_is_packed(DT) || dt_is_mm(DT)) {
         d = group_distance_rows<DT, OP>(x, y, (int)dim, v);
     } else if constexpr (S::kInt) {
         d = group_distance_int<OP, DT == DT_I8>(x, y, (int)dim, v);
@@ -270,7 +270,7 @@ int32_t launch_pairs_dt(int32_t metric, const uint8_t* xb, const uint8_t* yb, ui
         return launch_pairs_t<DT, OP_L2, false>(xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
     }
     if (op == OP_IP) {
-        if constexpr (DT == DT_F32 || DT == DT_F16) {
+        if constexpr (DT == DT_F32 || DT == DT_F16 || dt_is_mm(DT)) {
             if (norm) return launch_pairs_t<DT, OP_IP, true>(xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
         }
         return launch_pairs_t<DT, OP_IP, false>(xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
@@ -294,6 +294,10 @@ int32_t launch_pairs_any(int32_t dtype, int32_t metric, const uint8_t* xb, const
         case DT_SPH1: return launch_pairs_dt<DT_SPH1>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
         case DT_SPH2: return launch_pairs_dt<DT_SPH2>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
         case DT_SPH4: return launch_pairs_dt<DT_SPH4>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
+        case DT_MM1: return launch_pairs_dt<DT_MM1>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
+        case DT_MM2: return launch_pairs_dt<DT_MM2>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
+        case DT_MM4: return launch_pairs_dt<DT_MM4>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
+        case DT_MM8: return launch_pairs_dt<DT_MM8>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
     }
     set_error("bad dtype %d", dtype);
     return DANN_EINVAL;
@@ -303,7 +307,7 @@ template <int DT, int OP, bool NORM, int DIM>
 int32_t launch_eb_t(const IndexView& ix, const void* q, uint32_t nq, uint32_t chunks, const uint32_t* ids,
                     const uint64_t* offsets, float* out, hipStream_t stream) {
     const bool is_int = Scheme<DT, OP, false>::kInt;
-    size_t lds = ((is_int ? ix.qbytes : ix.dim * 4u) + 15u) & ~15u;
+    size_t lds = ((is_int ? int_query_slot_bytes(DT, ix.qbytes) : ix.dim * 4u) + 15u) & ~15u;
     hipLaunchKernelGGL((expand_beam_kernel<DT, OP, NORM, DIM>), dim3(nq, chunks), dim3(kWave), lds, stream, ix, q, ids,
                        offsets, out);
     hipError_t e = hipGetLastError();
@@ -330,7 +334,7 @@ int32_t launch_eb_dt(const IndexView& ix, const void* q, uint32_t nq, uint32_t c
         return launch_eb_t<DT, OP_L2, false, 0>(ix, q, nq, chunks, ids, offsets, out, stream);
     }
     if (op == OP_IP) {
-        if constexpr (DT == DT_F32 || DT == DT_F16) {
+        if constexpr (DT == DT_F32 || DT == DT_F16 || dt_is_mm(DT)) {
             if (norm) return launch_eb_t<DT, OP_IP, true, 0>(ix, q, nq, chunks, ids, offsets, out, stream);
         }
         return launch_eb_t<DT, OP_IP, false, 0>(ix, q, nq, chunks, ids, offsets, out, stream);
@@ -362,6 +366,10 @@ int32_t launch_expand_beam(const IndexView& ix, const void* d_queries, uint32_t 
         case DT_SPH1T: return launch_eb_dt<DT_SPH1T>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
         case DT_SPH2: return launch_eb_dt<DT_SPH2>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
         case DT_SPH4: return launch_eb_dt<DT_SPH4>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
+        case DT_MM1: return launch_eb_dt<DT_MM1>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
+        case DT_MM2: return launch_eb_dt<DT_MM2>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
+        case DT_MM4: return launch_eb_dt<DT_MM4>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
+        case DT_MM8: return launch_eb_dt<DT_MM8>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
     }
     set_error("bad dtype %d", ix.dtype);
     return DANN_EINVAL;
@@ -386,6 +394,10 @@ int32_t launch_rerank(const IndexView& ix, const void* d_queries, uint32_t nq, c
         case DT_SPH1T: return launch_rerank_dt<DT_SPH1T>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
         case DT_SPH2: return launch_rerank_dt<DT_SPH2>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
         case DT_SPH4: return launch_rerank_dt<DT_SPH4>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
+        case DT_MM1: return launch_rerank_dt<DT_MM1>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
+        case DT_MM2: return launch_rerank_dt<DT_MM2>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
+        case DT_MM4: return launch_rerank_dt<DT_MM4>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
+        case DT_MM8: return launch_rerank_dt<DT_MM8>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
     }
     return DANN_EINVAL;
 }

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(kWave) void paged_kernel(PagedArgs a) {
     const uint32_t rc = (R + 63u) & ~63u;
     uint32_t* cand_id = reinterpret_cast<uint32_t*>(smem);
     float* cand_d = reinterpret_cast<float*>(smem + (size_t)rc * 4);
-    QT* qs = reinterpret_cast<QT*>(smem + (size_t)rc * 8);
+    QT* qs = reinterpret_cast<QT*>(smem + (size_t)rc * 8 + query_stage_off(DT));
     const SqParams sqp{ix.sq_k, ix.sq_shift_norm_sq};
     {
         const uint8_t* qsrc = reinterpret_cast<const uint8_t*>(a.queries) + (uint64_t)qi * ix.qbytes;
@@ -310,7 +310,7 @@ template <int DT, int OP, bool NORM>
 int32_t launch_paged_t(const PagedArgs& a, hipStream_t stream) {
     const bool is_int = Scheme<DT, OP, false>::kInt;
     const uint32_t rc = (a.ix.max_degree + 63u) & ~63u;
-    const size_t lds = (size_t)rc * 8 + (((is_int ? a.ix.qbytes : a.ix.dim * 4u) + 15u) & ~15u);
+    const size_t lds = (size_t)rc * 8 + (((is_int ? int_query_slot_bytes(DT, a.ix.qbytes) : a.ix.dim * 4u) + 15u) & ~15u);
     auto kern = paged_kernel<DT, OP, NORM>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -335,7 +335,7 @@ int32_t launch_paged_dt(const PagedArgs& a, hipStream_t stream) {
         return launch_paged_t<DT, OP_L2, false>(a, stream);
     }
     if (op == OP_IP) {
-        if constexpr (DT == DT_F32 || DT == DT_F16) {
+        if constexpr (DT == DT_F32 || DT == DT_F16 || dt_is_mm(DT)) {
             if (norm) return launch_paged_t<DT, OP_IP, true>(a, stream);
         }
         return launch_paged_t<DT, OP_IP, false>(a, stream);
@@ -357,6 +357,10 @@ int32_t launch_paged(const PagedArgs& a, hipStream_t stream) {
         case DT_SPH1T: return launch_paged_dt<DT_SPH1T>(a, stream);
         case DT_SPH2: return launch_paged_dt<DT_SPH2>(a, stream);
         case DT_SPH4: return launch_paged_dt<DT_SPH4>(a, stream);
+        case DT_MM1: return launch_paged_dt<DT_MM1>(a, stream);
+        case DT_MM2: return launch_paged_dt<DT_MM2>(a, stream);
+        case DT_MM4: return launch_paged_dt<DT_MM4>(a, stream);
+        case DT_MM8: return launch_paged_dt<DT_MM8>(a, stream);
     }
     set_error("paged search is not defined for dtype %d", a.ix.dtype);
     return DANN_EUNSUPPORTED;

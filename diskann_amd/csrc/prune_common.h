@@ -49,7 +49,7 @@ int32_t dispatch(const IndexView& ix, const Args& a, uint32_t grid, size_t lds, 
             return Launcher<DT, OP_L2, false>::run(a, grid, lds, stream);                              \
         }                                                                                              \
         if (op == OP_IP) {                                                                             \
-            if constexpr (DT == DT_F32 || DT == DT_F16) {                                              \
+            if constexpr (DT == DT_F32 || DT == DT_F16 || dt_is_mm(DT)) {                              \
                 if (norm) return Launcher<DT, OP_IP, true>::run(a, grid, lds, stream);                 \
             }                                                                                          \
             return Launcher<DT, OP_IP, false>::run(a, grid, lds, stream);                              \
@@ -67,6 +67,10 @@ int32_t dispatch(const IndexView& ix, const Args& a, uint32_t grid, size_t lds, 
         DANN_CASE(DT_SPH4)
         DANN_CASE(DT_SPH2)
         DANN_CASE(DT_SPH1)
+        DANN_CASE(DT_MM8)
+        DANN_CASE(DT_MM4)
+        DANN_CASE(DT_MM2)
+        DANN_CASE(DT_MM1)
     }
 #undef DANN_CASE
     set_error("bad dtype %d", ix.dtype);

@@ -17,12 +17,30 @@ enum : int {
     DT_SPH1 = 33, DT_SPH2 = 34, DT_SPH4 = 36,
     // internal, never a dann_config::dtype: DT_SPH1 rows searched with a FOUR_BIT_TRANSPOSED query (IndexView::dtype
     // of the query-taking entry points; the inner-product routine differs, so the layout is a template argument)
-    DT_SPH1T = 97
+    DT_SPH1T = 97,
+    // MinMax-quantised rows (minmax::Data<NBITS>, front-canonical: the 20-byte MinMaxCompensation, then the code
+    // bytes), dtype value 48 + bits
+    DT_MM1 = 49, DT_MM2 = 50, DT_MM4 = 52, DT_MM8 = 56
 };
 // scalar-quantised rows: SQ-8 (one byte per code) and the packed widths, whose dtype value is 16 + bits
 DANN_HD constexpr bool dt_is_sq(int dt) { return dt == DT_SQ8 || dt == DT_SQ4 || dt == DT_SQ1; }
 DANN_HD constexpr bool dt_is_sph(int dt) { return dt == DT_SPH1 || dt == DT_SPH2 || dt == DT_SPH4 || dt == DT_SPH1T; }
-DANN_HD constexpr bool dt_is_packed(int dt) { return dt == DT_SQ4 || dt == DT_SQ1 || dt_is_sph(dt); }
+DANN_HD constexpr bool dt_is_mm(int dt) { return dt == DT_MM1 || dt == DT_MM2 || dt == DT_MM4 || dt == DT_MM8; }
+// rows of sub-byte codes: a 4-lane distance group (MM8 is one byte per code and takes the u8 path's 8 lanes)
+DANN_HD constexpr bool dt_is_packed(int dt) {
+    return dt == DT_SQ4 || dt == DT_SQ1 || dt_is_sph(dt) || dt == DT_MM1 || dt == DT_MM2 || dt == DT_MM4;
+}
+// MinMax rows: bytes of the MinMaxCompensation in front of the codes, and where a query image is staged inside its
+// LDS slot.  The codes start at byte 20 of an image: staged at slot + 12 they start at slot + 32, and every 16-, 8- or
+// 4-byte LDS read of the lane shapes is naturally aligned; the slot (mm_query_lds_bytes) ends at the 16-byte step that
+// covers the last code byte -- the tail step reads whole dwords, masked beyond dim * bits.
+constexpr uint32_t kMmHeader = 20u, kMmStageOff = 12u;
+DANN_HD constexpr uint32_t query_stage_off(int dt) { return dt_is_mm(dt) ? kMmStageOff : 0u; }
+DANN_HD constexpr uint32_t mm_query_lds_bytes(uint32_t image_bytes) {
+    return kMmStageOff + kMmHeader + ((image_bytes - kMmHeader + 15u) & ~15u);
+}
+// bytes of the LDS slot of a query of integer rows staged as raw bytes
+DANN_HD constexpr uint32_t int_query_slot_bytes(int dt, uint32_t qbytes) { return dt_is_mm(dt) ? mm_query_lds_bytes(qbytes) : qbytes; }
 enum : int { M_COSINE = 0, M_IP = 1, M_L2 = 2, M_COSN = 3 };
 enum : int { OP_L2 = 0, OP_IP = 1, OP_COS = 2 };
 
@@ -43,6 +61,14 @@ DANN_HD inline bool resolve_metric(int dtype, int metric, int* op, bool* norm) {
         if (metric == M_IP) { *op = OP_IP; return true; }
         if (metric == M_COSINE) { *op = OP_COS; return true; }
         return false;
+    }
+    if (dt_is_mm(dtype)) {  // distance_comparer (minmax_repr.rs:330-335): the form of the epilogue, finish_minmax
+        if (metric == M_L2) { *op = OP_L2; return true; }
+        if (metric == M_IP) { *op = OP_IP; return true; }
+        if (metric == M_COSINE) { *op = OP_COS; return true; }
+        *op = OP_IP;
+        *norm = true;  // MinMaxCosineNormalized = 1 - v
+        return true;
     }
     if (dt_is_sq(dtype)) {
         if (metric == M_L2) { *op = OP_L2; return true; }

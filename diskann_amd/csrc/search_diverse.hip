@@ -66,7 +66,7 @@ __global__ __launch_bounds__(kWave) void diverse_search_kernel(DiverseArgs a) {
     const uint32_t cmax = dv_cmax(ix, W);
     const SqParams sqp{ix.sq_k, ix.sq_shift_norm_sq};
     uint32_t off = 0;
-    QT* qs = reinterpret_cast<QT*>(smem);
+    QT* qs = reinterpret_cast<QT*>(smem + query_stage_off(DT));
     off += round16(query_lds_bytes(ix));
     uint32_t* cand_id = reinterpret_cast<uint32_t*>(smem + off);
     off += round16(cmax * 4u);
@@ -292,7 +292,7 @@ int32_t launch_dv_dt(const DiverseArgs& a, size_t lds, hipStream_t st) {
         return launch_dv<DT, OP_L2, false>(a, lds, st);
     }
     if (op == OP_IP) {
-        if constexpr (DT == DT_F32 || DT == DT_F16) {
+        if constexpr (DT == DT_F32 || DT == DT_F16 || dt_is_mm(DT)) {
             if (norm) return launch_dv<DT, OP_IP, true>(a, lds, st);
         }
         return launch_dv<DT, OP_IP, false>(a, lds, st);
@@ -314,6 +314,10 @@ int32_t launch_dv_any(const DiverseArgs& a, size_t lds, hipStream_t st) {
         case DT_SPH1T: return launch_dv_dt<DT_SPH1T>(a, lds, st);
         case DT_SPH2: return launch_dv_dt<DT_SPH2>(a, lds, st);
         case DT_SPH4: return launch_dv_dt<DT_SPH4>(a, lds, st);
+        case DT_MM1: return launch_dv_dt<DT_MM1>(a, lds, st);
+        case DT_MM2: return launch_dv_dt<DT_MM2>(a, lds, st);
+        case DT_MM4: return launch_dv_dt<DT_MM4>(a, lds, st);
+        case DT_MM8: return launch_dv_dt<DT_MM8>(a, lds, st);
     }
     set_error("diverse search: rows of dtype %d are not supported", a.ix.dtype);
     return DANN_EUNSUPPORTED;

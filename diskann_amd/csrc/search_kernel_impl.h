@@ -1007,12 +1007,14 @@ __device__ __forceinline__ void beam_search_one(const SearchArgs& a, const uint3
                                                                                        : ((ix.nstart + 63u) & ~63u));
     // fixed-length instantiations know the staged query's size (f32 vector, raw bytes, SQ-8: bytes + compensation)
     // (spherical rows: the query's size follows its layout, a run-time property)
-    const uint32_t qbytes = DIM > 0 && !dt_is_sph(DT) ? (dt_is_sq(DT) ? sq_code_bytes(DT, (uint32_t)DIM) + 4u
+    // (MinMax rows: the image at slot + 12, mm_query_lds_bytes)
+    const uint32_t qbytes = DIM > 0 && !dt_is_sph(DT) ? (dt_is_mm(DT) ? mm_query_lds_bytes(kMmHeader + sq_code_bytes(DT, (uint32_t)DIM))
+                                                         : dt_is_sq(DT) ? sq_code_bytes(DT, (uint32_t)DIM) + 4u
                                                                       : kInt ? (uint32_t)DIM : (uint32_t)DIM * 4u)
                                                       : query_lds_bytes(ix);
     const SqParams sqp{ix.sq_k, ix.sq_shift_norm_sq};
     const SearchLds L = search_lds_layout(a.ht_entries, cmax, lds_queue_entries(a), qbytes, TEAM > 1);
-    QT* qs = reinterpret_cast<QT*>(smem + L.q_off);
+    QT* qs = reinterpret_cast<QT*>(smem + L.q_off + query_stage_off(DT));
     uint32_t* ht = reinterpret_cast<uint32_t*>(smem + L.ht_off);
     uint32_t* cand_id = reinterpret_cast<uint32_t*>(smem + L.cand_id_off);
     float* cand_d = reinterpret_cast<float*>(smem + L.cand_d_off);
@@ -1082,7 +1084,9 @@ __device__ __forceinline__ void beam_search_one(const SearchArgs& a, const uint3
     int xx_pre = 0;
     if constexpr (DIM > 0 && kInt) {
         static_assert(!kInt || DIM == 0 || DIM == 128, "integer rows: only the 128-element length is specialised");
-        if constexpr (dt_is_sph(DT)) {  // (code dwords, widened 2-bit codes or the four plane dwords)
+        if constexpr (dt_is_mm(DT)) {  // (the lane's code dwords of the staged image; 2-bit codes widened)
+            xqi = mm_query_pre<sq_bits(DT)>(reinterpret_cast<const uint8_t*>(qs), v);
+        } else if constexpr (dt_is_sph(DT)) {  // (code dwords, widened 2-bit codes or the four plane dwords)
             xqi = sph_query_pre<DT>(reinterpret_cast<const uint8_t*>(qs), v);
         } else if constexpr (dt_is_packed(DT)) {  // (64 or 16 code bytes over the group's 4 lanes)
             xqi = packed_query_pre<sq_bits(DT)>(reinterpret_cast<const uint8_t*>(qs), v);
@@ -1246,7 +1250,8 @@ __device__ __forceinline__ void beam_search_one(const SearchArgs& a, const uint3
 #pragma unroll
                     for (int u = 0; u < U; ++u) tg[u] = (act[u] && v == 0) ? rows[u][tag_off] : (uint8_t)255;
                 }
-                if constexpr (dt_is_sph(DT)) group_ip_sph_pre<DT, U>(xqi, rows, v, out);
+                if constexpr (dt_is_mm(DT)) group_ip_mm_pre<sq_bits(DT), U>(xqi, rows, v, out);
+                else if constexpr (dt_is_sph(DT)) group_ip_sph_pre<DT, U>(xqi, rows, v, out);
                 else if constexpr (dt_is_packed(DT)) group_distance_packed_pre<sq_bits(DT), OP, U>(xqi, xx_pre, rows, v, out);
                 else group_distance_int_pre<OP, DT == DT_I8, U>(xqi, xx_pre, rows, v, out);
 #pragma unroll
@@ -2452,7 +2457,7 @@ constexpr int kTeam = DANN_TEAM_WAVES;  // wavefronts per query in the latency r
 
 template <int DT, int OP, bool NORM, int QS, int DIM, int MODE, int LOOP = 0, int TEAM = 1, bool HT16 = false>
 int32_t launch_one(const SearchArgs& a, size_t lds, hipStream_t stream, int* regs_out) {
-    if constexpr (MODE == kModePlain && LOOP == 0 && TEAM == 1 && DIM > 0 && QS <= 4 && DT != DT_PQ && !dt_is_packed(DT)) {
+    if constexpr (MODE == kModePlain && LOOP == 0 && TEAM == 1 && DIM > 0 && QS <= 4 && DT != DT_PQ && !dt_is_packed(DT) && !dt_is_mm(DT)) {
         if (a.team && !a.srv.ring && !a.grid && !regs_out)
             return launch_one<DT, OP, NORM, QS, DIM, MODE, 0, kTeam>(a, lds, stream, regs_out);
     }
@@ -2534,14 +2539,14 @@ int32_t launch_dt(const SearchArgs& a, uint32_t qcap, size_t lds, hipStream_t st
                 return launch_qs<DT, OP_L2, true, 0>(a, qcap, lds, stream, regs_out);
             }
         }
-        if constexpr (dt_is_packed(DT)) {  // (packed rows: no team instantiations, team_shape)
+        if constexpr (dt_is_packed(DT) && !dt_is_mm(DT)) {  // (packed rows: no team instantiations, team_shape)
             if (norm) {
                 if (a.ix.dim == 128) return launch_qs<DT, OP_L2, true, 128>(a, qcap, lds, stream, regs_out);
                 return launch_qs<DT, OP_L2, true, 0>(a, qcap, lds, stream, regs_out);
             }
             if (a.ix.dim == 128) return launch_qs<DT, OP_L2, false, 128>(a, qcap, lds, stream, regs_out);
         }
-        if constexpr (DT == DT_U8 || DT == DT_I8 || DT == DT_SQ8) {  // 128-byte integer rows (C-int8)
+        if constexpr (DT == DT_U8 || DT == DT_I8 || DT == DT_SQ8 || dt_is_mm(DT)) {  // 128-byte integer rows (C-int8), 128-d MinMax rows
             if (a.ix.dim == 128) return launch_qs<DT, OP_L2, false, 128>(a, qcap, lds, stream, regs_out);
         }
         return launch_qs<DT, OP_L2, false, 0>(a, qcap, lds, stream, regs_out);
@@ -2550,12 +2555,18 @@ int32_t launch_dt(const SearchArgs& a, uint32_t qcap, size_t lds, hipStream_t st
         if constexpr (DT == DT_F32 || DT == DT_F16) {
             if (norm) return launch_qs<DT, OP_IP, true, 0>(a, qcap, lds, stream, regs_out);
         }
-        if constexpr (DT == DT_U8 || DT == DT_I8 || dt_is_sq(DT) || dt_is_sph(DT)) {
+        if constexpr (dt_is_mm(DT)) {  // (MinMaxCosineNormalized: the inner product's kernels, 1 - v)
+            if (norm) {
+                if (a.ix.dim == 128) return launch_qs<DT, OP_IP, true, 128>(a, qcap, lds, stream, regs_out);
+                return launch_qs<DT, OP_IP, true, 0>(a, qcap, lds, stream, regs_out);
+            }
+        }
+        if constexpr (DT == DT_U8 || DT == DT_I8 || dt_is_sq(DT) || dt_is_sph(DT) || dt_is_mm(DT)) {
             if (a.ix.dim == 128) return launch_qs<DT, OP_IP, false, 128>(a, qcap, lds, stream, regs_out);
         }
         return launch_qs<DT, OP_IP, false, 0>(a, qcap, lds, stream, regs_out);
     }
-    if constexpr (DT == DT_U8 || DT == DT_I8 || dt_is_sph(DT)) {
+    if constexpr (DT == DT_U8 || DT == DT_I8 || dt_is_sph(DT) || dt_is_mm(DT)) {
         if (a.ix.dim == 128) return launch_qs<DT, OP_COS, false, 128>(a, qcap, lds, stream, regs_out);
     }
     if constexpr (!dt_is_sq(DT) && DT != DT_PQ) return launch_qs<DT, OP_COS, false, 0>(a, qcap, lds, stream, regs_out);

@@ -68,6 +68,10 @@ int32_t launch_search(const SearchArgs& a, hipStream_t stream, int* regs_out) {
         case DT_SPH1T: return launch_search_sph1t(a, qcap, lds, stream, regs_out);
         case DT_SPH2: return launch_search_sph2(a, qcap, lds, stream, regs_out);
         case DT_SPH4: return launch_search_sph4(a, qcap, lds, stream, regs_out);
+        case DT_MM1: return launch_search_mm1(a, qcap, lds, stream, regs_out);
+        case DT_MM2: return launch_search_mm2(a, qcap, lds, stream, regs_out);
+        case DT_MM4: return launch_search_mm4(a, qcap, lds, stream, regs_out);
+        case DT_MM8: return launch_search_mm8(a, qcap, lds, stream, regs_out);
         case DT_PQ: return launch_search_pq(a, qcap, lds, stream, regs_out);
     }
     set_error("bad dtype %d", a.ix.dtype);

@@ -14,11 +14,11 @@ import os
 import numpy as np
 
 from . import _ffi
-from ._ffi import (BuildConfig, Config, DannError, SearchStats, check, F32, F16, U8, I8, SQ8, SQ1, SQ4, SPH1, SPH2, SPH4, PQ, COSINE, INNER_PRODUCT, L2,
+from ._ffi import (BuildConfig, Config, DannError, SearchStats, check, F32, F16, U8, I8, SQ8, SQ1, SQ4, SPH1, SPH2, SPH4, MM1, MM2, MM4, MM8, PQ, COSINE, INNER_PRODUCT, L2,
                    COSINE_NORMALIZED, IBC_ALL, IBC_NONE)
 
 NP_DTYPE = {F32: np.float32, F16: np.float16, U8: np.uint8, I8: np.int8, SQ8: np.uint8, SQ1: np.uint8, SQ4: np.uint8, SPH1: np.uint8, SPH2: np.uint8,
-            SPH4: np.uint8, PQ: np.uint8}
+            SPH4: np.uint8, MM1: np.uint8, MM2: np.uint8, MM4: np.uint8, MM8: np.uint8, PQ: np.uint8}
 FILTER_INLINE, FILTER_MULTIHOP = 1, 2  # dann.h DANN_FILTER_*
 STATS_DTYPE = np.dtype([("cmps", np.uint32), ("hops", np.uint32), ("result_count", np.uint32), ("status", np.uint32),
                         ("written", np.uint32)])
@@ -87,9 +87,9 @@ class Provider:
         self.dtype, self.metric, self.dim = dtype, metric, int(dim)
         self.capacity, self.max_degree = int(capacity), int(max_degree)
         # quantised rows are their payload bytes: the code bytes and a trailing f32 compensation (scalar) or DataMeta
-        # (spherical)
+        # (spherical); MinMax rows: the 20-byte MinMaxCompensation, then the code bytes
         self.row_elems = (int(_ffi.lib().dann_layer_bytes(dtype, self.dim))
-                          if dtype in (SQ8, SQ4, SQ1, SPH1, SPH2, SPH4) else self.dim)
+                          if dtype in (SQ8, SQ4, SQ1, SPH1, SPH2, SPH4, MM1, MM2, MM4, MM8) else self.dim)
         self.query_dtype, self.query_elems = NP_DTYPE[dtype], self.row_elems
         pq_chunks = 0
         if dtype == PQ:  # rows are PQ codes, queries stay full-precision f32
@@ -691,6 +691,18 @@ def sq_compress(x, shift, scale, bits, device=-1):
     check(_ffi.lib().dann_sq_compress(device, int(bits), _p(x), x.shape[0], x.shape[1], _p(shift), float(scale), _p(out)),
           "dann_sq_compress")
     return out
+
+
+def minmax_compress(x, bits, grid_scale=1.0, device=-1, return_loss=False):
+    """MinMaxQuantizer::compress_into::<bits> on the GPU, bits in (1, 2, 4, 8), for vectors already through the
+    quantiser's transform: MM1 / MM2 / MM4 / MM8 row images of 20 + ceil(dim * bits / 8) bytes (and the L2 losses)"""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    x = x.reshape(-1, x.shape[-1])
+    out = np.empty((x.shape[0], 20 + (x.shape[1] * int(bits) + 7) // 8), np.uint8)
+    loss = np.empty(x.shape[0], np.float32)
+    check(_ffi.lib().dann_minmax_compress(device, int(bits), _p(x), x.shape[0], x.shape[1], float(grid_scale), _p(out),
+                                          _p(loss)), "dann_minmax_compress")
+    return (out, loss) if return_loss else out
 
 
 def pq_build_lut(metric, pivots, chunk_offsets, queries, device=-1):

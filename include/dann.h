@@ -70,7 +70,24 @@ typedef enum {
      * take part, whatever the padding bits hold. */
     DANN_SPH1 = 33,
     DANN_SPH2 = 34,
-    DANN_SPH4 = 36
+    DANN_SPH4 = 36,
+    /* MinMax-quantised rows, value 48 + bits: the front-canonical byte image of minmax::Data<NBITS>
+     * (diskann-quantization/src/minmax/vectors.rs, meta/vector.rs:124-146; what MinMax8 / MinMax4 of
+     * diskann-providers/src/common/minmax_repr.rs and Garnet's MinMax8Bit store) -- the 20-byte MinMaxCompensation
+     * first (vectors.rs:43-51, little-endian: u32 dim, f32 b, f32 n, f32 a, f32 norm_squared), then ceil(dim * bits / 8)
+     * code bytes in the Dense permutation, packed as DANN_SQ1 / DANN_SQ4 / DANN_SPH2 rows (8 bits: one byte per code).
+     * `dim` is the quantiser's output_dim(); the kernels never read the header's dim, the host-pointer row writers
+     * (dann_set_element(s), dann_load_vectors_bin, the start rows of dann_index_create, dann_query_create) answer
+     * DANN_EINVAL for an image whose leading u32 differs from it, the device-pointer and verbatim paths do not look.
+     * dim * (2^bits - 1)^2 must fit a u32 (else DANN_EINVAL).  All four metrics: MinMaxCosine, MinMaxIP,
+     * MinMaxL2Squared, MinMaxCosineNormalized (vectors.rs:206-473, distance_comparer minmax_repr.rs:330-335), bit for
+     * bit, the query (in prunes: the candidate under test) as the function's first argument -- the epilogue is not
+     * symmetric in its arguments.  No training: sq_scale and sq_shift_norm_sq are ignored.  Queries are row images
+     * (DANN_QUERY_SAME_AS_DATA).  Elements at or beyond dim never take part, whatever the padding bits hold. */
+    DANN_MM1 = 49,
+    DANN_MM2 = 50,
+    DANN_MM4 = 52,
+    DANN_MM8 = 56
 } dann_dtype;
 
 /* iface::QueryLayout: the byte image of a query of a spherical index.  QueryMeta is four f32: inner_product_correction,
@@ -81,7 +98,10 @@ typedef enum {
                                            64 four-bit values (bits/distances.rs:2123-2249): ceil(dim / 64) * 32 plane
                                            bytes, then the QueryMeta                                                   */
     DANN_QUERY_SCALAR_QUANTIZED = 2,    /* 2- and 4-bit rows: Dense codes of the rows' width, then the QueryMeta        */
-    DANN_QUERY_FULL_PRECISION = 3       /* reserved: DANN_EUNSUPPORTED                                                  */
+    DANN_QUERY_FULL_PRECISION = 3,      /* reserved: DANN_EUNSUPPORTED                                                  */
+    /* 4 .. 7: DANN_EINVAL */
+    DANN_QUERY_EIGHT_BIT = 8            /* MinMaxQuery::EightBit, an MM8 image against narrower MinMax rows: reserved,
+                                           DANN_EUNSUPPORTED on every index                                            */
 } dann_query_layout;
 
 /* == `#[repr(C)] enum Metric`, diskann-vector/src/distance/metric.rs:8-20 */
@@ -464,6 +484,12 @@ int32_t dann_sq8_compress(int32_t device, const float* x, uint32_t n, uint32_t d
  * (the trained scale and shift do not depend on it, quantizer.rs:187-189).  Host pointers. */
 int32_t dann_sq_compress(int32_t device, int32_t bits, const float* x, uint32_t n, uint32_t dim, const float* shift,
                          float scale, void* out);
+/* MinMaxQuantizer::compress_into::<bits> (minmax/quantizer.rs:117-228) for vectors that have already been through the
+ * quantiser's transform (the host keeps the Transform; NullTransform = the data itself).  bits in {1, 2, 4, 8}.
+ * out: n row images of dann_layer_bytes(48 + bits, dim), padding bits zero; out_loss (optional, n): L2Loss::as_f32.
+ * A NaN in row i: DANN_EINVAL (InputContainsNaN), outputs unspecified.  Host pointers. */
+int32_t dann_minmax_compress(int32_t device, int32_t bits, const float* x, uint32_t n, uint32_t dim, float grid_scale,
+                             void* out, float* out_loss);
 
 /* build-path options (never change the resulting graph).  The matrix-core path evaluates the pair similarities a
  * RobustPrune asks for (prune.rs:196-232) as the lower triangle of one Gram matrix per candidate list
@@ -645,7 +671,7 @@ int32_t dann_drop_deleted_neighbors(dann_index* idx, const dann_build_config* cf
                                     uint32_t only_orphans, int32_t* out_kind);
 
 /* ABI revision of this header; bumped on any incompatible change of a signature or struct layout */
-#define DANN_ABI_VERSION 4
+#define DANN_ABI_VERSION 5
 int32_t dann_abi_version(void);
 
 /* ---- diagnostics ------------------------------------------------------------------- */
