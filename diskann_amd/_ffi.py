@@ -27,6 +27,8 @@ CONSOLIDATE_COMPLETE, CONSOLIDATE_DELETED = 0, 1  # ConsolidateKind (dann_consol
 CONSOLIDATE_DROP_DELETED = 1  # dann_consolidate flag
 INPLACE_VISITED_AND_TOPK, INPLACE_TWO_HOP_AND_ONE_HOP, INPLACE_ONE_HOP = 0, 1, 2  # dann_inplace_delete_params.method
 INPLACE_COUNTERS = 9
+# dann_transform_parts.kind (TransformKind); RANDOM_ROTATION is reserved (DANN_EUNSUPPORTED)
+TRANSFORM_NULL, TRANSFORM_PADDING_HADAMARD, TRANSFORM_DOUBLE_HADAMARD, TRANSFORM_RANDOM_ROTATION = 0, 1, 2, 3
 
 
 class Config(C.Structure):
@@ -84,6 +86,13 @@ class ServerConfig(C.Structure):
     """dann_server_config: the resident search server (dann_server_start)."""
     _fields_ = [("l_value", C.c_uint32), ("k", C.c_uint32), ("workers", C.c_uint32), ("ring", C.c_uint32),
                 ("idle_timeout_us", C.c_uint32)]
+
+
+class TransformParts(C.Structure):
+    """dann_transform_parts: the arguments of Transform::try_from_parts (host pointers, copied by dann_transform_create)."""
+    _fields_ = [("kind", C.c_int32), ("dim", C.c_uint32), ("signs0", C.c_void_p), ("signs0_len", C.c_uint32),
+                ("signs1", C.c_void_p), ("signs1_len", C.c_uint32), ("padded_dim", C.c_uint32),
+                ("subsample", C.c_void_p), ("subsample_len", C.c_uint32)]
 
 
 class SearchStats(C.Structure):
@@ -170,6 +179,14 @@ SYMBOLS = {
     "dann_sq8_compress": (_i32, [_i32, _vp, _u32, _u32, _vp, _f32, _vp]),
     "dann_sq_compress": (_i32, [_i32, _i32, _vp, _u32, _u32, _vp, _f32, _vp]),
     "dann_minmax_compress": (_i32, [_i32, _i32, _vp, _u32, _u32, _f32, _vp, _vp]),
+    "dann_transform_create": (_i32, [_i32, _P(TransformParts), _P(_vp)]),
+    "dann_transform_destroy": (_i32, [_vp]),
+    "dann_transform_input_dim": (_i32, [_vp]),
+    "dann_transform_output_dim": (_i32, [_vp]),
+    "dann_transform_apply": (_i32, [_vp, _vp, _u32, _vp]),
+    "dann_transform_apply_device": (_i32, [_vp, _vp, _u64, _u32, _vp, _u64]),
+    "dann_minmax_quantize": (_i32, [_vp, _i32, _f32, _vp, _u32, _vp, _vp]),
+    "dann_minmax_quantize_device": (_i32, [_vp, _i32, _f32, _vp, _u64, _u32, _vp, _u64, _vp]),
     "dann_pq_build_lut": (_i32, [_i32, _i32, _vp, _vp, _u32, _u32, _vp, _u32, _vp]),
     "dann_pq_compress": (_i32, [_i32, _vp, _u32, _vp, _u32, _u32, _vp, _u64, _vp]),
     "dann_pq_lloyds": (_i32, [_i32, _vp, _u64, _u32, _vp, _u32, _u32, _vp, _u32, _vp, _vp]),

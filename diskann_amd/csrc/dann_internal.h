@@ -144,6 +144,10 @@ int32_t prune_pools_into_rows(dann_index* idx, const dann_build_config& cfg, con
 // idx->d_deleted, allocated and cleared on first use (consolidate.hip; dann_delete_points, dann_inplace_delete)
 int32_t ensure_deleted_bitmap(dann_index* idx);
 
+// minmax_kernels.hip: MinMaxQuantizer::compress on device buffers (dann_minmax_compress, dann_minmax_quantize(_device))
+int32_t launch_minmax_compress(int32_t bits, const float* d_x, uint32_t n, uint32_t dim, float grid_scale, uint8_t* d_out,
+                               float* d_out_loss, uint32_t* d_nan_flag, hipStream_t stream);
+
 int32_t launch_expand_beam(const IndexView& ix, const void* d_queries, uint32_t nq, const uint32_t* d_ids,
                            const uint64_t* d_offsets, uint64_t max_len, float* d_out, hipStream_t stream);
 int32_t launch_rerank(const IndexView& ix, const void* d_queries, uint32_t nq, const uint32_t* d_cand, uint32_t stride,

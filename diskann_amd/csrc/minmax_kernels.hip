@@ -85,6 +85,20 @@ __global__ __launch_bounds__(64) void minmax_compress_kernel(const float* __rest
 }
 
 }  // namespace
+
+// minmax_compress_kernel on device buffers: x packed n x dim, out n zeroed packed images, out_loss optional, nan_flag cleared
+int32_t launch_minmax_compress(int32_t bits, const float* px, uint32_t n, uint32_t dim, float grid_scale, uint8_t* po,
+                               float* pl, uint32_t* pf, hipStream_t st) {
+    const dim3 grid((n + 63u) / 64u), block(64);
+    switch (bits) {
+        case 1: hipLaunchKernelGGL(minmax_compress_kernel<1>, grid, block, 0, st, px, n, dim, grid_scale, po, pl, pf); break;
+        case 2: hipLaunchKernelGGL(minmax_compress_kernel<2>, grid, block, 0, st, px, n, dim, grid_scale, po, pl, pf); break;
+        case 4: hipLaunchKernelGGL(minmax_compress_kernel<4>, grid, block, 0, st, px, n, dim, grid_scale, po, pl, pf); break;
+        default: hipLaunchKernelGGL(minmax_compress_kernel<8>, grid, block, 0, st, px, n, dim, grid_scale, po, pl, pf); break;
+    }
+    DANN_HIP(hipGetLastError());
+    return DANN_OK;
+}
 }  // namespace dann
 
 extern "C" int32_t dann_minmax_compress(int32_t device, int32_t bits, const float* x, uint32_t n, uint32_t dim,
@@ -111,18 +125,10 @@ extern "C" int32_t dann_minmax_compress(int32_t device, int32_t bits, const floa
     DANN_HIP(hipMemcpy(dx.p, x, xb, hipMemcpyHostToDevice));
     DANN_HIP(hipMemset(dout.p, 0, ob));
     DANN_HIP(hipMemset(dflag.p, 0, 4));
-    const dim3 grid((n + 63u) / 64u), block(64);
-    const float* px = static_cast<const float*>(dx.p);
-    uint8_t* po = static_cast<uint8_t*>(dout.p);
-    float* pl = static_cast<float*>(dloss.p);
-    uint32_t* pf = static_cast<uint32_t*>(dflag.p);
-    switch (bits) {
-        case 1: hipLaunchKernelGGL(minmax_compress_kernel<1>, grid, block, 0, 0, px, n, dim, grid_scale, po, pl, pf); break;
-        case 2: hipLaunchKernelGGL(minmax_compress_kernel<2>, grid, block, 0, 0, px, n, dim, grid_scale, po, pl, pf); break;
-        case 4: hipLaunchKernelGGL(minmax_compress_kernel<4>, grid, block, 0, 0, px, n, dim, grid_scale, po, pl, pf); break;
-        default: hipLaunchKernelGGL(minmax_compress_kernel<8>, grid, block, 0, 0, px, n, dim, grid_scale, po, pl, pf); break;
-    }
-    DANN_HIP(hipGetLastError());
+    if (int32_t rc = launch_minmax_compress(bits, static_cast<const float*>(dx.p), n, dim, grid_scale,
+                                            static_cast<uint8_t*>(dout.p), static_cast<float*>(dloss.p),
+                                            static_cast<uint32_t*>(dflag.p), nullptr))
+        return rc;
     uint32_t flag = 0;
     DANN_HIP(hipMemcpy(&flag, dflag.p, 4, hipMemcpyDeviceToHost));
     DANN_HIP(hipMemcpy(out, dout.p, ob, hipMemcpyDeviceToHost));

@@ -705,6 +705,95 @@ def minmax_compress(x, bits, grid_scale=1.0, device=-1, return_loss=False):
     return (out, loss) if return_loss else out
 
 
+_ONE_U32 = np.zeros(1, np.uint32)
+
+
+class Transform:
+    """algorithms::transforms::Transform resident on one device, built from its parts (Transform::try_from_parts: the
+    host constructs a transform, drawing the random signs and subsample indices; applying one is deterministic)."""
+
+    def __init__(self, parts, keep=(), device=-1):
+        h = C.c_void_p()
+        check(_ffi.lib().dann_transform_create(int(device), C.byref(parts), C.byref(h)), "dann_transform_create")
+        del keep  # (the arrays the parts point into: copied by now)
+        self._h = h
+        self.input_dim = _ffi.lib().dann_transform_input_dim(h)
+        self.output_dim = _ffi.lib().dann_transform_output_dim(h)
+
+    @staticmethod
+    def _u32(a):
+        """(array, pointer, length); an empty array still has a non-null pointer (present but empty)"""
+        if a is None:
+            return None, None, 0
+        a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
+        return a, _p(a if a.size else _ONE_U32), a.size
+
+    @classmethod
+    def null(cls, dim, device=-1):
+        return cls(_ffi.TransformParts(kind=_ffi.TRANSFORM_NULL, dim=int(dim)), device=device)
+
+    @classmethod
+    def padding_hadamard(cls, signs, padded_dim, subsample=None, device=-1):
+        s, sp, sn = cls._u32(signs)
+        u, up, un = cls._u32(subsample)
+        return cls(_ffi.TransformParts(kind=_ffi.TRANSFORM_PADDING_HADAMARD, signs0=sp, signs0_len=sn,
+                                       padded_dim=int(padded_dim), subsample=up, subsample_len=un), (s, u), device)
+
+    @classmethod
+    def double_hadamard(cls, signs0, signs1, subsample=None, device=-1):
+        s0, s0p, s0n = cls._u32(signs0)
+        s1, s1p, s1n = cls._u32(signs1)
+        u, up, un = cls._u32(subsample)
+        return cls(_ffi.TransformParts(kind=_ffi.TRANSFORM_DOUBLE_HADAMARD, signs0=s0p, signs0_len=s0n, signs1=s1p,
+                                       signs1_len=s1n, subsample=up, subsample_len=un), (s0, s1, u), device)
+
+    def apply(self, x):
+        """Transform::transform_into for (n, input_dim) host rows -> (n, output_dim) f32"""
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, self.input_dim)
+        out = np.empty((x.shape[0], self.output_dim), np.float32)
+        check(_ffi.lib().dann_transform_apply(self._h, _p(x), x.shape[0], _p(out)), "dann_transform_apply")
+        return out
+
+    def apply_device(self, x_ptr, n, out_ptr, x_stride=0, out_stride=0):
+        """n rows at device address x_ptr -> out_ptr on the transform's device; strides in floats (0 = packed)"""
+        check(_ffi.lib().dann_transform_apply_device(self._h, C.c_void_p(int(x_ptr)), int(x_stride) or self.input_dim, int(n),
+                                                     C.c_void_p(int(out_ptr)), int(out_stride) or self.output_dim),
+              "dann_transform_apply_device")
+
+    def close(self):
+        if self._h:
+            _ffi.lib().dann_transform_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def minmax_quantize(t, x, bits, grid_scale=1.0, return_loss=False):
+    """MinMaxQuantizer::compress_into::<bits> including the transform `t`, on the GPU: (n, t.input_dim) f32 host rows ->
+    MM1 / MM2 / MM4 / MM8 images of 20 + ceil(t.output_dim * bits / 8) bytes (and the L2 losses)"""
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, t.input_dim)
+    out = np.empty((x.shape[0], 20 + (t.output_dim * int(bits) + 7) // 8), np.uint8)
+    loss = np.empty(x.shape[0], np.float32) if return_loss else None
+    check(_ffi.lib().dann_minmax_quantize(t._h, int(bits), float(grid_scale), _p(x), x.shape[0], _p(out), _p(loss)),
+          "dann_minmax_quantize")
+    return (out, loss) if return_loss else out
+
+
+def minmax_quantize_device(t, x_ptr, n, bits, out_ptr, grid_scale=1.0, x_stride=0, out_stride=0, loss_ptr=0):
+    """the same device to device: n rows at device address x_ptr (x_stride floats apart, 0 = packed) -> images at out_ptr
+    (out_stride bytes apart, 0 = packed), ready for Provider.set_elements_device or as device queries; loss_ptr
+    (optional): n f32 on the device"""
+    lb = 20 + (t.output_dim * int(bits) + 7) // 8
+    check(_ffi.lib().dann_minmax_quantize_device(t._h, int(bits), float(grid_scale), C.c_void_p(int(x_ptr)),
+                                                 int(x_stride) or t.input_dim, int(n), C.c_void_p(int(out_ptr)),
+                                                 int(out_stride) or lb, C.c_void_p(int(loss_ptr)) if loss_ptr else None),
+          "dann_minmax_quantize_device")
+
+
 def pq_build_lut(metric, pivots, chunk_offsets, queries, device=-1):
     piv = np.ascontiguousarray(pivots, dtype=np.float32)
     off = np.ascontiguousarray(chunk_offsets, dtype=np.uint32)

@@ -491,6 +491,58 @@ int32_t dann_sq_compress(int32_t device, int32_t bits, const float* x, uint32_t 
 int32_t dann_minmax_compress(int32_t device, int32_t bits, const float* x, uint32_t n, uint32_t dim, float grid_scale,
                              void* out, float* out_loss);
 
+/* ---- the quantisers' transforms (diskann-quantization/src/algorithms/transforms), applied on the GPU, device to device.
+ * Only CONSTRUCTING a transform draws random numbers; the host keeps doing that and hands over the parts that
+ * Transform::try_from_parts and the flatbuffer carry.  Applying one is deterministic and is restated bit for bit from
+ * the reference's x86-64 V3 path of hadamard_transform (algorithms/hadamard.rs:22-371):
+ *   NullTransform    a copy
+ *   PaddingHadamard  padding_hadamard.rs:204-273: input_dim = signs0_len, output_dim = subsample_len or padded_dim
+ *   DoubleHadamard   double_hadamard.rs:238-287 (as its code runs: both transforms, also when the intermediate length is
+ *                    a power of two): input_dim = signs0_len, output_dim = subsample_len or signs1_len
+ *   RandomRotation   reserved: DANN_EUNSUPPORTED (a dense matrix through the reference's sgemm, whose summation order is
+ *                    not part of its source)
+ * Validation is that of try_from_parts (padding_hadamard.rs:137-173, double_hadamard.rs:146-206): each error variant is
+ * DANN_EINVAL with the variant's name in the message; so are a padded_dim that is not a power of two, empty signs, and
+ * a DoubleHadamard with a subsample whose signs1_len differs from signs0_len (the reference's constructor never builds
+ * one and its transform would index out of bounds).  A working length (padded_dim, or max(input_dim, output_dim)) above
+ * 16384 floats: DANN_EUNSUPPORTED. */
+enum { DANN_TRANSFORM_NULL = 0,
+       DANN_TRANSFORM_PADDING_HADAMARD = 1,
+       DANN_TRANSFORM_DOUBLE_HADAMARD = 2,
+       DANN_TRANSFORM_RANDOM_ROTATION = 3 /* reserved: DANN_EUNSUPPORTED */ } /* dann_transform_kind */;
+typedef struct {
+    int32_t kind;              /* DANN_TRANSFORM_* */
+    uint32_t dim;              /* NULL only: input = output dim */
+    const uint32_t* signs0;    /* each 0 or 0x80000000; PADDING: `signs` */
+    uint32_t signs0_len;       /* = input_dim */
+    const uint32_t* signs1;    /* DOUBLE only */
+    uint32_t signs1_len;
+    uint32_t padded_dim;       /* PADDING only */
+    const uint32_t* subsample; /* NULL with subsample_len 0 = none; strictly increasing */
+    uint32_t subsample_len;
+} dann_transform_parts;        /* host pointers; the arrays are copied */
+typedef struct dann_transform dann_transform; /* == algorithms::transforms::Transform, resident on one device */
+int32_t dann_transform_create(int32_t device, const dann_transform_parts* parts, dann_transform** out);
+int32_t dann_transform_destroy(dann_transform* t);
+int32_t dann_transform_input_dim(const dann_transform* t);
+int32_t dann_transform_output_dim(const dann_transform* t);
+/* Transform::transform_into for n rows.  Host pointers, packed rows of input_dim / output_dim floats. */
+int32_t dann_transform_apply(const dann_transform* t, const float* x, uint32_t n, float* out);
+/* The same on the transform's device: strides in floats (>= the respective dim, else DANN_EINVAL), floats between the
+ * rows of d_out are left untouched; complete on return. */
+int32_t dann_transform_apply_device(const dann_transform* t, const float* d_x, uint64_t x_stride, uint32_t n, float* d_out,
+                                    uint64_t out_stride);
+/* MinMaxQuantizer::compress_into::<bits> INCLUDING the transform (minmax/quantizer.rs:117-228): x n rows of input_dim
+ * floats, out n images of dann_layer_bytes(48 + bits, output_dim), padding bits zero; out_loss optional.  A NaN in a
+ * transformed vector: DANN_EINVAL (InputContainsNaN).  bits and grid_scale as dann_minmax_compress.  Host pointers. */
+int32_t dann_minmax_quantize(const dann_transform* t, int32_t bits, float grid_scale, const float* x, uint32_t n, void* out,
+                             float* out_loss);
+/* Device form: rows x_stride floats apart, images out_stride bytes apart (>= the layer bytes; bytes between images are
+ * left untouched), ready for dann_set_elements_device or as d_queries; d_out_loss (optional) n floats on the device.
+ * One 4-byte NaN flag is read back, nothing else crosses PCIe; complete on return. */
+int32_t dann_minmax_quantize_device(const dann_transform* t, int32_t bits, float grid_scale, const float* d_x,
+                                    uint64_t x_stride, uint32_t n, void* d_out, uint64_t out_stride, float* d_out_loss);
+
 /* build-path options (never change the resulting graph).  The matrix-core path evaluates the pair similarities a
  * RobustPrune asks for (prune.rs:196-232) as the lower triangle of one Gram matrix per candidate list
  * (v_mfma_f32_32x32x2_f32; three kernels: list / sort, Gram tiles, sweep), with a bit-exact re-evaluation of every
