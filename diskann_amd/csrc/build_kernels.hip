@@ -2015,27 +2015,24 @@ __global__ void set_bulk_kernel(IndexView ix, const uint32_t* locs, const uint32
 }
 
 // ---- dispatch helpers ------------------------------------------------------------------------
-DANN_LAUNCHER(PoolLauncher, pool_prune_kernel, PoolArgs)
-DANN_LAUNCHER(BootLauncher, bootstrap_kernel, ListArgs)
-DANN_LAUNCHER(BackLauncher, backedge_kernel, BackArgs)
+constexpr auto kPoolPrune = [](auto r) { using R = decltype(r); return KernelOf<pool_prune_kernel<R::dt, R::op, R::norm>>{}; };
+constexpr auto kBootstrap = [](auto r) { using R = decltype(r); return KernelOf<bootstrap_kernel<R::dt, R::op, R::norm>>{}; };
+constexpr auto kBackedge = [](auto r) { using R = decltype(r); return KernelOf<backedge_kernel<R::dt, R::op, R::norm>>{}; };
 
 // the three kernels of the MFMA pool prune: float rows (f32 / f16), L2 / inner product / cosine-normalized
-template <template <int, int, bool> class K, class Args>
-int32_t dispatch_float(const IndexView& ix, const Args& a, uint32_t grid, size_t lds, hipStream_t stream) {
-    int op;
-    bool norm;
-    if (!resolve_metric(ix.dtype, ix.metric, &op, &norm) || op == OP_COS || (ix.dtype != DT_F32 && ix.dtype != DT_F16))
+template <class Kernel, class Args>
+int32_t launch_float_rows(const IndexView& ix, Kernel kernel, const char* what, const Args& a, uint32_t grid, size_t lds,
+                          hipStream_t stream) {
+    const int32_t rc = visit_row_op<kRowsFloat>(ix.dtype, ix.metric, [&](auto r) -> int32_t {
+        if constexpr (decltype(r)::op != OP_COS)
+            return launch_kernel<decltype(kernel(r))::fn>(what, dim3(grid), dim3(kWave), lds, stream, a);
         return DANN_EUNSUPPORTED;
-    if (ix.dtype == DT_F32) {
-        if (op == OP_L2) return K<DT_F32, OP_L2, false>::run(a, grid, lds, stream);
-        return norm ? K<DT_F32, OP_IP, true>::run(a, grid, lds, stream) : K<DT_F32, OP_IP, false>::run(a, grid, lds, stream);
-    }
-    if (op == OP_L2) return K<DT_F16, OP_L2, false>::run(a, grid, lds, stream);
-    return norm ? K<DT_F16, OP_IP, true>::run(a, grid, lds, stream) : K<DT_F16, OP_IP, false>::run(a, grid, lds, stream);
+    });
+    return rc == kNoMetric || rc == kNoRow ? DANN_EUNSUPPORTED : rc;
 }
-DANN_LAUNCHER(SortLauncher, pool_sort_kernel, SortArgs)
-DANN_LAUNCHER(SweepLauncher, pool_sweep_kernel, SweepArgs)
-DANN_LAUNCHER(BackListLauncher, backedge_list_kernel, BackListArgs)
+constexpr auto kPoolSort = [](auto r) { using R = decltype(r); return KernelOf<pool_sort_kernel<R::dt, R::op, R::norm>>{}; };
+constexpr auto kPoolSweep = [](auto r) { using R = decltype(r); return KernelOf<pool_sweep_kernel<R::dt, R::op, R::norm>>{}; };
+constexpr auto kBackedgeList = [](auto r) { using R = decltype(r); return KernelOf<backedge_list_kernel<R::dt, R::op, R::norm>>{}; };
 
 // f16_mfma: f16 rows through v_mfma_f32_32x32x16_f16 (gram_tiles_f16_kernel; the default) instead of widened through the
 // f32 matrix core (DANN_DBG_GRAM_F16_WIDEN: the round-3 form, whose entries are the reference's FMA chain bit for bit)
@@ -2050,26 +2047,12 @@ int32_t launch_gram_tiles(const TileArgs& a, uint32_t grid, hipStream_t stream, 
     uint32_t tmax = 0;
     for (uint32_t b2 = 0; b2 < tr; ++b2) tmax += (b2 < tc ? b2 : tc - 1u) + 1u;
     const bool narrow = tmax <= 8u;
-    const void* fn = h16 ? (narrow ? (const void*)gram_tiles_f16_kernel<1> : (const void*)gram_tiles_f16_kernel<3>)
-                   : narrow ? (f32 ? (const void*)gram_tiles_kernel<float, 1> : (const void*)gram_tiles_kernel<__half, 1>)
-                            : (f32 ? (const void*)gram_tiles_kernel<float, 3> : (const void*)gram_tiles_kernel<__half, 3>);
-    if (lds > 64u * 1024u) {  // beyond the default limit of dynamic LDS
-        hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (ea != hipSuccess) return hip_fail(ea, "hipFuncSetAttribute");
-    }
-    if (h16) {
-        if (narrow) hipLaunchKernelGGL((gram_tiles_f16_kernel<1>), dim3(grid), dim3(512), lds, stream, a);
-        else hipLaunchKernelGGL((gram_tiles_f16_kernel<3>), dim3(grid), dim3(512), lds, stream, a);
-    } else if (narrow) {
-        if (f32) hipLaunchKernelGGL((gram_tiles_kernel<float, 1>), dim3(grid), dim3(512), lds, stream, a);
-        else hipLaunchKernelGGL((gram_tiles_kernel<__half, 1>), dim3(grid), dim3(512), lds, stream, a);
-    } else {
-        if (f32) hipLaunchKernelGGL((gram_tiles_kernel<float, 3>), dim3(grid), dim3(512), lds, stream, a);
-        else hipLaunchKernelGGL((gram_tiles_kernel<__half, 3>), dim3(grid), dim3(512), lds, stream, a);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gram_tiles_kernel launch");
-    return DANN_OK;
+    const auto go = [&](auto kernel) {
+        return launch_kernel<decltype(kernel)::fn>("gram_tiles_kernel launch", dim3(grid), dim3(512), lds, stream, a);
+    };
+    if (h16) return narrow ? go(KernelOf<gram_tiles_f16_kernel<1>>{}) : go(KernelOf<gram_tiles_f16_kernel<3>>{});
+    if (f32) return narrow ? go(KernelOf<gram_tiles_kernel<float, 1>>{}) : go(KernelOf<gram_tiles_kernel<float, 3>>{});
+    return narrow ? go(KernelOf<gram_tiles_kernel<__half, 1>>{}) : go(KernelOf<gram_tiles_kernel<__half, 3>>{});
 }
 
 uint32_t next_pow2(uint32_t x) {
@@ -2379,7 +2362,7 @@ static int32_t batch_candidates(dann_index* idx, const dann_build_config& cfg, B
         so.sid = s.g_sid.as<uint32_t>();
         so.sd = s.g_sd.as<float>();
         so.sn = s.g_sn.as<uint32_t>();
-        rc = dispatch_float<SortLauncher>(ix, so, m, lds, st);
+        rc = launch_float_rows(ix, kPoolSort, "pool_sort_kernel launch", so, m, lds, st);
         if (rc != DANN_OK) return rc;
         TileArgs ta;
         ta.ix = ix;
@@ -2411,12 +2394,12 @@ static int32_t batch_candidates(dann_index* idx, const dann_build_config& cfg, B
         sw.one_by_one = sweep_one_by_one(idx);
         sw.order = ta.order;
         sw.compact_lds = sweep_is_batched(pc, mg, sw.one_by_one) ? 1u : 0u;
-        rc = dispatch_float<SweepLauncher>(ix, sw, m, sweep_lds_bytes(sw), st);
+        rc = launch_float_rows(ix, kPoolSweep, "pool_sweep_kernel launch", sw, m, sweep_lds_bytes(sw), st);
         if (rc != DANN_OK) return rc;
         pool_gram = true;
     }
     if (!pool_gram) {
-        rc = dispatch<PoolLauncher>(ix, pa, m, lds, st);
+        rc = launch_rows(ix, kPoolPrune, "pool_prune_kernel launch", pa, m, lds, st);
         if (rc != DANN_OK) return rc;
     }
     hipLaunchKernelGGL(stats_reduce_kernel, dim3((m + 255u) / 256u), dim3(256), 0, st, s.stats.as<dann_search_stats>(), m,
@@ -2505,7 +2488,7 @@ static int32_t batch_commit(dann_index* idx, const dann_build_config& cfg, Build
             return DANN_EUNSUPPORTED;
         }
         const size_t lds = pool_lds_layout(la.pcap, pc.pruned_degree).total;
-        rc = dispatch<BootLauncher>(ix, la, n, lds, st);
+        rc = launch_rows(ix, kBootstrap, "bootstrap_kernel launch", la, n, lds, st);
         if (rc != DANN_OK) return rc;
         pending = s.pending2.as<uint32_t>();
         rc = aggregate(h_meta);
@@ -2568,7 +2551,7 @@ static int32_t batch_commit(dann_index* idx, const dann_build_config& cfg, Build
                 return DANN_EOVERFLOW;
             }
             ba.pcap = pcap_all;
-            rc = dispatch<BackLauncher>(ix, ba, ba.nseg, pool_lds_layout(ba.pcap, pc.pruned_degree).total, st);
+            rc = launch_rows(ix, kBackedge, "backedge_kernel launch", ba, ba.nseg, pool_lds_layout(ba.pcap, pc.pruned_degree).total, st);
             if (rc != DANN_OK) return rc;
         } else {
         uint32_t* work = s.seg_len.as<uint32_t>() + (size_t)n * s.degree;  // 2 x nseg entries behind seg_len
@@ -2619,7 +2602,7 @@ static int32_t batch_commit(dann_index* idx, const dann_build_config& cfg, Build
                 run_on = side;
                 side_busy = true;
             }
-            rc = dispatch<BackLauncher>(ix, bl, bl.nseg, pool_lds_layout(bl.pcap, pc.pruned_degree).total, run_on);
+            rc = launch_rows(ix, kBackedge, "backedge_kernel launch", bl, bl.nseg, pool_lds_layout(bl.pcap, pc.pruned_degree).total, run_on);
             if (rc != DANN_OK) return rc;
         }
         // (3) short lists
@@ -2641,7 +2624,7 @@ static int32_t batch_commit(dann_index* idx, const dann_build_config& cfg, Build
                 la.sd = s.g_sd.as<float>();
                 la.sn = s.g_sn.as<uint32_t>();
                 la.loc = s.g_loc.as<uint32_t>();
-                rc = dispatch_float<BackListLauncher>(ix, la, nshort, lds_pool, st);
+                rc = launch_float_rows(ix, kBackedgeList, "backedge_list_kernel launch", la, nshort, lds_pool, st);
                 if (rc != DANN_OK) return rc;
                 TileArgs ta;
                 ta.ix = ix;
@@ -2678,12 +2661,12 @@ static int32_t batch_commit(dann_index* idx, const dann_build_config& cfg, Build
                 sw.order = ta.order;
                 sw.out_loc = la.loc;
                 sw.compact_lds = sweep_is_batched(pc, mg, sw.one_by_one) ? 1u : 0u;
-                rc = dispatch_float<SweepLauncher>(ix, sw, nshort, sweep_lds_bytes(sw), st);
+                rc = launch_float_rows(ix, kPoolSweep, "pool_sweep_kernel launch", sw, nshort, sweep_lds_bytes(sw), st);
                 if (rc != DANN_OK) return rc;
                 gram = true;
             }
             if (!gram) {
-                rc = dispatch<BackLauncher>(ix, bs, bs.nseg, pool_lds_layout(bs.pcap, pc.pruned_degree).total, st);
+                rc = launch_rows(ix, kBackedge, "backedge_kernel launch", bs, bs.nseg, pool_lds_layout(bs.pcap, pc.pruned_degree).total, st);
                 if (rc != DANN_OK) return rc;
             }
         }
@@ -2798,7 +2781,7 @@ int32_t prune_pools_into_rows(dann_index* idx, const dann_build_config& cfg, con
     pa.into_rows = 1;
     const bool want_gram = prune_pools_use_gram(idx);
     const size_t lds = pool_lds_layout(stride, pc.pruned_degree).total;
-    if (!want_gram) return dispatch<PoolLauncher>(ix, pa, m, lds, st);
+    if (!want_gram) return launch_rows(ix, kPoolPrune, "pool_prune_kernel launch", pa, m, lds, st);
     uint32_t mg = idx->dbg_u32(DANN_DBG_GRAM_COLS, 96u);
     mg = std::min<uint32_t>(std::max<uint32_t>((mg + 31u) & ~31u, 32u), 32u * kTileColBlocks);
     const uint32_t ng = std::max<uint32_t>(mg, std::min<uint32_t>(32u * kTileRowBlocks, stride));
@@ -2809,7 +2792,7 @@ int32_t prune_pools_into_rows(dann_index* idx, const dann_build_config& cfg, con
     so.sid = s.g_sid.as<uint32_t>();
     so.sd = s.g_sd.as<float>();
     so.sn = s.g_sn.as<uint32_t>();
-    rc = dispatch_float<SortLauncher>(ix, so, m, lds, st);
+    rc = launch_float_rows(ix, kPoolSort, "pool_sort_kernel launch", so, m, lds, st);
     if (rc != DANN_OK) return rc;
     TileArgs ta;
     ta.ix = ix;
@@ -2842,7 +2825,7 @@ int32_t prune_pools_into_rows(dann_index* idx, const dann_build_config& cfg, con
     sw.order = ta.order;
     sw.out_loc = d_locs;
     sw.compact_lds = sweep_is_batched(pc, mg, sw.one_by_one) ? 1u : 0u;
-    rc = dispatch_float<SweepLauncher>(ix, sw, m, sweep_lds_bytes(sw), st);
+    rc = launch_float_rows(ix, kPoolSweep, "pool_sweep_kernel launch", sw, m, sweep_lds_bytes(sw), st);
     if (rc != DANN_OK) return rc;
     *used_gram = true;
     return DANN_OK;
@@ -3179,7 +3162,7 @@ int32_t dann_prune_batch(dann_index* idx, const dann_build_config* cfg, const ui
     pa.out_stride = ostride;
     pa.err = derr.as<uint32_t>();
     const size_t lds = pool_lds_layout(pa.pcap, pa.cfg.pruned_degree).total;
-    rc = dispatch<PoolLauncher>(pa.ix, pa, n, lds, st);
+    rc = launch_rows(pa.ix, kPoolPrune, "pool_prune_kernel launch", pa, n, lds, st);
     if (rc != DANN_OK) return rc;
     DANN_HIP(hipMemcpyAsync(out_adj, dout.p, (size_t)n * ostride * 4, hipMemcpyDeviceToHost, st));
     DANN_HIP(hipStreamSynchronize(st));

@@ -259,7 +259,7 @@ __global__ __launch_bounds__(kWave) void cons_gather_kernel(ConsGatherArgs a) {
     }
 }
 
-DANN_LAUNCHER(GatherLauncher, cons_gather_kernel, ConsGatherArgs)
+constexpr auto kConsGather = [](auto r) { using R = decltype(r); return KernelOf<cons_gather_kernel<R::dt, R::op, R::norm>>{}; };
 
 __device__ __forceinline__ uint64_t select_key(float d, uint32_t pos) {  // build_kernels.hip sort_key: (distance, position)
     uint32_t u = __builtin_bit_cast(uint32_t, d + 0.0f);
@@ -586,7 +586,7 @@ int32_t dann_consolidate(dann_index* idx, const dann_build_config* cfg, const ui
         for (uint32_t lo = 0; lo < nwork; lo += chunk) {
             const uint32_t m = std::min<uint32_t>(chunk, nwork - lo);
             ga.lo = lo;
-            int32_t rc = dispatch<GatherLauncher>(ix, ga, m, lds, st);
+            int32_t rc = launch_rows(ix, kConsGather, "cons_gather_kernel launch", ga, m, lds, st);
             if (rc != DANN_OK) return rc;
             bool used_gram = false;
             if (huge) {

@@ -18,6 +18,7 @@
 
 #include "../../include/dann.h"
 #include "../../include/dann_debug.h"
+#include "row_dispatch.h"  // visit_row_op, RowSet, kNoMetric / kNoRow
 #include "search_args.h"  // IndexView, ServerView, SearchArgs, VisitedCalib
 #include "small_calls.h"
 
@@ -48,6 +49,48 @@ int32_t hip_fail(hipError_t e, const char* what);
         ::dann::set_error("internal error");                    \
         return DANN_EINVAL;                                     \
     }
+
+// visit_row_op (row_dispatch.h) for a launch site: a metric that is not defined for the row type is the same error
+// everywhere; kNoRow comes back, and the site answers a dtype outside its row set in its own words
+template <RowSet ROWS, class F>
+int32_t dispatch_row_op(int dtype, int metric, F&& f) {
+    const int32_t rc = visit_row_op<ROWS>(dtype, metric, f);
+    if (rc != kNoMetric) return rc;
+    set_error("metric %d is not defined for dtype %d", metric, dtype);
+    return DANN_EUNSUPPORTED;
+}
+
+// how a launch raises its kernel's limit of dynamic LDS past the default 64 KiB
+enum LdsRaise {
+    kLdsExact,   // to the launch's own size, on every launch that needs it
+    kLds160Once, // to the CU's 160 KiB, once per device for each instantiation
+    kLds160      // to 160 KiB, on every launch that needs it
+};
+
+// Raise the LDS limit, launch, check.  `what` is the text of a failed launch's error.
+template <auto Kern, LdsRaise RAISE = kLdsExact, class... Args>
+int32_t launch_kernel(const char* what, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Args&... args) {
+    if (lds > 64 * 1024) {
+        const void* fn = reinterpret_cast<const void*>(Kern);
+        if constexpr (RAISE == kLdsExact) {
+            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute");
+        } else {
+            static bool raised[64] = {};  // (one per instantiation: Kern is a template argument)
+            int dev = 0;
+            if (RAISE == kLds160Once) (void)hipGetDevice(&dev);
+            if (RAISE == kLds160 || dev < 0 || dev >= 64 || !raised[dev]) {
+                hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+                if (RAISE == kLds160Once && dev >= 0 && dev < 64) raised[dev] = true;
+            }
+        }
+    }
+    hipLaunchKernelGGL(Kern, grid, block, lds, stream, args...);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, what);
+    return DANN_OK;
+}
 
 struct KernelClock {
     double total_ms = 0.0;

@@ -179,38 +179,8 @@ int32_t launch_rerank_t(const IndexView& ix, const void* q, uint32_t nq, const u
     while (pcap < stride) pcap <<= 1;
     const bool is_int = Scheme<DT, OP, false>::kInt;
     const size_t lds = (size_t)pcap * 16 + (((is_int ? int_query_slot_bytes(DT, ix.qbytes) : ix.dim * 4u) + 15u) & ~15u);
-    auto kern = rerank_kernel<DT, OP, NORM>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute");
-    }
-    hipLaunchKernelGGL(kern, dim3(nq), dim3(kWave), lds, stream, ix, q, cand, stride, k, oi, od);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "rerank_kernel launch");
-    return DANN_OK;
-}
-
-template <int DT>
-int32_t launch_rerank_dt(const IndexView& ix, const void* q, uint32_t nq, const uint32_t* cand, uint32_t stride,
-                         uint32_t k, uint32_t* oi, float* od, hipStream_t stream) {
-    int op;
-    bool norm;
-    if (!resolve_metric(ix.dtype, ix.metric, &op, &norm)) return DANN_EUNSUPPORTED;
-    if (op == OP_L2) {
-        if constexpr (dt_is_sq(DT)) {
-            if (norm) return launch_rerank_t<DT, OP_L2, true>(ix, q, nq, cand, stride, k, oi, od, stream);
-        }
-        return launch_rerank_t<DT, OP_L2, false>(ix, q, nq, cand, stride, k, oi, od, stream);
-    }
-    if (op == OP_IP) {
-        if constexpr (DT == DT_F32 || DT == DT_F16 || dt_is_mm(DT)) {
-            if (norm) return launch_rerank_t<DT, OP_IP, true>(ix, q, nq, cand, stride, k, oi, od, stream);
-        }
-        return launch_rerank_t<DT, OP_IP, false>(ix, q, nq, cand, stride, k, oi, od, stream);
-    }
-    if constexpr (!dt_is_sq(DT)) return launch_rerank_t<DT, OP_COS, false>(ix, q, nq, cand, stride, k, oi, od, stream);
-    return DANN_EUNSUPPORTED;
+    return launch_kernel<rerank_kernel<DT, OP, NORM>>("rerank_kernel launch", dim3(nq), dim3(kWave), lds, stream, ix, q, cand,
+                                                      stride, k, oi, od);
 }
 
 // pair i: rows xa[i], yb[i] given as byte pointers base + id*stride (stored rows) or
@@ -246,59 +216,19 @@ int32_t launch_pairs_t(const uint8_t* xb, const uint8_t* yb, uint64_t xs, uint64
     constexpr int G = Scheme<DT, OP, true>::G;
     const uint64_t threads = (uint64_t)n * G;
     const uint32_t blocks = (uint32_t)((threads + 255) / 256);
-    hipLaunchKernelGGL((pair_kernel<DT, OP, NORM>), dim3(blocks), dim3(256), 0, stream, xb, yb, xs, ys, a, b, n, dim,
-                       sqp, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "pair_kernel launch");
-    return DANN_OK;
+    return launch_kernel<pair_kernel<DT, OP, NORM>>("pair_kernel launch", dim3(blocks), dim3(256), 0, stream, xb, yb, xs, ys, a,
+                                                    b, n, dim, sqp, out);
 }
 
-template <int DT>
-int32_t launch_pairs_dt(int32_t metric, const uint8_t* xb, const uint8_t* yb, uint64_t xs, uint64_t ys,
-                        const uint32_t* a, const uint32_t* b, uint32_t n, uint32_t dim, SqParams sqp, float* out,
-                        hipStream_t stream) {
-    int op;
-    bool norm;
-    if (!resolve_metric(DT, metric, &op, &norm)) {
-        set_error("metric %d is not defined for dtype %d", metric, DT);
-        return DANN_EUNSUPPORTED;
-    }
-    if (op == OP_L2) {
-        if constexpr (dt_is_sq(DT)) {
-            if (norm) return launch_pairs_t<DT, OP_L2, true>(xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
-        }
-        return launch_pairs_t<DT, OP_L2, false>(xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
-    }
-    if (op == OP_IP) {
-        if constexpr (DT == DT_F32 || DT == DT_F16 || dt_is_mm(DT)) {
-            if (norm) return launch_pairs_t<DT, OP_IP, true>(xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
-        }
-        return launch_pairs_t<DT, OP_IP, false>(xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
-    }
-    if constexpr (!dt_is_sq(DT)) return launch_pairs_t<DT, OP_COS, false>(xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
-    return DANN_EUNSUPPORTED;
-}
-
-int32_t launch_pairs_any(int32_t dtype, int32_t metric, const uint8_t* xb, const uint8_t* yb, uint64_t xs, uint64_t ys,
+int32_t launch_pairs_rows(int32_t dtype, int32_t metric, const uint8_t* xb, const uint8_t* yb, uint64_t xs, uint64_t ys,
                          const uint32_t* a, const uint32_t* b, uint32_t n, uint32_t dim, SqParams sqp, float* out,
                          hipStream_t stream) {
     if (n == 0) return DANN_OK;
-    switch (dtype) {
-        case DT_F32: return launch_pairs_dt<DT_F32>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
-        case DT_F16: return launch_pairs_dt<DT_F16>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
-        case DT_U8: return launch_pairs_dt<DT_U8>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
-        case DT_I8: return launch_pairs_dt<DT_I8>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
-        case DT_SQ8: return launch_pairs_dt<DT_SQ8>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
-        case DT_SQ4: return launch_pairs_dt<DT_SQ4>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
-        case DT_SQ1: return launch_pairs_dt<DT_SQ1>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
-        case DT_SPH1: return launch_pairs_dt<DT_SPH1>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
-        case DT_SPH2: return launch_pairs_dt<DT_SPH2>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
-        case DT_SPH4: return launch_pairs_dt<DT_SPH4>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
-        case DT_MM1: return launch_pairs_dt<DT_MM1>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
-        case DT_MM2: return launch_pairs_dt<DT_MM2>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
-        case DT_MM4: return launch_pairs_dt<DT_MM4>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
-        case DT_MM8: return launch_pairs_dt<DT_MM8>(metric, xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
-    }
+    const int32_t rc = dispatch_row_op<kRowsStored>(dtype, metric, [&](auto r) {
+        using R = decltype(r);
+        return launch_pairs_t<R::dt, R::op, R::norm>(xb, yb, xs, ys, a, b, n, dim, sqp, out, stream);
+    });
+    if (rc != kNoRow) return rc;
     set_error("bad dtype %d", dtype);
     return DANN_EINVAL;
 }
@@ -308,39 +238,8 @@ int32_t launch_eb_t(const IndexView& ix, const void* q, uint32_t nq, uint32_t ch
                     const uint64_t* offsets, float* out, hipStream_t stream) {
     const bool is_int = Scheme<DT, OP, false>::kInt;
     size_t lds = ((is_int ? int_query_slot_bytes(DT, ix.qbytes) : ix.dim * 4u) + 15u) & ~15u;
-    hipLaunchKernelGGL((expand_beam_kernel<DT, OP, NORM, DIM>), dim3(nq, chunks), dim3(kWave), lds, stream, ix, q, ids,
-                       offsets, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "expand_beam_kernel launch");
-    return DANN_OK;
-}
-
-template <int DT>
-int32_t launch_eb_dt(const IndexView& ix, const void* q, uint32_t nq, uint32_t chunks, const uint32_t* ids,
-                     const uint64_t* offsets, float* out, hipStream_t stream) {
-    int op;
-    bool norm;
-    if (!resolve_metric(ix.dtype, ix.metric, &op, &norm)) {
-        set_error("metric %d is not defined for dtype %d", ix.metric, ix.dtype);
-        return DANN_EUNSUPPORTED;
-    }
-    if (op == OP_L2) {
-        if constexpr (DT == DT_F32) {
-            if (ix.dim == 128) return launch_eb_t<DT, OP_L2, false, 128>(ix, q, nq, chunks, ids, offsets, out, stream);
-        }
-        if constexpr (dt_is_sq(DT)) {
-            if (norm) return launch_eb_t<DT, OP_L2, true, 0>(ix, q, nq, chunks, ids, offsets, out, stream);
-        }
-        return launch_eb_t<DT, OP_L2, false, 0>(ix, q, nq, chunks, ids, offsets, out, stream);
-    }
-    if (op == OP_IP) {
-        if constexpr (DT == DT_F32 || DT == DT_F16 || dt_is_mm(DT)) {
-            if (norm) return launch_eb_t<DT, OP_IP, true, 0>(ix, q, nq, chunks, ids, offsets, out, stream);
-        }
-        return launch_eb_t<DT, OP_IP, false, 0>(ix, q, nq, chunks, ids, offsets, out, stream);
-    }
-    if constexpr (!dt_is_sq(DT)) return launch_eb_t<DT, OP_COS, false, 0>(ix, q, nq, chunks, ids, offsets, out, stream);
-    return DANN_EUNSUPPORTED;
+    return launch_kernel<expand_beam_kernel<DT, OP, NORM, DIM>>("expand_beam_kernel launch", dim3(nq, chunks), dim3(kWave), lds,
+                                                                stream, ix, q, ids, offsets, out);
 }
 
 }  // namespace
@@ -354,23 +253,15 @@ int32_t launch_expand_beam(const IndexView& ix, const void* d_queries, uint32_t 
         set_error("id list too long for one launch (%llu ids)", (unsigned long long)max_len);
         return DANN_EUNSUPPORTED;
     }
-    switch (ix.dtype) {
-        case DT_F32: return launch_eb_dt<DT_F32>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
-        case DT_F16: return launch_eb_dt<DT_F16>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
-        case DT_U8: return launch_eb_dt<DT_U8>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
-        case DT_I8: return launch_eb_dt<DT_I8>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
-        case DT_SQ8: return launch_eb_dt<DT_SQ8>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
-        case DT_SQ4: return launch_eb_dt<DT_SQ4>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
-        case DT_SQ1: return launch_eb_dt<DT_SQ1>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
-        case DT_SPH1: return launch_eb_dt<DT_SPH1>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
-        case DT_SPH1T: return launch_eb_dt<DT_SPH1T>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
-        case DT_SPH2: return launch_eb_dt<DT_SPH2>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
-        case DT_SPH4: return launch_eb_dt<DT_SPH4>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
-        case DT_MM1: return launch_eb_dt<DT_MM1>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
-        case DT_MM2: return launch_eb_dt<DT_MM2>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
-        case DT_MM4: return launch_eb_dt<DT_MM4>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
-        case DT_MM8: return launch_eb_dt<DT_MM8>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
-    }
+    const int32_t rc = dispatch_row_op<kRowsQuery>(ix.dtype, ix.metric, [&](auto r) {
+        using R = decltype(r);
+        if constexpr (R::dt == DT_F32 && R::op == OP_L2 && !R::norm) {  // the one form with the row length fixed at 128
+            if (ix.dim == 128)
+                return launch_eb_t<R::dt, R::op, R::norm, 128>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
+        }
+        return launch_eb_t<R::dt, R::op, R::norm, 0>(ix, d_queries, nq, chunks, d_ids, d_offsets, d_out, stream);
+    });
+    if (rc != kNoRow) return rc;
     set_error("bad dtype %d", ix.dtype);
     return DANN_EINVAL;
 }
@@ -382,35 +273,22 @@ int32_t launch_rerank(const IndexView& ix, const void* d_queries, uint32_t nq, c
         set_error("rerank supports 1..4096 candidates per query (got %u)", stride);
         return DANN_EUNSUPPORTED;
     }
-    switch (ix.dtype) {
-        case DT_F32: return launch_rerank_dt<DT_F32>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
-        case DT_F16: return launch_rerank_dt<DT_F16>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
-        case DT_U8: return launch_rerank_dt<DT_U8>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
-        case DT_I8: return launch_rerank_dt<DT_I8>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
-        case DT_SQ8: return launch_rerank_dt<DT_SQ8>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
-        case DT_SQ4: return launch_rerank_dt<DT_SQ4>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
-        case DT_SQ1: return launch_rerank_dt<DT_SQ1>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
-        case DT_SPH1: return launch_rerank_dt<DT_SPH1>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
-        case DT_SPH1T: return launch_rerank_dt<DT_SPH1T>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
-        case DT_SPH2: return launch_rerank_dt<DT_SPH2>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
-        case DT_SPH4: return launch_rerank_dt<DT_SPH4>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
-        case DT_MM1: return launch_rerank_dt<DT_MM1>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
-        case DT_MM2: return launch_rerank_dt<DT_MM2>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
-        case DT_MM4: return launch_rerank_dt<DT_MM4>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
-        case DT_MM8: return launch_rerank_dt<DT_MM8>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
-    }
-    return DANN_EINVAL;
+    const int32_t rc = dispatch_row_op<kRowsQuery>(ix.dtype, ix.metric, [&](auto r) {
+        using R = decltype(r);
+        return launch_rerank_t<R::dt, R::op, R::norm>(ix, d_queries, nq, d_cand, stride, k, d_out_ids, d_out_d, stream);
+    });
+    return rc == kNoRow ? DANN_EINVAL : rc;
 }
 
 int32_t launch_distance_pairs(const IndexView& ix, const uint32_t* d_a, const uint32_t* d_b, uint32_t n, float* d_out,
                               hipStream_t stream) {
-    return launch_pairs_any(ix.dtype, ix.metric, ix.rows, ix.rows, ix.row_stride, ix.row_stride, d_a, d_b, n, ix.dim,
+    return launch_pairs_rows(ix.dtype, ix.metric, ix.rows, ix.rows, ix.row_stride, ix.row_stride, d_a, d_b, n, ix.dim,
                             SqParams{ix.sq_k, ix.sq_shift_norm_sq}, d_out, stream);
 }
 
 int32_t launch_distance_raw(const IndexView& ix, const void* d_x, const void* d_y, uint64_t stride, uint32_t n,
                             float* d_out, hipStream_t stream) {
-    return launch_pairs_any(ix.dtype, ix.metric, reinterpret_cast<const uint8_t*>(d_x),
+    return launch_pairs_rows(ix.dtype, ix.metric, reinterpret_cast<const uint8_t*>(d_x),
                             reinterpret_cast<const uint8_t*>(d_y), stride, stride, nullptr, nullptr, n, ix.dim,
                             SqParams{ix.sq_k, ix.sq_shift_norm_sq}, d_out, stream);
 }

@@ -231,7 +231,7 @@ __global__ __launch_bounds__(kWave) void idel_search_kernel(IdelSearchArgs a) {
     if (lane == 0) a.out_cnt[p] = nout;
 }
 
-DANN_LAUNCHER(SearchLauncher, idel_search_kernel, IdelSearchArgs)
+constexpr auto kIdelSearch = [](auto r) { using R = decltype(r); return KernelOf<idel_search_kernel<R::dt, R::op, R::norm>>{}; };
 
 struct WorkArgs {
     IndexView ix;
@@ -479,7 +479,7 @@ __global__ __launch_bounds__(kWave) void idel_edge_kernel(EdgeArgs a) {
     if (lane == 0) atomicAdd(&a.stats[3], ndist);
 }
 
-DANN_LAUNCHER(EdgeLauncher, idel_edge_kernel, EdgeArgs)
+constexpr auto kIdelEdge = [](auto r) { using R = decltype(r); return KernelOf<idel_edge_kernel<R::dt, R::op, R::norm>>{}; };
 
 // the first edge of every source: heads (unordered) and the largest number of edges of one source
 __global__ void idel_heads_kernel(const unsigned long long* keys, uint32_t E, uint32_t* heads, uint32_t* meta) {
@@ -593,7 +593,7 @@ __global__ __launch_bounds__(kWave) void idel_agg_kernel(AggArgs a) {
     }
 }
 
-DANN_LAUNCHER(AggLauncher, idel_agg_kernel, AggArgs)
+constexpr auto kIdelAgg = [](auto r) { using R = decltype(r); return KernelOf<idel_agg_kernel<R::dt, R::op, R::norm>>{}; };
 
 __global__ void idel_drop_lists_kernel(IndexView ix, const uint32_t* ids, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -667,11 +667,6 @@ struct CallBuf {
         return reinterpret_cast<T*>(p);
     }
 };
-
-hipError_t set_lds(const void* kern, size_t lds) {
-    if (lds <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
 
 int32_t check_cfg(const dann_index* idx, const dann_build_config* cfg, const char* what) {
     if (idx->cfg.dtype == DT_PQ) {
@@ -848,7 +843,7 @@ int32_t dann_inplace_delete(dann_index* idx, const dann_build_config* cfg, const
                 const uint32_t m = std::min(schunk, nu - lo);
                 sa.lo = lo;
                 DANN_HIP(hipMemsetAsync(d_vis.p, 0, (size_t)m * words * 4, st));
-                if (int32_t rc = dispatch<SearchLauncher>(ix, sa, m, lds, st)) return rc;
+                if (int32_t rc = launch_rows(ix, kIdelSearch, "idel_search_kernel launch", sa, m, lds, st)) return rc;
             }
         }
         WorkArgs wa;
@@ -906,7 +901,7 @@ int32_t dann_inplace_delete(dann_index* idx, const dann_build_config* cfg, const
         ea.stats = stats;
         ea.err = meta + 3;
         const size_t edge_lds = (size_t)pow2_at_least(rcap) * 8 + rust_order::kKeyWorkBytes + (size_t)3 * rcap * 4;
-        if (int32_t rc = dispatch<EdgeLauncher>(ix, ea, nu, edge_lds, st)) return rc;
+        if (int32_t rc = launch_rows(ix, kIdelEdge, "idel_edge_kernel launch", ea, nu, edge_lds, st)) return rc;
         DANN_HIP(hipMemcpyAsync(&E, meta + 0, 4, hipMemcpyDeviceToHost, st));
         DANN_HIP(hipStreamSynchronize(st));
         E = std::min(E, ecap);
@@ -972,7 +967,7 @@ int32_t dann_inplace_delete(dann_index* idx, const dann_build_config* cfg, const
         for (uint32_t lo = 0; lo < nsrc; lo += chunk) {
             const uint32_t m = std::min(chunk, nsrc - lo);
             ga.lo = lo;
-            if (int32_t rc = dispatch<AggLauncher>(ix, ga, m, (size_t)pcap * 4, st)) return rc;
+            if (int32_t rc = launch_rows(ix, kIdelAgg, "idel_agg_kernel launch", ga, m, (size_t)pcap * 4, st)) return rc;
             bool used_gram = false;
             if (int32_t rc = prune_pools_into_rows(idx, *cfg, ga.locs, ga.pool_ids, ga.pool_d, ga.counts, pcap, m, &used_gram))
                 return rc;
@@ -1043,9 +1038,7 @@ int32_t dann_drop_deleted_neighbors(dann_index* idx, const dann_build_config* cf
     DropArgs da{ix, idx->d_deleted, ids ? d_ids.as<uint32_t>() : nullptr, only_orphans, cfg->pruned_degree,
                 d_kinds.as<uint8_t>()};
     const size_t lds = (size_t)ix.max_degree * 4;
-    DANN_HIP(set_lds(reinterpret_cast<const void*>(idel_drop_kernel), lds));
-    hipLaunchKernelGGL(idel_drop_kernel, dim3(m), dim3(kWave), lds, st, da, m);
-    DANN_HIP(hipGetLastError());
+    if (int32_t rc = launch_kernel<idel_drop_kernel>("hipGetLastError()", dim3(m), dim3(kWave), lds, st, da, m)) return rc;
     std::vector<uint8_t> h_kinds(out_kind ? m : 0);
     if (out_kind) DANN_HIP(hipMemcpyAsync(h_kinds.data(), d_kinds.p, m, hipMemcpyDeviceToHost, st));
     DANN_HIP(hipStreamSynchronize(st));

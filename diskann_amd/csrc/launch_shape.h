@@ -92,7 +92,7 @@ inline bool plain_mode(const SearchArgs& a) {
 }
 
 // does a team instantiation exist for this launch?  (launch_one: plain mode, a fixed-length kernel -- 128-element rows
-// of the metric's specialised form --, at most 256 queue entries, not PQ rows; launch_dt's case analysis)
+// of the metric's specialised form --, at most 256 queue entries, not PQ rows; row_dispatch.h search_dim128_defined)
 inline bool team_shape(const SearchArgs& a) {
     int op;
     bool norm;

@@ -311,57 +311,15 @@ int32_t launch_paged_t(const PagedArgs& a, hipStream_t stream) {
     const bool is_int = Scheme<DT, OP, false>::kInt;
     const uint32_t rc = (a.ix.max_degree + 63u) & ~63u;
     const size_t lds = (size_t)rc * 8 + (((is_int ? int_query_slot_bytes(DT, a.ix.qbytes) : a.ix.dim * 4u) + 15u) & ~15u);
-    auto kern = paged_kernel<DT, OP, NORM>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute");
-    }
-    hipLaunchKernelGGL(kern, dim3(a.nq), dim3(kWave), lds, stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "paged_kernel launch");
-    return DANN_OK;
-}
-
-template <int DT>
-int32_t launch_paged_dt(const PagedArgs& a, hipStream_t stream) {
-    int op;
-    bool norm;
-    if (!resolve_metric(a.ix.dtype, a.ix.metric, &op, &norm)) return DANN_EUNSUPPORTED;
-    if (op == OP_L2) {
-        if constexpr (dt_is_sq(DT)) {
-            if (norm) return launch_paged_t<DT, OP_L2, true>(a, stream);
-        }
-        return launch_paged_t<DT, OP_L2, false>(a, stream);
-    }
-    if (op == OP_IP) {
-        if constexpr (DT == DT_F32 || DT == DT_F16 || dt_is_mm(DT)) {
-            if (norm) return launch_paged_t<DT, OP_IP, true>(a, stream);
-        }
-        return launch_paged_t<DT, OP_IP, false>(a, stream);
-    }
-    if constexpr (!dt_is_sq(DT)) return launch_paged_t<DT, OP_COS, false>(a, stream);
-    return DANN_EUNSUPPORTED;
+    return launch_kernel<paged_kernel<DT, OP, NORM>>("paged_kernel launch", dim3(a.nq), dim3(kWave), lds, stream, a);
 }
 
 int32_t launch_paged(const PagedArgs& a, hipStream_t stream) {
-    switch (a.ix.dtype) {
-        case DT_F32: return launch_paged_dt<DT_F32>(a, stream);
-        case DT_F16: return launch_paged_dt<DT_F16>(a, stream);
-        case DT_U8: return launch_paged_dt<DT_U8>(a, stream);
-        case DT_I8: return launch_paged_dt<DT_I8>(a, stream);
-        case DT_SQ8: return launch_paged_dt<DT_SQ8>(a, stream);
-        case DT_SQ4: return launch_paged_dt<DT_SQ4>(a, stream);
-        case DT_SQ1: return launch_paged_dt<DT_SQ1>(a, stream);
-        case DT_SPH1: return launch_paged_dt<DT_SPH1>(a, stream);
-        case DT_SPH1T: return launch_paged_dt<DT_SPH1T>(a, stream);
-        case DT_SPH2: return launch_paged_dt<DT_SPH2>(a, stream);
-        case DT_SPH4: return launch_paged_dt<DT_SPH4>(a, stream);
-        case DT_MM1: return launch_paged_dt<DT_MM1>(a, stream);
-        case DT_MM2: return launch_paged_dt<DT_MM2>(a, stream);
-        case DT_MM4: return launch_paged_dt<DT_MM4>(a, stream);
-        case DT_MM8: return launch_paged_dt<DT_MM8>(a, stream);
-    }
+    const int32_t rc = dispatch_row_op<kRowsQuery>(a.ix.dtype, a.ix.metric, [&](auto r) {
+        using R = decltype(r);
+        return launch_paged_t<R::dt, R::op, R::norm>(a, stream);
+    });
+    if (rc != kNoRow) return rc;
     set_error("paged search is not defined for dtype %d", a.ix.dtype);
     return DANN_EUNSUPPORTED;
 }

@@ -31,67 +31,24 @@ __device__ void fill_list_distances(const IndexView& ix, uint32_t loc, uint32_t*
     }
 }
 
-// Launcher<DT, OP, NORM>::run for the index's row type and metric (DANN_LAUNCHER below defines a Launcher per kernel)
-template <template <int, int, bool> class Launcher, class Args>
-int32_t dispatch(const IndexView& ix, const Args& a, uint32_t grid, size_t lds, hipStream_t stream) {
-    int op;
-    bool norm;
-    if (!resolve_metric(ix.dtype, ix.metric, &op, &norm)) {
-        set_error("metric %d is not defined for dtype %d", ix.metric, ix.dtype);
-        return DANN_EUNSUPPORTED;
-    }
-#define DANN_CASE(DT)                                                                                  \
-    case DT:                                                                                           \
-        if (op == OP_L2) {                                                                             \
-            if constexpr (dt_is_sq(DT)) {                                                              \
-                if (norm) return Launcher<DT, OP_L2, true>::run(a, grid, lds, stream);                 \
-            }                                                                                          \
-            return Launcher<DT, OP_L2, false>::run(a, grid, lds, stream);                              \
-        }                                                                                              \
-        if (op == OP_IP) {                                                                             \
-            if constexpr (DT == DT_F32 || DT == DT_F16 || dt_is_mm(DT)) {                              \
-                if (norm) return Launcher<DT, OP_IP, true>::run(a, grid, lds, stream);                 \
-            }                                                                                          \
-            return Launcher<DT, OP_IP, false>::run(a, grid, lds, stream);                              \
-        }                                                                                              \
-        if constexpr (!dt_is_sq(DT)) return Launcher<DT, OP_COS, false>::run(a, grid, lds, stream);     \
-        return DANN_EUNSUPPORTED;
-    switch (ix.dtype) {
-        DANN_CASE(DT_F32)
-        DANN_CASE(DT_F16)
-        DANN_CASE(DT_U8)
-        DANN_CASE(DT_I8)
-        DANN_CASE(DT_SQ8)
-        DANN_CASE(DT_SQ4)
-        DANN_CASE(DT_SQ1)
-        DANN_CASE(DT_SPH4)
-        DANN_CASE(DT_SPH2)
-        DANN_CASE(DT_SPH1)
-        DANN_CASE(DT_MM8)
-        DANN_CASE(DT_MM4)
-        DANN_CASE(DT_MM2)
-        DANN_CASE(DT_MM1)
-    }
-#undef DANN_CASE
+// A row kernel's instantiation as a type.  The translation units name each kernel template once, in a generic lambda
+// from a RowOp to its KernelOf, e.g.
+//     constexpr auto kPoolPrune = [](auto r) { using R = decltype(r); return KernelOf<pool_prune_kernel<R::dt, R::op, R::norm>>{}; };
+template <auto Kern>
+struct KernelOf {
+    static constexpr auto fn = Kern;
+};
+
+// launch `kernel`'s instantiation for the index's row type and metric, one wavefront per block, with `a` as its argument
+template <class Kernel, class Args>
+int32_t launch_rows(const IndexView& ix, Kernel kernel, const char* what, const Args& a, uint32_t grid, size_t lds,
+                    hipStream_t stream) {
+    const int32_t rc = dispatch_row_op<kRowsStored>(ix.dtype, ix.metric, [&](auto r) {
+        return launch_kernel<decltype(kernel(r))::fn>(what, dim3(grid), dim3(kWave), lds, stream, a);
+    });
+    if (rc != kNoRow) return rc;
     set_error("bad dtype %d", ix.dtype);
     return DANN_EINVAL;
 }
-
-#define DANN_LAUNCHER(NAME, KERNEL, ARGS)                                                          \
-    template <int DT, int OP, bool NORM>                                                           \
-    struct NAME {                                                                                  \
-        static int32_t run(const ARGS& a, uint32_t grid, size_t lds, hipStream_t stream) {         \
-            auto kern = KERNEL<DT, OP, NORM>;                                                      \
-            if (lds > 64 * 1024) {                                                                 \
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),            \
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-                if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute");                    \
-            }                                                                                      \
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(kWave), lds, stream, a);                     \
-            hipError_t e = hipGetLastError();                                                      \
-            if (e != hipSuccess) return hip_fail(e, #KERNEL " launch");                            \
-            return DANN_OK;                                                                        \
-        }                                                                                          \
-    };
 }  // namespace
 }  // namespace dann

@@ -259,66 +259,16 @@ __global__ __launch_bounds__(kWave) void diverse_search_kernel(DiverseArgs a) {
 
 template <int DT, int OP, bool NORM>
 int32_t launch_dv(const DiverseArgs& a, size_t lds, hipStream_t st) {
-    auto kern = diverse_search_kernel<DT, OP, NORM>;
-    if (lds > 64 * 1024) {
-        static bool raised[64] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64 || !raised[dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-            if (dev >= 0 && dev < 64) raised[dev] = true;
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3(a.nq), dim3(kWave), lds, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "diverse_search_kernel launch");
-    return DANN_OK;
+    return launch_kernel<diverse_search_kernel<DT, OP, NORM>, kLds160Once>("diverse_search_kernel launch", dim3(a.nq), dim3(kWave),
+                                                                            lds, st, a);
 }
 
-template <int DT>
-int32_t launch_dv_dt(const DiverseArgs& a, size_t lds, hipStream_t st) {
-    int op;
-    bool norm;
-    if (!resolve_metric(a.ix.dtype, a.ix.metric, &op, &norm)) {
-        set_error("metric %d is not defined for dtype %d", a.ix.metric, a.ix.dtype);
-        return DANN_EUNSUPPORTED;
-    }
-    if (op == OP_L2) {
-        if constexpr (dt_is_sq(DT)) {
-            if (norm) return launch_dv<DT, OP_L2, true>(a, lds, st);
-        }
-        return launch_dv<DT, OP_L2, false>(a, lds, st);
-    }
-    if (op == OP_IP) {
-        if constexpr (DT == DT_F32 || DT == DT_F16 || dt_is_mm(DT)) {
-            if (norm) return launch_dv<DT, OP_IP, true>(a, lds, st);
-        }
-        return launch_dv<DT, OP_IP, false>(a, lds, st);
-    }
-    if constexpr (!dt_is_sq(DT)) return launch_dv<DT, OP_COS, false>(a, lds, st);
-    return DANN_EUNSUPPORTED;
-}
-
-int32_t launch_dv_any(const DiverseArgs& a, size_t lds, hipStream_t st) {
-    switch (a.ix.dtype) {
-        case DT_F32: return launch_dv_dt<DT_F32>(a, lds, st);
-        case DT_F16: return launch_dv_dt<DT_F16>(a, lds, st);
-        case DT_U8: return launch_dv_dt<DT_U8>(a, lds, st);
-        case DT_I8: return launch_dv_dt<DT_I8>(a, lds, st);
-        case DT_SQ8: return launch_dv_dt<DT_SQ8>(a, lds, st);
-        case DT_SQ4: return launch_dv_dt<DT_SQ4>(a, lds, st);
-        case DT_SQ1: return launch_dv_dt<DT_SQ1>(a, lds, st);
-        case DT_SPH1: return launch_dv_dt<DT_SPH1>(a, lds, st);
-        case DT_SPH1T: return launch_dv_dt<DT_SPH1T>(a, lds, st);
-        case DT_SPH2: return launch_dv_dt<DT_SPH2>(a, lds, st);
-        case DT_SPH4: return launch_dv_dt<DT_SPH4>(a, lds, st);
-        case DT_MM1: return launch_dv_dt<DT_MM1>(a, lds, st);
-        case DT_MM2: return launch_dv_dt<DT_MM2>(a, lds, st);
-        case DT_MM4: return launch_dv_dt<DT_MM4>(a, lds, st);
-        case DT_MM8: return launch_dv_dt<DT_MM8>(a, lds, st);
-    }
+int32_t launch_dv_rows(const DiverseArgs& a, size_t lds, hipStream_t st) {
+    const int32_t rc = dispatch_row_op<kRowsQuery>(a.ix.dtype, a.ix.metric, [&](auto r) {
+        using R = decltype(r);
+        return launch_dv<R::dt, R::op, R::norm>(a, lds, st);
+    });
+    if (rc != kNoRow) return rc;
     set_error("diverse search: rows of dtype %d are not supported", a.ix.dtype);
     return DANN_EUNSUPPORTED;
 }
@@ -387,7 +337,7 @@ int32_t diverse_search_device(dann_index* idx, hipStream_t st, const void* d_que
         }
     } ev{e0, e1};
     DANN_HIP(hipEventRecord(e0, st));
-    if (int32_t rc = launch_dv_any(a, lds, st)) return rc;
+    if (int32_t rc = launch_dv_rows(a, lds, st)) return rc;
     DANN_HIP(hipEventRecord(e1, st));
     std::vector<dann_search_stats> stats(nq);
     DANN_HIP(hipMemcpyAsync(stats.data(), d_stats, (size_t)nq * sizeof(dann_search_stats), hipMemcpyDeviceToHost, st));
@@ -443,7 +393,7 @@ int32_t diverse_search_device(dann_index* idx, hipStream_t st, const void* d_que
             b.qmap = d_map + o;
             b.nq = (uint32_t)std::min<size_t>(chunk, failed.size() - o);
             DANN_HIP(hipEventRecord(e0, st));
-            if (int32_t rc = launch_dv_any(b, blds, st)) return rc;
+            if (int32_t rc = launch_dv_rows(b, blds, st)) return rc;
             DANN_HIP(hipEventRecord(e1, st));
             DANN_HIP(hipStreamSynchronize(st));
             float m2 = 0.f;

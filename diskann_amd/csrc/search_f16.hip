@@ -4,6 +4,6 @@
 
 namespace dann {
 int32_t launch_search_f16(const SearchArgs& a, uint32_t qcap, size_t lds, hipStream_t stream, int* regs_out) {
-    return launch_dt<DT_F16>(a, qcap, lds, stream, regs_out);
+    return launch_row_type<DT_F16>(a, qcap, lds, stream, regs_out);
 }
 }  // namespace dann

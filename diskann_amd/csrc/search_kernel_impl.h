@@ -2476,7 +2476,7 @@ int32_t launch_one(const SearchArgs& a, size_t lds, hipStream_t stream, int* reg
         set_error("internal: 16-bit visited table requested for a kernel that has none");
         return DANN_EINTERNAL;
     }
-    auto kern = beam_search_kernel<DT, OP, NORM, QS, DIM, MODE, LOOP, TEAM, HT16>;
+    constexpr auto kern = beam_search_kernel<DT, OP, NORM, QS, DIM, MODE, LOOP, TEAM, HT16>;
     if (regs_out) {  // query only: VGPRs of the instantiation this launch would use
         hipFuncAttributes attr;
         hipError_t e = hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(kern));
@@ -2484,22 +2484,8 @@ int32_t launch_one(const SearchArgs& a, size_t lds, hipStream_t stream, int* reg
         *regs_out = attr.numRegs;
         return DANN_OK;
     }
-    if (lds > 64 * 1024) {  // raise the dynamic LDS limit of this instantiation once per device (160 KiB per CU)
-        static bool raised[64] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64 || !raised[dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-            if (dev >= 0 && dev < 64) raised[dev] = true;
-        }
-    }
     const uint32_t grid = LOOP == 2 ? a.srv.workers + 1u : LOOP == 1 ? a.grid : a.nq;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kWave * TEAM), lds, stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "beam_search_kernel launch");
-    return DANN_OK;
+    return launch_kernel<kern, kLds160Once>("beam_search_kernel launch", dim3(grid), dim3(kWave * TEAM), lds, stream, a);
 }
 
 template <int DT, int OP, bool NORM, int DIM, int MODE>
@@ -2521,55 +2507,18 @@ int32_t launch_qs(const SearchArgs& a, uint32_t qcap, size_t lds, hipStream_t st
     return launch_qs2<DT, OP, NORM, DIM, kModeGeneral>(a, qcap, lds, stream, regs_out);
 }
 
+// every beam_search_kernel instantiation of one row type: the translation units search_<type>.hip each hold one
 template <int DT>
-int32_t launch_dt(const SearchArgs& a, uint32_t qcap, size_t lds, hipStream_t stream, int* regs_out) {
-    int op;
-    bool norm;
-    if (!resolve_metric(a.ix.dtype, a.ix.metric, &op, &norm)) {
-        set_error("metric %d is not defined for dtype %d", a.ix.metric, a.ix.dtype);
-        return DANN_EUNSUPPORTED;
-    }
-    if (op == OP_L2) {
-        if constexpr (DT == DT_F32 || DT == DT_F16) {
-            if (a.ix.dim == 128) return launch_qs<DT, OP_L2, false, 128>(a, qcap, lds, stream, regs_out);
+int32_t launch_row_type(const SearchArgs& a, uint32_t qcap, size_t lds, hipStream_t stream, int* regs_out) {
+    const int32_t rc = visit_metric<DT>(a.ix.metric, [&](auto r) {
+        using R = decltype(r);
+        if constexpr (search_dim128_defined(R::dt, R::op)) {
+            if (a.ix.dim == 128) return launch_qs<R::dt, R::op, R::norm, 128>(a, qcap, lds, stream, regs_out);
         }
-        if constexpr (DT == DT_SQ8) {
-            if (norm) {
-                if (a.ix.dim == 128) return launch_qs<DT, OP_L2, true, 128>(a, qcap, lds, stream, regs_out);
-                return launch_qs<DT, OP_L2, true, 0>(a, qcap, lds, stream, regs_out);
-            }
-        }
-        if constexpr (dt_is_packed(DT) && !dt_is_mm(DT)) {  // (packed rows: no team instantiations, team_shape)
-            if (norm) {
-                if (a.ix.dim == 128) return launch_qs<DT, OP_L2, true, 128>(a, qcap, lds, stream, regs_out);
-                return launch_qs<DT, OP_L2, true, 0>(a, qcap, lds, stream, regs_out);
-            }
-            if (a.ix.dim == 128) return launch_qs<DT, OP_L2, false, 128>(a, qcap, lds, stream, regs_out);
-        }
-        if constexpr (DT == DT_U8 || DT == DT_I8 || DT == DT_SQ8 || dt_is_mm(DT)) {  // 128-byte integer rows (C-int8), 128-d MinMax rows
-            if (a.ix.dim == 128) return launch_qs<DT, OP_L2, false, 128>(a, qcap, lds, stream, regs_out);
-        }
-        return launch_qs<DT, OP_L2, false, 0>(a, qcap, lds, stream, regs_out);
-    }
-    if (op == OP_IP) {
-        if constexpr (DT == DT_F32 || DT == DT_F16) {
-            if (norm) return launch_qs<DT, OP_IP, true, 0>(a, qcap, lds, stream, regs_out);
-        }
-        if constexpr (dt_is_mm(DT)) {  // (MinMaxCosineNormalized: the inner product's kernels, 1 - v)
-            if (norm) {
-                if (a.ix.dim == 128) return launch_qs<DT, OP_IP, true, 128>(a, qcap, lds, stream, regs_out);
-                return launch_qs<DT, OP_IP, true, 0>(a, qcap, lds, stream, regs_out);
-            }
-        }
-        if constexpr (DT == DT_U8 || DT == DT_I8 || dt_is_sq(DT) || dt_is_sph(DT) || dt_is_mm(DT)) {
-            if (a.ix.dim == 128) return launch_qs<DT, OP_IP, false, 128>(a, qcap, lds, stream, regs_out);
-        }
-        return launch_qs<DT, OP_IP, false, 0>(a, qcap, lds, stream, regs_out);
-    }
-    if constexpr (DT == DT_U8 || DT == DT_I8 || dt_is_sph(DT) || dt_is_mm(DT)) {
-        if (a.ix.dim == 128) return launch_qs<DT, OP_COS, false, 128>(a, qcap, lds, stream, regs_out);
-    }
-    if constexpr (!dt_is_sq(DT) && DT != DT_PQ) return launch_qs<DT, OP_COS, false, 0>(a, qcap, lds, stream, regs_out);
+        return launch_qs<R::dt, R::op, R::norm, 0>(a, qcap, lds, stream, regs_out);
+    });
+    if (rc != kNoMetric) return rc;
+    set_error("metric %d is not defined for dtype %d", a.ix.metric, a.ix.dtype);
     return DANN_EUNSUPPORTED;
 }
 

@@ -4,6 +4,6 @@
 
 namespace dann {
 int32_t launch_search_mm4(const SearchArgs& a, uint32_t qcap, size_t lds, hipStream_t stream, int* regs_out) {
-    return launch_dt<DT_MM4>(a, qcap, lds, stream, regs_out);
+    return launch_row_type<DT_MM4>(a, qcap, lds, stream, regs_out);
 }
 }  // namespace dann

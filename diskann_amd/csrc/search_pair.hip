@@ -3,12 +3,21 @@
 #include "search_pair_impl.h"
 
 namespace dann {
+// the kernel of the launch's row type, metric and pair_qe / pair_re
 int32_t launch_search_pair(const SearchArgs& a, size_t lds, hipStream_t stream) {
-    switch (a.ix.dtype) {
-        case DT_U8: return launch_pair_dt<DT_U8>(a, lds, stream);
-        case DT_I8: return launch_pair_dt<DT_I8>(a, lds, stream);
-        case DT_SQ8: return launch_pair_dt<DT_SQ8>(a, lds, stream);
-    }
+    const uint32_t grid = (a.nq + 1u) / 2u, qe = pair_qe(a), re = pair_re(a);
+    const int32_t rc = dispatch_row_op<kRowsPair>(a.ix.dtype, a.ix.metric, [&](auto r) {
+        using R = decltype(r);
+#define DANN_PAIR_GO(QE, RE)                                                                                       \
+    launch_kernel<pair_search_kernel<R::dt, R::op, R::norm, QE, RE>, kLds160>("pair_search_kernel launch", dim3(grid), \
+                                                                              dim3(kWave), lds, stream, a)
+        return re == 2u ? (qe == 3u ? DANN_PAIR_GO(3, 2) : DANN_PAIR_GO(2, 2))
+             : qe == 3u ? DANN_PAIR_GO(3, 1)
+             : qe == 2u ? DANN_PAIR_GO(2, 1)
+                        : DANN_PAIR_GO(1, 1);
+#undef DANN_PAIR_GO
+    });
+    if (rc != kNoRow) return rc;
     set_error("internal: two queries per wavefront serve 128-byte integer rows");
     return DANN_EINTERNAL;
 }

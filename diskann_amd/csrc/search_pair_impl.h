@@ -545,44 +545,5 @@ __global__ __launch_bounds__(kWave) void pair_search_kernel(SearchArgs a) {
     }
 }
 
-template <int DT>
-int32_t launch_pair_dt(const SearchArgs& a, size_t lds, hipStream_t stream) {
-    int op;
-    bool norm;
-    if (!resolve_metric(a.ix.dtype, a.ix.metric, &op, &norm)) {
-        set_error("metric %d is not defined for dtype %d", a.ix.metric, a.ix.dtype);
-        return DANN_EUNSUPPORTED;
-    }
-    const uint32_t grid = (a.nq + 1u) / 2u;
-    auto go = [&](auto kern) -> int32_t {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               160 * 1024);
-            if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-        }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kWave), lds, stream, a);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "pair_search_kernel launch");
-        return DANN_OK;
-    };
-    const uint32_t qe = pair_qe(a), re = pair_re(a);
-#define DANN_PAIR_GO(OPV, NORMV)                                                                   \
-    return re == 2u ? (qe == 3u ? go(pair_search_kernel<DT, OPV, NORMV, 3, 2>)                     \
-                                : go(pair_search_kernel<DT, OPV, NORMV, 2, 2>))                    \
-         : qe == 3u ? go(pair_search_kernel<DT, OPV, NORMV, 3, 1>)                                 \
-         : qe == 2u ? go(pair_search_kernel<DT, OPV, NORMV, 2, 1>)                                 \
-                    : go(pair_search_kernel<DT, OPV, NORMV, 1, 1>)
-    if (op == OP_L2) {
-        if constexpr (DT == DT_SQ8) {
-            if (norm) DANN_PAIR_GO(OP_L2, true);
-        }
-        DANN_PAIR_GO(OP_L2, false);
-    }
-    if (op == OP_IP) DANN_PAIR_GO(OP_IP, false);
-    if constexpr (DT != DT_SQ8) DANN_PAIR_GO(OP_COS, false);
-#undef DANN_PAIR_GO
-    return DANN_EUNSUPPORTED;
-}
-
 }  // namespace
 }  // namespace dann
