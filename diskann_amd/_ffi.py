@@ -22,6 +22,7 @@ OK, EINVAL, ELENGTH, EBOUNDS, ETOOLONG, EHIP, ENOMEM, EOVERFLOW, EUNSUPPORTED, E
     0, -1, -2, -3, -4, -5, -6, -7, -8, -9, -10)
 IBC_NONE, IBC_ALL = 0, 0xFFFFFFFF
 TIE_POSITION, TIE_RUST = 0, 1  # dann_set_prune_tie_order
+MAXSIM_KERNEL, MAXSIM_REFERENCE = 0, 1  # the two orders of dann_maxsim_batch / dann_chamfer_rerank_batch
 BUILD_MFMA_BACKEDGE, BUILD_MFMA_POOL, BUILD_ROW_KERNEL_ONLY = 1, 2, 4
 CONSOLIDATE_COMPLETE, CONSOLIDATE_DELETED = 0, 1  # ConsolidateKind (dann_consolidate out_kind)
 CONSOLIDATE_DROP_DELETED = 1  # dann_consolidate flag
@@ -147,6 +148,13 @@ SYMBOLS = {
     "dann_rerank_batch": (_i32, [_vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp]),
     "dann_rerank_batch_device": (_i32, [_vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp]),
     "dann_search_record_batch": (_i32, [_vp, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp]),
+    "dann_mvset_create": (_i32, [_i32, _i32, _u32, _u32, _vp, _vp, _P(_vp)]),
+    "dann_mvset_destroy": (_i32, [_vp]),
+    "dann_mvset_info": (_i32, [_vp, _P(_i32), _P(_u32), _P(_u32), _P(_u64)]),
+    "dann_maxsim_batch": (_i32, [_vp, _i32, _vp, _vp, _u32, _vp, _u32, _vp, _vp]),
+    "dann_maxsim_batch_device": (_i32, [_vp, _i32, _vp, _vp, _u32, _vp, _u32, _vp, _vp]),
+    "dann_chamfer_rerank_batch": (_i32, [_vp, _i32, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "dann_chamfer_rerank_batch_device": (_i32, [_vp, _i32, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
     "dann_prune_batch": (_i32, [_vp, _P(BuildConfig), _vp, _u32, _vp, _vp, _vp, _i32, _vp]),
     "dann_insert_batch": (_i32, [_vp, _P(BuildConfig), _vp, _u32]),
     "dann_insert": (_i32, [_vp, _P(BuildConfig), _u32]),
@@ -235,6 +243,7 @@ SYMBOLS = {
     "dann_debug_sched_pivots": (_i32, [_vp, _vp, _u32, _P(_u32), _P(_u32), _P(_f32)]),
     "dann_debug_family_name": (C.c_char_p, [_i32]),
     "dann_debug_pq_rolling_sum_stats": (_i32, [_i32, _P(_u64), _i32]),
+    "dann_debug_mvset_kernel_time": (_i32, [_vp, _i32, _P(C.c_double), _P(_u64)]),
 }
 
 # dann_debug.h: development switches (dann_debug_set) and kernel families (dann_debug_search_families)

@@ -191,6 +191,25 @@ int32_t ensure_deleted_bitmap(dann_index* idx);
 int32_t launch_minmax_compress(int32_t bits, const float* d_x, uint32_t n, uint32_t dim, float grid_scale, uint8_t* d_out,
                                float* d_out_loss, uint32_t* d_nan_flag, hipStream_t stream);
 
+// maxsim_kernels.hip: multi-vector scores (dann_maxsim_batch, dann_chamfer_rerank_batch).  Rows of documents and of
+// queries sit at `stride` bytes, a multiple of 16, the bytes behind `dim` zero.
+constexpr uint32_t kMaxSimQueryRows = 1024, kMaxSimDim = 4096, kMaxSimCands = 4096, kMaxSimQueries = 65535;
+struct MaxSimArgs {
+    const uint8_t* drows;      // the set's rows
+    const uint64_t* doff;      // ndocs + 1 row offsets
+    uint32_t ndocs, dim, stride;
+    const uint8_t* qrows;      // the queries' rows
+    const uint32_t* qoff;      // nq + 1 row offsets
+    const uint32_t* cand;      // nq x cand_stride document ids
+    uint32_t cand_stride;
+    float* out_chamfer;        // nq x cand_stride
+    float* out_scores;         // null, or q_rows(q) floats at qoff[q] * cand_stride + c * q_rows(q)
+    uint32_t* status;          // set to 1 by a candidate id >= ndocs
+};
+int32_t launch_maxsim(int32_t dtype, int32_t order, const MaxSimArgs& a, uint32_t nq, hipStream_t stream);
+int32_t launch_chamfer_sort(const uint32_t* d_cand, const float* d_chamfer, uint32_t nq, uint32_t stride, uint32_t ndocs,
+                            uint32_t k, uint32_t* d_out_ids, float* d_out_d, uint32_t* d_out_counts, hipStream_t stream);
+
 int32_t launch_expand_beam(const IndexView& ix, const void* d_queries, uint32_t nq, const uint32_t* d_ids,
                            const uint64_t* d_offsets, uint64_t max_len, float* d_out, hipStream_t stream);
 int32_t launch_rerank(const IndexView& ix, const void* d_queries, uint32_t nq, const uint32_t* d_cand, uint32_t stride,

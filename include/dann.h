@@ -722,6 +722,58 @@ int32_t dann_inplace_delete(dann_index* idx, const dann_build_config* cfg, const
 int32_t dann_drop_deleted_neighbors(dann_index* idx, const dann_build_config* cfg, const uint32_t* ids, uint32_t n,
                                     uint32_t only_orphans, int32_t* out_kind);
 
+/* ---- multi-vector (late-interaction) scores: diskann-quantization/src/multi_vector/ ------------------------------------
+ * A query and a document are small matrices of token rows (row-major, `dim` elements each, DANN_F32 or DANN_F16, query
+ * and document of one type).  MaxSim: for each query row the best inner product over the document's rows, as a
+ * similarity score (negated: smaller is better); Chamfer: their sum over the query's rows.  Two orders, because their
+ * bits differ -- the choice is the caller's and is never made by speed:
+ *   DANN_MAXSIM_KERNEL     what build_max_sim(Auto | X86_64_V3 | X86_64_V4, query).compute_max_sim(doc, scores) returns:
+ *                          ip(i, j) = one fma chain over k = 0 .. dim - 1 from +0.0 (f16 widened first, exactly),
+ *                          scores[i] = -max_j ip(i, j), the maximum from f32::MIN, the negation last (a maximum of +0.0
+ *                          gives -0.0).  Runs on the matrix cores (v_mfma_f32_32x32x2_f32 is that chain bit for bit).
+ *   DANN_MAXSIM_REFERENCE  MaxSim::evaluate / Chamfer::evaluate / MaxSimIsa::Reference: scores[i] = min_j
+ *                          InnerProduct::evaluate(q_i, d_j), the minimum from f32::MAX -- the pair function behind
+ *                          dann_distance_pairs with DANN_INNER_PRODUCT.
+ * Both: a document without rows scores f32::MAX for every query row and has Chamfer 0.0; Chamfer = the sequential f32 sum
+ * of scores[i] in query-row order from 0.0 (0.0 for a query without rows).
+ * Outside the contract: NaN or infinite inputs (the CPU's vmaxps operand rule is not reproduced), and products that
+ * underflow to -0.0 (the sign of a zero maximum is then ambiguous in the reference itself).
+ *
+ * A dann_mvset is an immutable, device-resident set of ndocs documents in CSR form: document d is rows
+ * [row_offsets[d], row_offsets[d + 1]) of `rows`; row_offsets[0] == 0, non-decreasing; documents without rows allowed.
+ * Queries are CSR too: query q is rows [q_offsets[q], q_offsets[q + 1]) of `queries`, in the set's dtype.
+ * cand_ids: nq x cand_stride document ids; entries equal to 0xFFFFFFFF are skipped, their out_chamfer and out_scores
+ * cells written as +infinity.  out_chamfer: nq x cand_stride.  out_scores: NULL, or the per-row MaxSim scores: those of
+ * (q, c) are the q_rows(q) floats at q_offsets[q] * cand_stride + c * q_rows(q).
+ * Limits: 1 <= dim <= 4096; at most 1024 rows per query; any number of rows per document; cand_stride 1 .. 4096;
+ * nq <= 65535 per call.  Beyond them: DANN_EUNSUPPORTED.
+ * Errors: DANN_EINVAL for null pointers, an order that is not a DANN_MAXSIM_*, a dtype other than DANN_F32 / DANN_F16,
+ * dim == 0, k == 0; DANN_ELENGTH for offsets that decrease or do not start at 0; DANN_EBOUNDS for a candidate id >= ndocs
+ * (found on the device instead of the read; the outputs of that call are then unspecified).
+ * The calls are host-synchronous.  The _device forms take queries, offsets, candidates and outputs on the set's device. */
+typedef struct dann_mvset dann_mvset;
+enum { DANN_MAXSIM_KERNEL = 0, DANN_MAXSIM_REFERENCE = 1 };
+int32_t dann_mvset_create(int32_t device, int32_t dtype, uint32_t dim, uint32_t ndocs, const uint64_t* row_offsets,
+                          const void* rows, dann_mvset** out);
+int32_t dann_mvset_destroy(dann_mvset* set);
+int32_t dann_mvset_info(const dann_mvset* set, int32_t* dtype, uint32_t* dim, uint32_t* ndocs, uint64_t* nrows);
+int32_t dann_maxsim_batch(const dann_mvset* set, int32_t order, const void* queries, const uint32_t* q_offsets,
+                          uint32_t nq, const uint32_t* cand_ids, uint32_t cand_stride, float* out_chamfer,
+                          float* out_scores);
+int32_t dann_maxsim_batch_device(const dann_mvset* set, int32_t order, const void* d_queries, const uint32_t* d_q_offsets,
+                                 uint32_t nq, const uint32_t* d_cand_ids, uint32_t cand_stride, float* d_out_chamfer,
+                                 float* d_out_scores);
+/* the same Chamfer scores, sorted ascending per query (equal scores keep candidate order, skipped entries dropped), the
+ * first k returned: out_ids / out_dists nq x k, padded as dann_rerank_batch pads (0xFFFFFFFF / +infinity);
+ * out_counts[q] = entries written for query q */
+int32_t dann_chamfer_rerank_batch(const dann_mvset* set, int32_t order, const void* queries, const uint32_t* q_offsets,
+                                  uint32_t nq, const uint32_t* cand_ids, uint32_t cand_stride, uint32_t k,
+                                  uint32_t* out_ids, float* out_dists, uint32_t* out_counts);
+int32_t dann_chamfer_rerank_batch_device(const dann_mvset* set, int32_t order, const void* d_queries,
+                                         const uint32_t* d_q_offsets, uint32_t nq, const uint32_t* d_cand_ids,
+                                         uint32_t cand_stride, uint32_t k, uint32_t* d_out_ids, float* d_out_dists,
+                                         uint32_t* d_out_counts);
+
 /* ABI revision of this header; bumped on any incompatible change of a signature or struct layout */
 #define DANN_ABI_VERSION 5
 int32_t dann_abi_version(void);

@@ -114,6 +114,10 @@ int32_t dann_debug_small_call_stats(dann_index* idx, uint64_t* out2);
  * their hard inputs reach the walk. */
 int32_t dann_debug_pq_rolling_sum_stats(int32_t device, uint64_t* out4, int32_t reset);
 
+/* HIP-event time (ms) and count of the scoring launches (maxsim_mfma_kernel / maxsim_rows_kernel) of a multi-vector set
+ * since its creation or the last call with reset != 0; either pointer may be null.  What scratch/maxsim_rate.py times. */
+int32_t dann_debug_mvset_kernel_time(const dann_mvset* set, int32_t reset, double* total_ms, uint64_t* launches);
+
 #ifdef __cplusplus
 }
 #endif
