@@ -12,11 +12,12 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "libdann_oracle.so")
 
-F32, F16, U8, I8, SQ8, PQ = 0, 1, 2, 3, 4, 5
+F32, F16, U8, I8, SQ8, PQ, TABLE = 0, 1, 2, 3, 4, 5, 6
 COSINE, INNER_PRODUCT, L2, COSINE_NORMALIZED = 0, 1, 2, 3
 IBC_NONE, IBC_ALL = 0, 0xFFFFFFFF
 
-NP_DTYPE = {F32: np.float32, F16: np.float16, U8: np.uint8, I8: np.int8, SQ8: np.uint8, PQ: np.uint8}
+NP_DTYPE = {F32: np.float32, F16: np.float16, U8: np.uint8, I8: np.int8, SQ8: np.uint8, PQ: np.uint8,
+            TABLE: np.uint32}
 
 
 def build(force=False):
@@ -47,6 +48,8 @@ class OrcIndex(C.Structure):
         ("pq_offsets", C.c_void_p),
         ("pq_chunks", C.c_uint32),
         ("tag_offset", C.c_uint32),
+        ("table", C.c_void_p),
+        ("table_keys", C.c_uint64),
     ]
 
 
@@ -173,7 +176,7 @@ class Index:
     """Host-side arrays in the diskann-inmem layout + the oracle's algorithms over them."""
 
     def __init__(self, dtype, metric, dim, capacity, max_degree, start_rows, row_stride=None, sq_scale=0.0,
-                 sq_shift_norm_sq=0.0, pq_pivots=None, pq_offsets=None, tags=False):
+                 sq_shift_norm_sq=0.0, pq_pivots=None, pq_offsets=None, tags=False, table=None):
         self.dtype, self.metric, self.dim = dtype, metric, int(dim)
         self.capacity, self.max_degree = int(capacity), int(max_degree)
         self.row_elems = self.dim + 4 if dtype == SQ8 else self.dim
@@ -189,6 +192,17 @@ class Index:
             self.query_dtype, self.query_elems = np.float32, self.dim
         start_rows = np.ascontiguousarray(start_rows, dtype=NP_DTYPE[dtype]).reshape(-1, self.row_elems)
         self.nstart = start_rows.shape[0]
+        # TABLE: distances come from the caller's f32 matrix (keys x slots); slot i holds key i, start points included,
+        # and keys past the slots are external queries.  table[x, y]: x is the row (first argument), y the stored slot.
+        self.table = None
+        if dtype == TABLE:
+            nslots = self.capacity + self.nstart
+            self.table = np.ascontiguousarray(table, dtype=np.float32)
+            if self.dim != 1 or self.table.ndim != 2 or self.table.shape[1] != nslots or self.table.shape[0] < nslots:
+                raise ValueError("TABLE index: dim 1 and a (keys >= slots, slots) f32 table")
+            start_rows = np.arange(self.capacity, nslots, dtype=np.uint32).reshape(-1, 1)
+        elif table is not None:
+            raise ValueError("table= belongs to a TABLE index")
         self.row_bytes = pq_chunks if dtype == PQ else layer_bytes(dtype, dim)
         self.row_stride = int(row_stride) if row_stride else self.row_bytes
         n = self.capacity + self.nstart
@@ -208,7 +222,11 @@ class Index:
         self._c = OrcIndex(dtype, metric, self.dim, self.capacity, self.nstart, self.max_degree,
                            self.row_stride, self.rows.ctypes.data, self.adj.ctypes.data, sq_scale, sq_shift_norm_sq,
                            self.pq_pivots.ctypes.data if dtype == PQ else None,
-                           self.pq_offsets.ctypes.data if dtype == PQ else None, pq_chunks, self.tag_offset)
+                           self.pq_offsets.ctypes.data if dtype == PQ else None, pq_chunks, self.tag_offset,
+                           self.table.ctypes.data if dtype == TABLE else None,
+                           self.table.shape[0] if dtype == TABLE else 0)
+        if dtype == TABLE:
+            self.set_rows(0, np.arange(self.capacity, dtype=np.uint32))
 
     # -- storage ------------------------------------------------------------
     def set_row(self, slot, vec):

@@ -381,7 +381,7 @@ inline int eff_metric(int dtype, int metric) {
     if ((dtype == ORC_U8 || dtype == ORC_I8) && metric == ORC_COSINE_NORMALIZED) return ORC_COSINE;
     return metric;
 }
-inline size_t elem_size(int dtype) { return dtype == ORC_F32 ? 4 : dtype == ORC_F16 ? 2 : 1; }
+inline size_t elem_size(int dtype) { return dtype == ORC_F32 || dtype == ORC_TABLE ? 4 : dtype == ORC_F16 ? 2 : 1; }
 inline size_t layer_bytes(int dtype, size_t dim) { return dim * elem_size(dtype) + (dtype == ORC_SQ8 ? 4 : 0); }
 inline size_t query_bytes(const orc_index* ix) { return ix->dtype == ORC_PQ ? (size_t)ix->dim * 4 : layer_bytes(ix->dtype, ix->dim); }
 
@@ -559,7 +559,19 @@ struct View {
         std::memcpy(r + 1 + cur, n, (size_t)take * 4);
         r[0] = cur + take;
     }
+    /* ORC_TABLE: a row is one u32 key; the distance of (row key, stored slot b) is table[key][b].  The FIRST argument
+     * names the table row -- the table need not be symmetric.  Out-of-range reads give NaN, never memory. */
+    uint32_t key(uint32_t id) const {
+        uint32_t k;
+        std::memcpy(&k, row(id), 4);
+        return k;
+    }
+    float table_at(uint32_t k, uint32_t b) const {
+        if (!ix->table || k >= ix->table_keys || b >= nslots()) return std::numeric_limits<float>::quiet_NaN();
+        return ix->table[(size_t)k * nslots() + b];
+    }
     float pair(uint32_t a, uint32_t b) const {
+        if (ix->dtype == ORC_TABLE) return table_at(key(a), b);
         if (ix->dtype == ORC_SQ8) return sq8_similarity(metric, row(a), row(b), ix->dim, ix->sq_scale, ix->sq_shift_norm_sq);
         return post_op(metric, pair_raw(ix->dtype, metric, row(a), row(b), ix->dim));
     }
@@ -584,6 +596,11 @@ struct QueryCtx {
         }
     }
     float eval(uint32_t id) const {
+        if (v.ix->dtype == ORC_TABLE) {
+            uint32_t k;
+            std::memcpy(&k, q, 4);
+            return v.table_at(k, id);
+        }
         if (v.ix->dtype == ORC_PQ) return orc_pq_lookup(lut.data(), v.row(id), v.ix->pq_chunks);
         if (v.ix->dtype == ORC_SQ8)
             return sq8_similarity(v.metric, (const uint8_t*)q, v.row(id), v.ix->dim, v.ix->sq_scale, v.ix->sq_shift_norm_sq);
@@ -592,6 +609,20 @@ struct QueryCtx {
         return post_op(v.metric, raw);
     }
 };
+
+/* ORC_TABLE entry check: the table is there, covers every stored slot, and the query key (when there is one) names a
+ * table row; the AVX twins read row bytes and have no table form.  0 = fine (also for every other dtype). */
+inline int32_t table_check(const orc_index* ix, const void* query, bool fast) {
+    if (!ix || ix->dtype != ORC_TABLE) return 0;
+    if (fast) return -6;
+    if (!ix->table || ix->dim != 1 || ix->row_stride < 4 || ix->table_keys < (uint64_t)ix->capacity + ix->nstart) return -5;
+    if (query) {
+        uint32_t k;
+        std::memcpy(&k, query, 4);
+        if (k >= ix->table_keys) return -5;
+    }
+    return 0;
+}
 
 struct SearchOut {
     uint32_t cmps = 0, hops = 0;
@@ -659,6 +690,7 @@ int32_t search_one(const orc_index* ix, const void* query, uint32_t l_value, uin
                    uint32_t* out_ids, float* out_dists, uint32_t* stats,
                    std::vector<std::pair<uint32_t, float>>* record, bool fast) {
     if (!ix || !query || l_value == 0 || beam_width == 0) return -1;
+    if (int32_t rc = table_check(ix, query, fast)) return rc;
     View v(ix);
     QueryCtx qc(v, query, fast);
     /* queue capacity == search_l == L + num_start_points (scratch.rs:199-207) */
@@ -904,11 +936,13 @@ float orc_f16_to_f32(uint16_t h) { return f16_to_f32(h); }
 uint16_t orc_f32_to_f16(float f) { return f32_to_f16(f); }
 
 float orc_distance(int32_t dtype, int32_t metric, const void* x, const void* y, size_t dim) {
+    if (dtype == ORC_TABLE) return std::numeric_limits<float>::quiet_NaN(); /* a key is not a vector */
     int m = eff_metric(dtype, metric);
     return post_op(m, pair_raw(dtype, m, x, y, dim));
 }
 
 float orc_query_distance(int32_t dtype, int32_t metric, const void* query, const void* row, size_t dim) {
+    if (dtype == ORC_TABLE) return std::numeric_limits<float>::quiet_NaN(); /* a key is not a vector */
     int m = eff_metric(dtype, metric);
     std::vector<float> q32;
     if (dtype == ORC_F16) {
@@ -919,6 +953,7 @@ float orc_query_distance(int32_t dtype, int32_t metric, const void* query, const
 }
 
 float orc_query_distance_fast(int32_t dtype, int32_t metric, const void* query, const void* row, size_t dim) {
+    if (dtype == ORC_TABLE) return std::numeric_limits<float>::quiet_NaN(); /* a key is not a vector */
     int m = eff_metric(dtype, metric);
     std::vector<float> q32;
     if (dtype == ORC_F16) {
@@ -931,6 +966,7 @@ float orc_query_distance_fast(int32_t dtype, int32_t metric, const void* query, 
 /* diskann-vector/src/distance/reference.rs: plain scalar loops, f32 accumulation
  * (floats), exact integers. */
 float orc_distance_scalar_ref(int32_t dtype, int32_t metric, const void* x, const void* y, size_t dim) {
+    if (dtype == ORC_TABLE) return std::numeric_limits<float>::quiet_NaN(); /* a key is not a vector */
     int m = eff_metric(dtype, metric);
     auto get = [&](const void* p, size_t i) -> float {
         switch (dtype) {
@@ -1026,6 +1062,7 @@ int32_t orc_range_search(const orc_index* ix, const void* query, uint32_t starti
                          float range_slack, uint64_t max_returned, uint32_t* out_ids, float* out_dists,
                          uint64_t out_cap, uint32_t* stats) {
     if (!ix || !query || starting_l == 0 || beam_width == 0) return -1;
+    if (int32_t rc = table_check(ix, query, false)) return rc;
     View v(ix);
     QueryCtx qc(v, query, false);
     Queue best((size_t)starting_l + ix->nstart);
@@ -1192,6 +1229,7 @@ int32_t orc_inline_filter_search(const orc_index* ix, const void* query, uint32_
                                  double adaptive_scale, uint32_t* out_ids, float* out_dists, uint32_t* stats) {
     if (!ix || !query || !filter_bits || l_value == 0 || beam_width == 0) return -1;
     if (adaptive_samples && !(adaptive_scale >= 1.0)) return -1; /* AdaptiveLSearchError */
+    if (int32_t rc = table_check(ix, query, false)) return rc;
     View v(ix);
     QueryCtx qc(v, query, false);
     Queue best((size_t)l_value + ix->nstart);
@@ -1223,6 +1261,7 @@ int32_t orc_inline_filter_search(const orc_index* ix, const void* query, uint32_
 int32_t orc_multihop_search(const orc_index* ix, const void* query, uint32_t l_value, uint32_t beam_width, uint32_t k,
                             const uint32_t* filter_bits, uint32_t* out_ids, float* out_dists, uint32_t* stats) {
     if (!ix || !query || !filter_bits || l_value == 0 || beam_width == 0) return -1;
+    if (int32_t rc = table_check(ix, query, false)) return rc;
     View v(ix);
     QueryCtx qc(v, query, false);
     Queue best((size_t)l_value + ix->nstart);
@@ -1305,6 +1344,7 @@ int32_t orc_filtered_range_search(const orc_index* ix, const void* query, uint32
                                   float range_slack, uint64_t max_returned, const uint32_t* filter_bits,
                                   uint32_t* out_ids, float* out_dists, uint64_t out_cap, uint32_t* stats) {
     if (!ix || !query || !filter_bits || starting_l == 0 || beam_width == 0) return -1;
+    if (int32_t rc = table_check(ix, query, false)) return rc;
     View v(ix);
     QueryCtx qc(v, query, false);
     Queue best((size_t)starting_l + ix->nstart);
@@ -1404,6 +1444,7 @@ struct orc_paged {
 
 orc_paged* orc_paged_begin(const orc_index* ix, const void* query, uint32_t l_value) {
     if (!ix || !query || l_value == 0) return nullptr;
+    if (table_check(ix, query, false)) return nullptr;
     orc_paged* s = new orc_paged(ix, (size_t)l_value + ix->nstart);
     s->best.auto_resizable = true;
     s->qbytes.assign((const uint8_t*)query, (const uint8_t*)query + query_bytes(ix));
@@ -1490,6 +1531,7 @@ void orc_paged_end(orc_paged* s) {
 int32_t orc_expand_beam(const orc_index* ix, const void* query, const uint32_t* ids, uint32_t n,
                         uint32_t* out_ids, float* out_dists) {
     if (!ix || !query) return -1;
+    if (int32_t rc = table_check(ix, query, false)) return rc;
     View v(ix);
     QueryCtx qc(v, query, false);
     uint32_t m = 0;
@@ -1518,6 +1560,7 @@ int32_t orc_prune_pool(const orc_index* ix, const orc_build_config* cfg, uint32_
                        float* pool_dists, uint32_t pool_n, int32_t force_saturate, uint32_t* out_neighbors,
                        uint64_t* pair_evals) {
     if (!ix || !cfg) return -1;
+    if (int32_t rc = table_check(ix, nullptr, false)) return rc;
     View v(ix);
     std::vector<PNeighbor> pool(pool_n);
     for (uint32_t i = 0; i < pool_n; ++i) pool[i] = {pool_ids[i], pool_dists[i], i};
@@ -1669,6 +1712,7 @@ double orc_bench_distance(int32_t dtype, int32_t metric, uint32_t dim, uint64_t 
  * reference's grid_insert goldens hold as insert_metrics.{set_neighbors, append_neighbors, get_neighbors} */
 int32_t orc_insert(orc_index* ix, const orc_build_config* cfg, uint32_t slot, uint64_t* counters) {
     if (!ix || !cfg || slot >= ix->capacity) return -1;
+    if (int32_t rc = table_check(ix, nullptr, false)) return rc;
     View v(ix);
     /* insert_search_accessor == search_accessor (glue.rs:932-939); beam width 1, L = l_build */
     QueryCtx qc(v, v.row(slot), false);
@@ -1695,6 +1739,7 @@ int32_t orc_insert(orc_index* ix, const orc_build_config* cfg, uint32_t slot, ui
 int32_t orc_multi_insert(orc_index* ix, const orc_build_config* cfg, const uint32_t* slots, uint32_t n,
                          uint64_t* counters) {
     if (!ix || !cfg) return -1;
+    if (int32_t rc = table_check(ix, nullptr, false)) return rc;
     View v(ix);
     struct Pending {
         uint32_t source;

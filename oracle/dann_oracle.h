@@ -36,7 +36,13 @@ enum {
     ORC_U8 = 2,
     ORC_I8 = 3,
     ORC_SQ8 = 4, /* dim code bytes + f32 compensation */
-    ORC_PQ = 5   /* pq_chunks code bytes; f32 queries; lookup-table distances */
+    ORC_PQ = 5,  /* pq_chunks code bytes; f32 queries; lookup-table distances */
+    /* dim = 1, a row (and a query) is one u32 key; every distance is read from the caller's table: stored slot i holds
+     * key i, pair(a, b) = table[key(a)][b], query x slot = table[key(query)][slot] -- the first argument names the
+     * table row, and the table need not be symmetric.  `metric` only selects RobustPrune's rule (occluding == IP).
+     * Lets every algorithm restated here run on a row type whose distances a numpy model supplies.  Entry points that
+     * read row bytes (orc_distance*, the `fast` twins, orc_bench_distance) answer NaN / an error for it. */
+    ORC_TABLE = 6
 };
 enum { ORC_COSINE = 0, ORC_INNER_PRODUCT = 1, ORC_L2 = 2, ORC_COSINE_NORMALIZED = 3 };
 enum { ORC_IBC_NONE = 0, ORC_IBC_ALL = 0xFFFFFFFFu }; /* else Max(n) */
@@ -67,6 +73,8 @@ typedef struct {
      * Tag::PUBLISHED (254) is skipped by expand_beam after the visited insert and is not counted (provider.rs:448-473,
      * 681-686). */
     uint32_t tag_offset;
+    const float* table;   /* ORC_TABLE: table_keys x (capacity + nstart) f32, row-major */
+    uint64_t table_keys;  /* >= capacity + nstart; keys past the stored slots are external queries */
 } orc_index;
 
 /* graph::config::Builder (diskann/src/graph/config/mod.rs:261-338, defaults.rs) */

@@ -10,13 +10,22 @@ COMPLETE, DELETED = 0, 1
 
 def pair_distance(oix, x, y):
     """d(row x, row y) as the index evaluates it: the oracle's element-type distance, or for SQ-8 rows the compensated
-    distance with the index's quantiser parameters (CompensatedSquaredL2 / IP / CosineNormalized)"""
+    distance with the index's quantiser parameters (CompensatedSquaredL2 / IP / CosineNormalized), or for a TABLE index
+    the caller's table entry, x naming the table row"""
+    if oix.dtype == oracle.TABLE:
+        return np.float32(oix.table[x, y])
+    return row_distance(oix, oix.rows[x, :oix.row_bytes], oix.rows[y, :oix.row_bytes])
+
+
+def row_distance(oix, a, b):
+    """pair_distance for two row images (payload bytes) that need not be stored in the index"""
     if oix.dtype != oracle.SQ8:
-        return oracle.distance(oix.dtype, oix.metric, oix.row(x), oix.row(y))
+        dt = oracle.NP_DTYPE[oix.dtype]
+        return oracle.distance(oix.dtype, oix.metric, np.ascontiguousarray(a).view(dt), np.ascontiguousarray(b).view(dt))
     import ctypes as C
     dim = oix.dim
-    a = np.ascontiguousarray(oix.rows[x, :dim + 4])
-    b = np.ascontiguousarray(oix.rows[y, :dim + 4])
+    a = np.ascontiguousarray(a[:dim + 4])
+    b = np.ascontiguousarray(b[:dim + 4])
     metric = oix.metric if oix.metric != oracle.COSINE_NORMALIZED else oracle.L2
     d = oracle.lib().orc_sq8_distance(metric, a.ctypes.data, C.c_float(a[dim:].view(np.float32)[0]), b.ctypes.data,
                                       C.c_float(b[dim:].view(np.float32)[0]), dim, C.c_float(oix._c.sq_scale),

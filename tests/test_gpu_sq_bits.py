@@ -239,11 +239,13 @@ def test_search_server_sq4():
 
 
 # ---- build --------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("bits,dim", [(4, 32), (1, 16)])
-def test_build_matches_twin(bits, dim):
-    """SQ1 at dim 16: distances take 17 values, nearly every pool holds ties (default tie order)"""
+@pytest.mark.parametrize("bits,dim,metric", [(b, d, m) for m in METRICS for b, d in ((4, 32), (1, 16))],
+                         ids=[f"{b}-{d}{t}" for t in ("", "-ip", "-cosn") for b, d in ((4, 32), (1, 16))])
+def test_build_matches_twin(bits, dim, metric):
+    """SQ1 at dim 16: distances take 17 values, nearly every pool holds ties (default tie order).  Inner product is the
+    one metric under which RobustPrune takes its Occluding rule; CosineNormalized is the L2 kernel with an epilogue"""
     n, R, maxdeg, lb = 500, 8, 10, 24
-    c = Case(bits, oracle.L2, n, dim, R, 50 + bits, adj=False, maxdeg=maxdeg)
+    c = Case(bits, metric, n, dim, R, 50 + bits, adj=False, maxdeg=maxdeg)
     ocfg = oracle.build_config(R, maxdeg, lb, intra_batch_candidates=oracle.IBC_NONE)
     gcfg = da.build_config(R, maxdeg, lb, intra_batch_candidates=da.IBC_NONE)
     s = 0
@@ -270,8 +272,16 @@ def _same_graph(gix, oix):
 
 
 def test_consolidate_sq4():
+    _consolidate(4, 61)
+
+
+def test_consolidate_sq1():
+    _consolidate(1, 63)
+
+
+def _consolidate(bits, seed):
     n, R = 1200, 32
-    c = Case(4, oracle.L2, n, 128, R, 61)
+    c = Case(bits, oracle.L2, n, 128, R, seed)
     deleted = np.zeros(n + 1, bool)
     deleted[c.rng.choice(n, n // 10, replace=False)] = True
     c.gix.delete_points(np.flatnonzero(deleted))
@@ -283,8 +293,16 @@ def test_consolidate_sq4():
 
 
 def test_inplace_delete_sq4():
+    _inplace_delete(4, 62)
+
+
+def test_inplace_delete_sq1():
+    _inplace_delete(1, 64)
+
+
+def _inplace_delete(bits, seed):
     n, R = 1000, 32
-    c = Case(4, oracle.L2, n, 128, R, 62)
+    c = Case(bits, oracle.L2, n, 128, R, seed)
     deleted = np.zeros(n + 1, bool)
     ids = c.rng.choice(n, 16, replace=False)
     c.gix.set_prune_tie_order(da.TIE_RUST)
