@@ -17,6 +17,7 @@
 
 #include "dann_device.h"
 #include "dann_internal.h"
+#include "wave_lists.h"  // kTagReadable
 
 namespace dann {
 
@@ -61,20 +62,6 @@ static bool mm_headers_ok(const dann_index* idx, const void* rows, uint64_t n, u
 }
 static bool valid_metric(int32_t m) { return m >= 0 && m <= 3; }
 
-// temporary device buffer with RAII
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-    template <class T>
-    T* as() {
-        return reinterpret_cast<T*>(p);
-    }
-};
-
-// time one launch on the index stream with HIP events (the stream the kernel runs on)
 // a block of a context's arena, carved into 256-byte aligned pieces
 struct Carve {
     size_t off = 0;
@@ -94,6 +81,7 @@ struct ArenaPtr {
     }
 };
 
+// time one launch on the index stream with HIP events (the stream the kernel runs on)
 template <class F>
 static int32_t timed(dann_index* idx, int which, F&& f) {
     DANN_HIP(hipEventRecord(idx->main.ev0, idx->main.stream));
@@ -216,16 +204,6 @@ int32_t search_device(dann_index* idx, SearchCtx& ctx, const void* d_queries, co
     a.rec_dists = d_rec_d;
     a.rec_stride = rec_stride;
     a.rec_n = d_rec_n;
-    a.qmap = nullptr;
-    a.range_ids = nullptr;
-    a.range_d = nullptr;
-    a.range_second = nullptr;
-    a.range_cap = a.range_max = a.range_thresh = a.has_inner = 0;
-    a.radius = a.inner_radius = a.range_slack = 0.0f;
-    a.fail_flag = nullptr;
-    a.spill = nullptr;
-    a.spill_next = nullptr;
-    a.spill_slices = a.spill_bits = 0;
     return search_with_retry(idx, ctx, a);
 }
 
@@ -539,8 +517,8 @@ int32_t dann_set_elements(dann_index* idx, uint32_t first_slot, uint32_t n, cons
                               idx->layer_bytes, idx->layer_bytes, n, hipMemcpyHostToDevice, idx->main.stream));
     if (idx->cfg.inline_tags) {  // Slot::publish (store.rs:776-782)
         DANN_HIP(hipMemset2DAsync(idx->d_rows + (size_t)first_slot * idx->cfg.row_stride + idx->layer_bytes,
-                                  idx->cfg.row_stride, 254, 1, n, idx->main.stream));
-        std::fill(idx->h_tags.begin() + first_slot, idx->h_tags.begin() + first_slot + n, (uint8_t)254);
+                                  idx->cfg.row_stride, kTagReadable, 1, n, idx->main.stream));
+        std::fill(idx->h_tags.begin() + first_slot, idx->h_tags.begin() + first_slot + n, kTagReadable);
     }
     DANN_HIP(hipStreamSynchronize(idx->main.stream));
     return DANN_OK;
@@ -564,8 +542,8 @@ int32_t dann_set_elements_device(dann_index* idx, uint32_t first_slot, uint32_t 
                               idx->layer_bytes, n, hipMemcpyDeviceToDevice, idx->main.stream));
     if (idx->cfg.inline_tags) {  // Slot::publish (store.rs:776-782)
         DANN_HIP(hipMemset2DAsync(idx->d_rows + (size_t)first_slot * idx->cfg.row_stride + idx->layer_bytes,
-                                  idx->cfg.row_stride, 254, 1, n, idx->main.stream));
-        std::fill(idx->h_tags.begin() + first_slot, idx->h_tags.begin() + first_slot + n, (uint8_t)254);
+                                  idx->cfg.row_stride, kTagReadable, 1, n, idx->main.stream));
+        std::fill(idx->h_tags.begin() + first_slot, idx->h_tags.begin() + first_slot + n, kTagReadable);
     }
     DANN_HIP(hipStreamSynchronize(idx->main.stream));
     return DANN_OK;
@@ -591,7 +569,7 @@ int32_t dann_set_tags(dann_index* idx, uint32_t first_slot, uint32_t n, const ui
     // start points are FROZEN for the lifetime of the store (store.rs:766-772); a search that cannot read one fails
     // ("could not retrieve start point", provider.rs:408-431) -- refuse the state instead of producing it
     for (uint32_t i = 0; i < n; ++i)
-        if (first_slot + i >= idx->cfg.capacity && tags[i] < 254) {
+        if (first_slot + i >= idx->cfg.capacity && tags[i] < kTagReadable) {
             set_error("dann_set_tags: start point slot %u must stay readable (tag >= 254), got %u", first_slot + i, tags[i]);
             return DANN_EINVAL;
         }
@@ -606,7 +584,7 @@ int32_t dann_get_tags(const dann_index* idx, uint32_t first_slot, uint32_t n, ui
     if (!idx || (n && !tags)) return DANN_EINVAL;
     ::dann::ExclusiveGuard lock(idx);
     if ((uint64_t)first_slot + n > idx->nslots) return DANN_EBOUNDS;
-    if (!idx->cfg.inline_tags) memset(tags, 254, n);  // a store without tags: every slot readable
+    if (!idx->cfg.inline_tags) memset(tags, kTagReadable, n);  // a store without tags: every slot readable
     else memcpy(tags, idx->h_tags.data() + first_slot, n);
     return DANN_OK;
 } DANN_CATCH_ALL
@@ -644,7 +622,7 @@ int32_t dann_upload_store(dann_index* idx, const void* base, uint64_t stride, ui
     if (tags) {  // as dann_set_tags: a start point must stay readable
         const uint8_t* b = reinterpret_cast<const uint8_t*>(base) + idx->layer_bytes;
         for (uint32_t i = idx->cfg.capacity; i < nrows; ++i)
-            if (b[(size_t)i * stride] < 254) {
+            if (b[(size_t)i * stride] < kTagReadable) {
                 set_error("dann_upload_store: start point slot %u must be readable (tag >= 254), got %u", i, b[(size_t)i * stride]);
                 return DANN_EINVAL;
             }
@@ -1012,7 +990,7 @@ int32_t dann_expand_beam(const dann_query* q, const uint32_t* ids, uint32_t n, u
     // read_in_bounds(i) -> None for a slot whose tag is not readable: skipped, not counted (provider.rs:681-686)
     uint32_t m = 0;
     for (uint32_t i = 0; i < n; ++i)
-        if (!idx->cfg.inline_tags || idx->h_tags[ids[i]] >= 254) out_ids[m++] = ids[i];
+        if (!idx->cfg.inline_tags || idx->h_tags[ids[i]] >= kTagReadable) out_ids[m++] = ids[i];
     *out_n = m;
     if (m == 0) return DANN_OK;
     return expand_on_device(idx, idx->qview(q->layout), q->d_query, out_ids, m, out_dists);
@@ -1050,7 +1028,7 @@ int32_t dann_expand_beam_batch(const dann_index* cidx, const void* queries, uint
     DANN_HIP(hipStreamSynchronize(idx->main.stream));
     if (idx->cfg.inline_tags)  // the positional batch form cannot drop entries: unreadable slots report NaN
         for (uint64_t i = 0; i < total; ++i)
-            if (idx->h_tags[ids[i]] < 254) out_dists[i] = __builtin_nanf("");
+            if (idx->h_tags[ids[i]] < kTagReadable) out_dists[i] = __builtin_nanf("");
     return DANN_OK;
 } DANN_CATCH_ALL
 
@@ -1068,14 +1046,9 @@ int32_t dann_search_batch_device(dann_index* idx, const void* d_queries, uint32_
                          nullptr, nullptr, 0, nullptr);
 } DANN_CATCH_ALL
 
-int32_t dann_range_search_batch(dann_index* idx, const void* queries, uint32_t nq, uint32_t starting_l,
-                                uint32_t beam_width, float radius, int32_t has_inner_radius, float inner_radius,
-                                float initial_slack, float range_slack, uint32_t max_returned, uint32_t out_cap,
-                                uint32_t* out_ids, float* out_dists, dann_search_stats* out_stats,
-                                uint32_t* out_second_round) try {
-    CHECK_IDX_SHARED(idx);  // read-only: concurrent callers run side by side, each on its own context
-    ArenaTrim _trim{ctx};
-    // RangeSearchError (range_search.rs:30-45, 93-131)
+// RangeSearchError (range_search.rs:30-45, 93-131), for both range entry points
+static int32_t check_range_params(uint32_t starting_l, uint32_t beam_width, float radius, int32_t has_inner_radius,
+                                  float inner_radius, float initial_slack, float range_slack, uint32_t max_returned) {
     if (starting_l == 0 || beam_width == 0) {
         set_error("l_value and beam width cannot be zero");
         return DANN_EINVAL;
@@ -1096,6 +1069,33 @@ int32_t dann_range_search_batch(dann_index* idx, const void* queries, uint32_t n
         set_error("inner_radius must be less than or equal to radius");
         return DANN_EINVAL;
     }
+    return DANN_OK;
+}
+
+// The n per-query stats of a launch on `st`: copied back (the stream is synchronised, so the copies queued before have
+// landed too), mirrored into the caller's out_stats if there is one; *first_bad = the first query whose status is
+// non-zero, or n.  What an exhausted query means is the caller's to say.
+static int32_t fetch_stats(hipStream_t st, const void* d_stats, uint32_t n, dann_search_stats* out_stats, uint32_t* first_bad) {
+    std::vector<dann_search_stats> stats(n);
+    DANN_HIP(hipMemcpyAsync(stats.data(), d_stats, (size_t)n * sizeof(dann_search_stats), hipMemcpyDeviceToHost, st));
+    DANN_HIP(hipStreamSynchronize(st));
+    if (out_stats) memcpy(out_stats, stats.data(), (size_t)n * sizeof(dann_search_stats));
+    uint32_t i = 0;
+    while (i < n && !stats[i].status) ++i;
+    *first_bad = i;
+    return DANN_OK;
+}
+
+int32_t dann_range_search_batch(dann_index* idx, const void* queries, uint32_t nq, uint32_t starting_l,
+                                uint32_t beam_width, float radius, int32_t has_inner_radius, float inner_radius,
+                                float initial_slack, float range_slack, uint32_t max_returned, uint32_t out_cap,
+                                uint32_t* out_ids, float* out_dists, dann_search_stats* out_stats,
+                                uint32_t* out_second_round) try {
+    CHECK_IDX_SHARED(idx);  // read-only: concurrent callers run side by side, each on its own context
+    ArenaTrim _trim{ctx};
+    if (int32_t rc = check_range_params(starting_l, beam_width, radius, has_inner_radius, inner_radius, initial_slack,
+                                        range_slack, max_returned))
+        return rc;
     if (nq == 0) return DANN_OK;
     if (!queries || !out_ids || !out_dists || out_cap == 0) return DANN_EINVAL;
     uint64_t cap = max_returned ? max_returned : (uint64_t)4 * out_cap + 1024;
@@ -1116,7 +1116,6 @@ int32_t dann_range_search_batch(dann_index* idx, const void* queries, uint32_t n
     SearchArgs a;
     a.ix = idx->qview();
     a.queries = bq.p;
-    a.qslots = nullptr;
     a.nq = nq;
     a.l_value = starting_l;
     a.beam_width = beam_width;
@@ -1125,11 +1124,6 @@ int32_t dann_range_search_batch(dann_index* idx, const void* queries, uint32_t n
     a.out_ids = bi.as<uint32_t>();
     a.out_dists = bd.as<float>();
     a.stats = bs.as<dann_search_stats>();
-    a.rec_ids = nullptr;
-    a.rec_dists = nullptr;
-    a.rec_stride = 0;
-    a.rec_n = nullptr;
-    a.qmap = nullptr;
     a.range_ids = bri.as<uint32_t>();
     a.range_d = brd.as<float>();
     a.range_second = bsec.as<uint32_t>();
@@ -1140,27 +1134,19 @@ int32_t dann_range_search_batch(dann_index* idx, const void* queries, uint32_t n
     a.radius = radius;
     a.inner_radius = inner_radius;
     a.range_slack = range_slack;
-    a.fail_flag = nullptr;
-    a.spill = nullptr;
-    a.spill_next = nullptr;
-    a.spill_slices = a.spill_bits = 0;
     int32_t rc = search_with_retry(idx, ctx, a);
     if (rc != DANN_OK) return rc;
-    std::vector<dann_search_stats> stats(nq);
     DANN_HIP(hipMemcpyAsync(out_ids, bi.p, (size_t)nq * out_cap * 4, hipMemcpyDeviceToHost, ctx.stream));
     DANN_HIP(hipMemcpyAsync(out_dists, bd.p, (size_t)nq * out_cap * 4, hipMemcpyDeviceToHost, ctx.stream));
-    DANN_HIP(hipMemcpyAsync(stats.data(), bs.p, (size_t)nq * sizeof(dann_search_stats), hipMemcpyDeviceToHost,
-                            ctx.stream));
     if (out_second_round)
         DANN_HIP(hipMemcpyAsync(out_second_round, bsec.p, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx.stream));
-    DANN_HIP(hipStreamSynchronize(ctx.stream));
-    if (out_stats) memcpy(out_stats, stats.data(), (size_t)nq * sizeof(dann_search_stats));
-    for (uint32_t i = 0; i < nq; ++i)
-        if (stats[i].status) {
-            set_error("query %u: range result list or visited scratch exhausted (list capacity %llu)", i,
-                      (unsigned long long)cap);
-            return DANN_EOVERFLOW;
-        }
+    uint32_t bad = nq;
+    if (int32_t frc = fetch_stats(ctx.stream, bs.p, nq, out_stats, &bad)) return frc;
+    if (bad < nq) {
+        set_error("query %u: range result list or visited scratch exhausted (list capacity %llu)", bad,
+                  (unsigned long long)cap);
+        return DANN_EOVERFLOW;
+    }
     return DANN_OK;
 } DANN_CATCH_ALL
 
@@ -1318,7 +1304,6 @@ static int32_t filtered_search(dann_index* idx, SearchCtx& ctx, const FilteredCa
     a.out_dists = bd.as<float>();
     a.stats = bs.as<dann_search_stats>();
     a.queries = bq.p;
-    std::vector<dann_search_stats> stats(chunk);
     for (uint32_t off = 0; off < c.nq; off += chunk) {
         const uint32_t n = std::min(chunk, c.nq - off);
         DANN_HIP(hipMemcpyAsync(bq.p, (const uint8_t*)c.queries + (size_t)off * qb, (size_t)n * qb, hipMemcpyHostToDevice, st));
@@ -1328,17 +1313,15 @@ static int32_t filtered_search(dann_index* idx, SearchCtx& ctx, const FilteredCa
         if (rc != DANN_OK) return rc;
         DANN_HIP(hipMemcpyAsync(c.out_ids + (size_t)off * c.k, bi.p, (size_t)n * c.k * 4, hipMemcpyDeviceToHost, st));
         DANN_HIP(hipMemcpyAsync(c.out_dists + (size_t)off * c.k, bd.p, (size_t)n * c.k * 4, hipMemcpyDeviceToHost, st));
-        DANN_HIP(hipMemcpyAsync(stats.data(), bs.p, (size_t)n * sizeof(dann_search_stats), hipMemcpyDeviceToHost, st));
         if (c.out_second)
             DANN_HIP(hipMemcpyAsync(c.out_second + off, bsec.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        DANN_HIP(hipStreamSynchronize(st));
-        if (c.out_stats) memcpy(c.out_stats + off, stats.data(), (size_t)n * sizeof(dann_search_stats));
-        for (uint32_t i = 0; i < n; ++i)
-            if (stats[i].status) {
-                set_error("query %u: per-query scratch exhausted (matched list %u entries, result list %llu, visited "
-                          "table); raise dann_filter.matched_cap / out_cap", off + i, m_cap, (unsigned long long)rcap);
-                return DANN_EOVERFLOW;
-            }
+        uint32_t bad = n;
+        if (int32_t frc = fetch_stats(st, bs.p, n, c.out_stats ? c.out_stats + off : nullptr, &bad)) return frc;
+        if (bad < n) {
+            set_error("query %u: per-query scratch exhausted (matched list %u entries, result list %llu, visited "
+                      "table); raise dann_filter.matched_cap / out_cap", off + bad, m_cap, (unsigned long long)rcap);
+            return DANN_EOVERFLOW;
+        }
     }
     return DANN_OK;
 }
@@ -1362,27 +1345,9 @@ int32_t dann_filtered_range_search_batch(dann_index* idx, const void* queries, u
                                          uint32_t* out_second_round) try {
     CHECK_IDX_SHARED(idx);
     ArenaTrim _trim{ctx};
-    // RangeSearchError (range_search.rs:30-45, 93-131)
-    if (starting_l == 0 || beam_width == 0) {
-        set_error("l_value and beam width cannot be zero");
-        return DANN_EINVAL;
-    }
-    if (max_returned && max_returned < starting_l) {
-        set_error("max_returned must be greater than or equal to starting_l");
-        return DANN_EINVAL;
-    }
-    if (!(initial_slack >= 0.0f && initial_slack <= 1.0f)) {
-        set_error("initial_search_slack must be between 0 and 1.0");
-        return DANN_EINVAL;
-    }
-    if (!(range_slack >= 1.0f)) {
-        set_error("range_search_slack must be greater than or equal to 1.0");
-        return DANN_EINVAL;
-    }
-    if (has_inner_radius && inner_radius > radius) {
-        set_error("inner_radius must be less than or equal to radius");
-        return DANN_EINVAL;
-    }
+    if (int32_t rc = check_range_params(starting_l, beam_width, radius, has_inner_radius, inner_radius, initial_slack,
+                                        range_slack, max_returned))
+        return rc;
     if (nq == 0) return DANN_OK;
     if (!queries || !out_ids || !out_dists || out_cap == 0) return DANN_EINVAL;
     FilteredCall c{queries, nq, starting_l, beam_width, out_cap, filter, out_ids, out_dists, out_stats};
@@ -1805,71 +1770,50 @@ int32_t dann_chamfer_rerank_batch_device(const dann_mvset* set, int32_t order, c
                      d_out_counts, true);
 } DANN_CATCH_ALL
 
-int32_t dann_search_record_batch(dann_index* idx, const uint32_t* slots, uint32_t nq, uint32_t l_value,
-                                 uint32_t* rec_ids, float* rec_dists, uint32_t rec_stride, uint32_t* rec_n,
-                                 dann_search_stats* out_stats) try {
+// dann_search_record_batch / dann_search_record_queries: beam-1 searches that keep their visit records.  The queries are
+// stored rows (`slots`) or rows staged from the host (`queries`); the caller passes exactly one of the two.
+static int32_t search_record(dann_index* idx, const uint32_t* slots, const void* queries, uint32_t nq, uint32_t l_value,
+                             uint32_t* rec_ids, float* rec_dists, uint32_t rec_stride, uint32_t* rec_n,
+                             dann_search_stats* out_stats) {
     CHECK_IDX(idx);
     if (nq == 0) return DANN_OK;
-    if (!slots || !rec_ids || !rec_dists || !rec_n || rec_stride == 0) return DANN_EINVAL;
-    for (uint32_t i = 0; i < nq; ++i)
+    if (!(slots || queries) || !rec_ids || !rec_dists || !rec_n || rec_stride == 0) return DANN_EINVAL;
+    for (uint32_t i = 0; slots && i < nq; ++i)
         if (slots[i] >= idx->nslots) return DANN_EBOUNDS;
-    DevBuf bsl, bri, brd, brn, bs;
-    DANN_HIP(bsl.alloc((size_t)nq * 4));
+    hipStream_t st = idx->main.stream;
+    const size_t src_bytes = slots ? (size_t)nq * 4 : (size_t)nq * idx->query_bytes();
+    DevBuf bsrc, bri, brd, brn, bs;
+    DANN_HIP(bsrc.alloc(src_bytes + 16));  // (+ 16: the kernels read a query's tail with whole vector loads)
     DANN_HIP(bri.alloc((size_t)nq * rec_stride * 4));
     DANN_HIP(brd.alloc((size_t)nq * rec_stride * 4));
     DANN_HIP(brn.alloc((size_t)nq * 4));
     DANN_HIP(bs.alloc((size_t)nq * sizeof(dann_search_stats)));
-    DANN_HIP(hipMemcpyAsync(bsl.p, slots, (size_t)nq * 4, hipMemcpyHostToDevice, idx->main.stream));
-    int32_t rc = search_device(idx, idx->main, nullptr, bsl.as<uint32_t>(), nq, l_value, 1, 0, nullptr, nullptr,
-                               bs.as<dann_search_stats>(), bri.as<uint32_t>(), brd.as<float>(), rec_stride,
-                               brn.as<uint32_t>());
+    DANN_HIP(hipMemcpyAsync(bsrc.p, slots ? (const void*)slots : queries, src_bytes, hipMemcpyHostToDevice, st));
+    int32_t rc = search_device(idx, idx->main, slots ? nullptr : bsrc.p, slots ? bsrc.as<uint32_t>() : nullptr, nq, l_value,
+                               1, 0, nullptr, nullptr, bs.as<dann_search_stats>(), bri.as<uint32_t>(), brd.as<float>(),
+                               rec_stride, brn.as<uint32_t>());
     if (rc != DANN_OK) return rc;
-    std::vector<dann_search_stats> stats(nq);
-    DANN_HIP(hipMemcpyAsync(rec_ids, bri.p, (size_t)nq * rec_stride * 4, hipMemcpyDeviceToHost, idx->main.stream));
-    DANN_HIP(hipMemcpyAsync(rec_dists, brd.p, (size_t)nq * rec_stride * 4, hipMemcpyDeviceToHost, idx->main.stream));
-    DANN_HIP(hipMemcpyAsync(rec_n, brn.p, (size_t)nq * 4, hipMemcpyDeviceToHost, idx->main.stream));
-    DANN_HIP(hipMemcpyAsync(stats.data(), bs.p, (size_t)nq * sizeof(dann_search_stats), hipMemcpyDeviceToHost,
-                            idx->main.stream));
-    DANN_HIP(hipStreamSynchronize(idx->main.stream));
-    if (out_stats) memcpy(out_stats, stats.data(), (size_t)nq * sizeof(dann_search_stats));
-    for (uint32_t i = 0; i < nq; ++i)
-        if (stats[i].status) {
-            set_error("query %u: visited table or record buffer exhausted", i);
-            return DANN_EOVERFLOW;
-        }
+    DANN_HIP(hipMemcpyAsync(rec_ids, bri.p, (size_t)nq * rec_stride * 4, hipMemcpyDeviceToHost, st));
+    DANN_HIP(hipMemcpyAsync(rec_dists, brd.p, (size_t)nq * rec_stride * 4, hipMemcpyDeviceToHost, st));
+    DANN_HIP(hipMemcpyAsync(rec_n, brn.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    uint32_t bad = nq;
+    if (int32_t frc = fetch_stats(st, bs.p, nq, out_stats, &bad)) return frc;
+    if (bad < nq) {
+        set_error("query %u: visited table or record buffer exhausted", bad);
+        return DANN_EOVERFLOW;
+    }
     return DANN_OK;
+}
+
+int32_t dann_search_record_batch(dann_index* idx, const uint32_t* slots, uint32_t nq, uint32_t l_value,
+                                 uint32_t* rec_ids, float* rec_dists, uint32_t rec_stride, uint32_t* rec_n,
+                                 dann_search_stats* out_stats) try {
+    return search_record(idx, slots, nullptr, nq, l_value, rec_ids, rec_dists, rec_stride, rec_n, out_stats);
 } DANN_CATCH_ALL
 
 int32_t dann_search_record_queries(dann_index* idx, const void* queries, uint32_t nq, uint32_t l_value, uint32_t* rec_ids,
                                    float* rec_dists, uint32_t rec_stride, uint32_t* rec_n, dann_search_stats* out_stats) try {
-    CHECK_IDX(idx);
-    if (nq == 0) return DANN_OK;
-    if (!queries || !rec_ids || !rec_dists || !rec_n || rec_stride == 0) return DANN_EINVAL;
-    const size_t qb = idx->query_bytes();
-    DevBuf bq, bri, brd, brn, bs;
-    DANN_HIP(bq.alloc((size_t)nq * qb + 16));
-    DANN_HIP(bri.alloc((size_t)nq * rec_stride * 4));
-    DANN_HIP(brd.alloc((size_t)nq * rec_stride * 4));
-    DANN_HIP(brn.alloc((size_t)nq * 4));
-    DANN_HIP(bs.alloc((size_t)nq * sizeof(dann_search_stats)));
-    DANN_HIP(hipMemcpyAsync(bq.p, queries, (size_t)nq * qb, hipMemcpyHostToDevice, idx->main.stream));
-    int32_t rc = search_device(idx, idx->main, bq.p, nullptr, nq, l_value, 1, 0, nullptr, nullptr, bs.as<dann_search_stats>(),
-                               bri.as<uint32_t>(), brd.as<float>(), rec_stride, brn.as<uint32_t>());
-    if (rc != DANN_OK) return rc;
-    std::vector<dann_search_stats> stats(nq);
-    DANN_HIP(hipMemcpyAsync(rec_ids, bri.p, (size_t)nq * rec_stride * 4, hipMemcpyDeviceToHost, idx->main.stream));
-    DANN_HIP(hipMemcpyAsync(rec_dists, brd.p, (size_t)nq * rec_stride * 4, hipMemcpyDeviceToHost, idx->main.stream));
-    DANN_HIP(hipMemcpyAsync(rec_n, brn.p, (size_t)nq * 4, hipMemcpyDeviceToHost, idx->main.stream));
-    DANN_HIP(hipMemcpyAsync(stats.data(), bs.p, (size_t)nq * sizeof(dann_search_stats), hipMemcpyDeviceToHost,
-                            idx->main.stream));
-    DANN_HIP(hipStreamSynchronize(idx->main.stream));
-    if (out_stats) memcpy(out_stats, stats.data(), (size_t)nq * sizeof(dann_search_stats));
-    for (uint32_t i = 0; i < nq; ++i)
-        if (stats[i].status) {
-            set_error("query %u: visited table or record buffer exhausted", i);
-            return DANN_EOVERFLOW;
-        }
-    return DANN_OK;
+    return search_record(idx, nullptr, queries, nq, l_value, rec_ids, rec_dists, rec_stride, rec_n, out_stats);
 } DANN_CATCH_ALL
 
 // ---- on-disk formats ---------------------------------------------------------------------------

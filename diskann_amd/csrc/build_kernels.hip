@@ -41,8 +41,6 @@
 namespace dann {
 namespace {
 
-constexpr uint32_t kMaxPool = 4096;
-
 struct PruneCfg {
     uint32_t pruned_degree, max_degree, max_occlusion;
     float alpha;
@@ -115,12 +113,6 @@ __host__ __device__ inline PoolLds sweep_lds_layout(uint32_t pcap, uint32_t degr
     return l;
 }
 
-__device__ __forceinline__ uint64_t sort_key(float d, uint32_t pos) {
-    uint32_t u = __builtin_bit_cast(uint32_t, d + 0.0f);  // -0.0 -> +0.0: `<` treats them as equal
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((uint64_t)u << 32) | pos;
-}
-
 // PruneKind::update_occlude_factor (config/mod.rs:80-103)
 template <int OP>
 __device__ __forceinline__ float update_occlude(float d_ik, float d_jk, float cur, float alpha, bool occluding) {
@@ -186,7 +178,7 @@ __device__ void prune_sorted_pool(const IndexView& ix, const PruneCfg& cfg, uint
     for (uint32_t i = lane; i < pcap; i += kWave) {
         const float d = i < P ? pd[i] : 0.0f;
         saw_nan |= d != d;
-        keys[i] = i < P ? sort_key(d, i) : ~0ull;
+        keys[i] = i < P ? dist_key(d, i) : ~0ull;
     }
     __syncthreads();
     for (uint32_t k = 2; k <= pcap; k <<= 1) {
@@ -772,7 +764,7 @@ __device__ uint32_t sort_pool_wave(const PruneCfg& cfg, uint32_t P, uint32_t pca
     for (uint32_t i = lane; i < pcap; i += kWave) {
         const float d = i < P ? pd[i] : 0.0f;
         saw_nan |= d != d;
-        keys[i] = i < P ? sort_key(d, i) : ~0ull;
+        keys[i] = i < P ? dist_key(d, i) : ~0ull;
     }
     wave_sync();
     for (uint32_t k = 2; k <= pcap; k <<= 1) {
@@ -2055,12 +2047,6 @@ int32_t launch_gram_tiles(const TileArgs& a, uint32_t grid, hipStream_t stream, 
     return narrow ? go(KernelOf<gram_tiles_kernel<__half, 1>>{}) : go(KernelOf<gram_tiles_kernel<__half, 3>>{});
 }
 
-uint32_t next_pow2(uint32_t x) {
-    uint32_t p = 64;
-    while (p < x) p <<= 1;
-    return p;
-}
-
 // development switches (dann_debug_set): DANN_DBG_SWEEP_ONE_BY_ONE; DANN_DBG_POOL_GRAM = 0 keeps the row kernel for the
 // pool prune of large rows (A/B runs)
 uint32_t sweep_one_by_one(const dann_index* idx) { return idx->dbg_u32(DANN_DBG_SWEEP_ONE_BY_ONE, 0u) ? 1u : 0u; }
@@ -2077,44 +2063,6 @@ PruneCfg to_prune_cfg(const dann_index* idx, const dann_build_config& c) {
     p.counters = nullptr;
     return p;
 }
-
-int32_t validate_cfg(const dann_index* idx, const dann_build_config* cfg) {
-    if (!cfg) return DANN_EINVAL;
-    if (idx->cfg.dtype == DT_PQ) {
-        set_error("index build / prune are not defined on DANN_PQ rows (build on the full-precision index)");
-        return DANN_EUNSUPPORTED;
-    }
-    if (cfg->pruned_degree == 0 || cfg->l_build == 0 || cfg->max_degree < cfg->pruned_degree ||
-        cfg->max_degree > idx->cfg.max_degree || !(cfg->alpha >= 1.0f)) {
-        set_error("invalid build config (pruned_degree %u, max_degree %u (provider %u), l_build %u, alpha %g)",
-                  cfg->pruned_degree, cfg->max_degree, idx->cfg.max_degree, cfg->l_build, (double)cfg->alpha);
-        return DANN_EINVAL;
-    }
-    if (cfg->max_occlusion_size > kMaxPool) {
-        set_error("max_occlusion_size %u exceeds the supported %u", cfg->max_occlusion_size, kMaxPool);
-        return DANN_EUNSUPPORTED;
-    }
-    return DANN_OK;
-}
-
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    hipError_t alloc(size_t n) {
-        release();
-        return hipMalloc(&p, n ? n : 1);
-    }
-    template <class T>
-    T* as() {
-        return reinterpret_cast<T*>(p);
-    }
-};
 
 // persistent per-index scratch for batched inserts
 struct BuildScratch {
@@ -2240,6 +2188,31 @@ int32_t ensure_gram_scratch(BuildScratch& s, size_t items, uint32_t pcap, uint32
 
 }  // namespace
 
+int32_t check_build_cfg(const dann_index* idx, const dann_build_config* cfg, const char* what, bool need_l_build) {
+    if (!cfg) return DANN_EINVAL;
+    if (idx->cfg.dtype == DT_PQ) {
+        set_error("%s: not defined on DANN_PQ rows (use the full-precision index)", what);
+        return DANN_EUNSUPPORTED;
+    }
+    int op;
+    bool norm;
+    if (!resolve_metric(idx->cfg.dtype, idx->cfg.metric, &op, &norm)) {
+        set_error("metric %d is not defined for dtype %d", idx->cfg.metric, idx->cfg.dtype);
+        return DANN_EUNSUPPORTED;
+    }
+    if (cfg->pruned_degree == 0 || (need_l_build && cfg->l_build == 0) || cfg->max_degree < cfg->pruned_degree ||
+        cfg->max_degree > idx->cfg.max_degree || !(cfg->alpha >= 1.0f)) {
+        set_error("%s: invalid config (pruned_degree %u, max_degree %u (provider %u), l_build %u, alpha %g)", what,
+                  cfg->pruned_degree, cfg->max_degree, idx->cfg.max_degree, cfg->l_build, (double)cfg->alpha);
+        return DANN_EINVAL;
+    }
+    if (cfg->max_occlusion_size > kMaxPool) {
+        set_error("%s: max_occlusion_size %u exceeds the supported %u", what, cfg->max_occlusion_size, kMaxPool);
+        return DANN_EUNSUPPORTED;
+    }
+    return DANN_OK;
+}
+
 // what the host wants from the m insert searches of a slice: comparisons, hops, the first search that failed -- three
 // words instead of m records through a pageable copy (327 KB per 16 384-point batch)
 __global__ __launch_bounds__(256) void stats_reduce_kernel(const dann_search_stats* st, uint32_t m, unsigned long long* sums,
@@ -2288,30 +2261,16 @@ static int32_t batch_candidates(dann_index* idx, const dann_build_config& cfg, B
     const uint32_t nex = (cand != 0 && n > 1) ? std::min(cand, n - 1) : 0;
     SearchArgs sa;
     sa.ix = ix;
-    sa.queries = nullptr;
     sa.qslots = d_slots + lo;
     sa.nq = m;
     sa.l_value = cfg.l_build;
     sa.beam_width = 1;
-    sa.k = 0;
     sa.ht_entries = auto_visited_entries(idx, cfg.l_build, 1);
-    sa.out_ids = nullptr;
-    sa.out_dists = nullptr;
     sa.stats = s.stats.as<dann_search_stats>();
     sa.rec_ids = s.rec_ids.as<uint32_t>();
     sa.rec_dists = s.rec_d.as<float>();
     sa.rec_stride = s.rec_stride;
     sa.rec_n = s.rec_n.as<uint32_t>();
-    sa.qmap = nullptr;
-    sa.range_ids = nullptr;
-    sa.range_d = nullptr;
-    sa.range_second = nullptr;
-    sa.range_cap = sa.range_max = sa.range_thresh = sa.has_inner = 0;
-    sa.radius = sa.inner_radius = sa.range_slack = 0.0f;
-    sa.fail_flag = nullptr;
-    sa.spill = nullptr;
-    sa.spill_next = nullptr;
-    sa.spill_slices = sa.spill_bits = 0;
     uint32_t* meta = s.meta.as<uint32_t>();  // [0] nseg [1] nkeys [2] maxseg [3] err [4] appends [5] prunes [6] max record
     DANN_HIP(hipMemsetAsync(meta, 0, 128, st));
     sa.rec_max = meta + 6;
@@ -2334,7 +2293,7 @@ static int32_t batch_candidates(dann_index* idx, const dann_build_config& cfg, B
     pa.cand = cand;
     pa.n = n;
     pa.pos0 = lo;
-    pa.pcap = next_pow2(h_recmax + nex);
+    pa.pcap = pow2_at_least(h_recmax + nex);
     pa.force_saturate = 0;
     pa.out = d_pending_out;
     pa.out_stride = s.pend_stride;
@@ -2476,7 +2435,7 @@ static int32_t batch_commit(dann_index* idx, const dann_build_config& cfg, Build
         la.pending = pending;
         la.pend_stride = s.pend_stride;
         la.n = n;
-        la.pcap = next_pow2(pc.pruned_degree + n);
+        la.pcap = pow2_at_least(pc.pruned_degree + n);
         la.out = s.pending2.as<uint32_t>();
         la.out_stride = s.pend_stride;
         la.err = meta + 3;
@@ -2532,7 +2491,7 @@ static int32_t batch_commit(dann_index* idx, const dann_build_config& cfg, Build
             if (const uint32_t e = idx->dbg_u32(DANN_DBG_BACKEDGE_GRAM_ROWS, 0u))
                 pg = std::min<uint32_t>(32u * kTileRowBlocks, std::max<uint32_t>(pg, (e + 31u) & ~31u));
         }
-        const uint32_t short_pcap = next_pow2(std::max<uint32_t>(pg, ix.max_degree + 1u));
+        const uint32_t short_pcap = pow2_at_least(std::max<uint32_t>(pg, ix.max_degree + 1u));
         const uint32_t short_cap = want_gram ? pg : short_pcap;
         // small rows without the MFMA path: the single-kernel form (list build + prune per target, its LDS pool sized by
         // the longest list of the batch) only while that pool is small.  One hub with a thousand back-edges in a batch
@@ -2543,7 +2502,7 @@ static int32_t batch_commit(dann_index* idx, const dann_build_config& cfg, Build
         // 6.0 s, 1 M x 128 build 0.64 / 0.64 / 0.62 / 0.61 / 0.61 s (round 2 had measured the split form slower at 1 M:
         // 0.78 against 0.68 s, before the scan kernel served four targets per wavefront).  Rows of 1 KiB and more always
         // take the split form (1 M x 768: 5.2 s -> 3.5 s, 3.25 s with the MFMA path).
-        const uint32_t pcap_all = next_pow2(ix.max_degree + h_meta[2]);
+        const uint32_t pcap_all = pow2_at_least(ix.max_degree + h_meta[2]);
         const uint32_t single_pool = idx->dbg_u32(DANN_DBG_BACKEDGE_SINGLE_POOL, 128u);
         if (!want_gram && ix.layer_bytes < 1024u && world <= 1u && pcap_all <= single_pool) {
             if (pcap_all > kMaxPool) {
@@ -2589,7 +2548,7 @@ static int32_t batch_commit(dann_index* idx, const dann_build_config& cfg, Build
             BackArgs bl = ba;
             bl.work = work + ba.nseg;
             bl.nseg = h_counts[1];
-            bl.pcap = next_pow2(h_counts[2]);
+            bl.pcap = pow2_at_least(h_counts[2]);
             bl.count_long = want_gram ? 1u : 0u;
             if (bl.pcap > kMaxPool) {
                 set_error("a node received back-edges for a list of %u entries in one batch (cap %u): lower max_batch",
@@ -2839,7 +2798,7 @@ int32_t dann_insert_batch(dann_index* idx, const dann_build_config* cfg, const u
     ::dann::ExclusiveGuard lock(idx);
     DANN_MUTATION(idx);
     DeviceGuard guard(idx->device);
-    int32_t rc = validate_cfg(idx, cfg);
+    int32_t rc = check_build_cfg(idx, cfg, "dann_insert_batch", true);
     if (rc != DANN_OK) return rc;
     if (n == 0) return DANN_OK;
     if (!slots) return DANN_EINVAL;
@@ -2863,7 +2822,7 @@ int32_t dann_insert(dann_index* idx, const dann_build_config* cfg, uint32_t slot
     ::dann::ExclusiveGuard lock(idx);
     DANN_MUTATION(idx);
     DeviceGuard guard(idx->device);
-    int32_t rc = validate_cfg(idx, cfg);
+    int32_t rc = check_build_cfg(idx, cfg, "dann_insert", true);
     if (rc != DANN_OK) return rc;
     if (cfg->max_backedges > cfg->pruned_degree) {  // config/mod.rs:308-311
         set_error("parameter \"max_backedges\" (%u) must not be greater than \"pruned_degree\" (%u)", cfg->max_backedges,
@@ -2891,7 +2850,7 @@ int32_t dann_insert_batch_candidates(dann_index* idx, const dann_build_config* c
     if (!idx) return DANN_EINVAL;
     ::dann::ExclusiveGuard lock(idx);
     DeviceGuard guard(idx->device);
-    int32_t rc = validate_cfg(idx, cfg);
+    int32_t rc = check_build_cfg(idx, cfg, "dann_insert_batch_candidates", true);
     if (rc != DANN_OK) return rc;
     if (lo > hi || hi > n) return DANN_EINVAL;
     if (n == 0 || lo == hi) return DANN_OK;
@@ -2912,7 +2871,7 @@ int32_t dann_insert_batch_commit(dann_index* idx, const dann_build_config* cfg, 
     ::dann::ExclusiveGuard lock(idx);
     DANN_MUTATION(idx);
     DeviceGuard guard(idx->device);
-    int32_t rc = validate_cfg(idx, cfg);
+    int32_t rc = check_build_cfg(idx, cfg, "dann_insert_batch_commit", true);
     if (rc != DANN_OK) return rc;
     if (n == 0) return DANN_OK;
     if (!slots || !d_pending_all) return DANN_EINVAL;
@@ -2934,7 +2893,7 @@ int32_t dann_insert_batch_commit_part(dann_index* idx, const dann_build_config* 
     ::dann::ExclusiveGuard lock(idx);
     DANN_MUTATION(idx);
     DeviceGuard guard(idx->device);
-    int32_t rc = validate_cfg(idx, cfg);
+    int32_t rc = check_build_cfg(idx, cfg, "dann_insert_batch_commit_part", true);
     if (rc != DANN_OK) return rc;
     if (n == 0) return DANN_OK;
     if (!slots || !d_pending_all) return DANN_EINVAL;
@@ -3071,7 +3030,7 @@ int32_t dann_build(dann_index* idx, const dann_build_config* cfg, uint32_t first
     ::dann::ExclusiveGuard lock(idx);
     DANN_MUTATION(idx);
     DeviceGuard guard(idx->device);
-    int32_t rc = validate_cfg(idx, cfg);
+    int32_t rc = check_build_cfg(idx, cfg, "dann_build", true);
     if (rc != DANN_OK) return rc;
     if ((uint64_t)first + n > idx->cfg.capacity) return DANN_EBOUNDS;
     if (!(growth > 0.0f) || max_batch == 0) return DANN_EINVAL;
@@ -3114,7 +3073,7 @@ int32_t dann_prune_batch(dann_index* idx, const dann_build_config* cfg, const ui
     if (!idx) return DANN_EINVAL;
     ::dann::ExclusiveGuard lock(idx);
     DeviceGuard guard(idx->device);
-    int32_t rc = validate_cfg(idx, cfg);
+    int32_t rc = check_build_cfg(idx, cfg, "dann_prune_batch", true);
     if (rc != DANN_OK) return rc;
     if (n == 0) return DANN_OK;
     if (!locs || !pool_ids || !pool_dists || !offsets || !out_adj) return DANN_EINVAL;
@@ -3156,7 +3115,7 @@ int32_t dann_prune_batch(dann_index* idx, const dann_build_config* cfg, const ui
     pa.cand = 0;
     pa.n = n;
     pa.pos0 = 0;
-    pa.pcap = next_pow2((uint32_t)maxlen);
+    pa.pcap = pow2_at_least((uint32_t)maxlen);
     pa.force_saturate = force_saturate;
     pa.out = dout.as<uint32_t>();
     pa.out_stride = ostride;

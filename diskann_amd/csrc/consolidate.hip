@@ -37,31 +37,13 @@
 namespace dann {
 namespace {
 
-constexpr uint8_t kTagRetiring = 2;     // Tag::RETIRING (diskann-inmem/src/tag.rs:81-135): not readable
 constexpr uint32_t kShortPool = 512;    // pool bounds up to this go to the short worklist
-constexpr uint32_t kMaxConsPool = 4096; // the prune kernels' largest LDS pool (build_kernels.hip kMaxPool); pools whose
-                                        // bound exceeds it are gathered in global memory (the huge worklist)
 constexpr uint32_t kChunkElems = 4096u * 512u;  // pool entries per chunk (ids + distances: 16 MiB)
 constexpr uint32_t kStatLines = 256;    // striped device counters: a workgroup adds to line blockIdx % kStatLines
 // counters per line: [0] lists rewritten without prune, [1] pools pruned, [2] largest pool, [3] distances d(vertex, c)
-// of the pruned pools, [4] pools of more than kMaxConsPool candidates, [5] those of [4] whose selected head holds equal
+// of the pruned pools, [4] pools of more than kMaxPool candidates, [5] those of [4] whose selected head holds equal
 // distances under DANN_TIE_RUST
 constexpr uint32_t kStatWords = 6;
-
-__device__ __forceinline__ bool is_deleted(const uint32_t* bm, uint32_t id, uint32_t nslots) {
-    return bm && id < nslots && ((bm[id >> 5] >> (id & 31u)) & 1u);
-}
-
-// append this lane's value to list[*count ..] with one atomic per wavefront
-__device__ __forceinline__ void wave_push(bool p, uint32_t* list, uint32_t* count, uint32_t value) {
-    const uint64_t m = ballot64(p);
-    if (m == 0) return;
-    const uint32_t leader = (uint32_t)__ffsll((unsigned long long)m) - 1u;
-    uint32_t base = 0;
-    if (lane_id() == leader) base = atomicAdd(count, (uint32_t)__popcll(m));
-    base = (uint32_t)__shfl((int)base, (int)leader);
-    if (p) list[base + mbcnt(m)] = value;
-}
 
 __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
     for (int o = 1; o < 64; o <<= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
@@ -79,7 +61,7 @@ __global__ void mark_deleted_kernel(uint32_t* bm, const uint32_t* slots, uint32_
 
 __global__ void drop_deleted_kernel(IndexView ix, const uint32_t* bm) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < ix.nslots && is_deleted(bm, i, ix.nslots)) ix.adj[(uint64_t)i * ix.adj_stride] = 0;
+    if (i < ix.nslots && in_bitmap(bm, i, ix.nslots)) ix.adj[(uint64_t)i * ix.adj_stride] = 0;
 }
 
 struct ConsScanArgs {
@@ -90,7 +72,7 @@ struct ConsScanArgs {
     uint32_t* claim;        // explicit ids: bitmap of the vertices already claimed (the first occurrence works), else null
     uint32_t pruned_degree;
     uint8_t* kinds;         // n: ConsolidateKind
-    uint32_t* work[3];      // short (bound <= kShortPool), long (<= kMaxConsPool), huge worklists
+    uint32_t* work[3];      // short (bound <= kShortPool), long (<= kMaxPool), huge worklists (gathered in global memory)
     uint32_t* counts;       // [0..2] entries of each worklist, [3..5] the largest bound in each
 };
 
@@ -101,7 +83,7 @@ __global__ __launch_bounds__(64) void cons_scan_kernel(ConsScanArgs a) {
     const uint32_t item = blockIdx.x * 4u + sub;
     const bool have = item < a.n;
     const uint32_t v = have ? (a.ids ? a.ids[item] : item) : 0u;
-    const bool del = have && is_deleted(a.bm, v, a.ix.nslots);
+    const bool del = have && in_bitmap(a.bm, v, a.ix.nslots);
     int first = 1;
     if (have && !del && a.claim && sl == 0) {
         const uint32_t bit = 1u << (v & 31u);
@@ -115,7 +97,7 @@ __global__ __launch_bounds__(64) void cons_scan_kernel(ConsScanArgs a) {
     uint32_t ndel = 0, bound = 0;
     for (uint32_t e = sl; e < len; e += 16u) {
         const uint32_t id = arow[1 + e];
-        if (is_deleted(a.bm, id, a.ix.nslots)) {
+        if (in_bitmap(a.bm, id, a.ix.nslots)) {
             ++ndel;
             bound += min(a.ix.adj[(uint64_t)id * a.ix.adj_stride], a.ix.max_degree);
         } else {
@@ -127,7 +109,7 @@ __global__ __launch_bounds__(64) void cons_scan_kernel(ConsScanArgs a) {
         bound += (uint32_t)__shfl_xor((int)bound, o);
     }
     const bool want = scan && (ndel != 0u || len > a.pruned_degree);
-    const uint32_t cls = bound <= kShortPool ? 0u : bound <= kMaxConsPool ? 1u : 2u;
+    const uint32_t cls = bound <= kShortPool ? 0u : bound <= kMaxPool ? 1u : 2u;
     for (uint32_t c = 0; c < 3; ++c) {
         wave_push(want && cls == c && sl == 0, a.work[c], &a.counts[c], item);
         const uint32_t mb = wave_max(want && cls == c ? bound : 0u);
@@ -153,38 +135,6 @@ struct ConsGatherArgs {
     uint32_t* err;          // set when a pool outgrows its bound (a bug, never an input)
 };
 
-// Appends the lanes' ids (kEmpty = none) that are not yet in the pool -- an id repeated among the lanes goes in once, from
-// its lowest lane: list order -- and returns the new length.  `hash` (hmask + 1 entries, kEmpty = free, at most half full)
-// is the set of the pool's ids: one probe sequence per new candidate instead of a scan of the pool.
-__device__ __forceinline__ uint32_t append_unique(uint32_t* pool, uint32_t* hash, uint32_t hmask, uint32_t cnt, uint32_t pcap,
-                                                  uint32_t id, uint32_t* err) {
-    const uint32_t lane = lane_id();
-    bool take = id != kEmpty;
-    for (int k = 0; k < 64; ++k) {
-        const uint32_t o = (uint32_t)__shfl((int)id, k);
-        take &= !((uint32_t)k < lane && o == id);
-    }
-    if (take) {
-        uint32_t h = (id * 2654435761u) & hmask;
-        for (uint32_t probe = 0; probe <= hmask; ++probe) {
-            const uint32_t old = atomicCAS(&hash[h], kEmpty, id);
-            if (old == kEmpty) break;
-            if (old == id) {
-                take = false;
-                break;
-            }
-            h = (h + 1u) & hmask;
-        }
-    }
-    const uint64_t tm = ballot64(take);
-    const uint32_t pos = cnt + mbcnt(tm);
-    if (take) {
-        if (pos < pcap) pool[pos] = id;
-        else atomicOr(err, 1u);
-    }
-    return min(cnt + (uint32_t)__popcll(tm), pcap);
-}
-
 template <int DT, int OP, bool NORM>
 __global__ __launch_bounds__(kWave) void cons_gather_kernel(ConsGatherArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -208,7 +158,7 @@ __global__ __launch_bounds__(kWave) void cons_gather_kernel(ConsGatherArgs a) {
     for (uint32_t e0 = 0; e0 < len; e0 += kWave) {
         const uint32_t e = e0 + lane;
         const uint32_t id = e < len ? arow[1 + e] : kEmpty;
-        const bool del = e < len && is_deleted(a.bm, id, nslots);
+        const bool del = e < len && in_bitmap(a.bm, id, nslots);
         const uint64_t dm = ballot64(del);
         if (del) dl[ndel + mbcnt(dm)] = id;
         ndel += (uint32_t)__popcll(dm);
@@ -230,7 +180,7 @@ __global__ __launch_bounds__(kWave) void cons_gather_kernel(ConsGatherArgs a) {
         for (uint32_t e0 = 0; e0 < dlen; e0 += kWave) {
             const uint32_t e = e0 + lane;
             const uint32_t id = e < dlen ? drow[1 + e] : kEmpty;
-            const bool live = e < dlen && id != v && !is_deleted(a.bm, id, nslots);
+            const bool live = e < dlen && id != v && !in_bitmap(a.bm, id, nslots);
             cnt = append_unique(pool, hash, hmask, cnt, a.pcap, live ? id : kEmpty, a.err);
         }
     }
@@ -261,28 +211,6 @@ __global__ __launch_bounds__(kWave) void cons_gather_kernel(ConsGatherArgs a) {
 
 constexpr auto kConsGather = [](auto r) { using R = decltype(r); return KernelOf<cons_gather_kernel<R::dt, R::op, R::norm>>{}; };
 
-__device__ __forceinline__ uint64_t select_key(float d, uint32_t pos) {  // build_kernels.hip sort_key: (distance, position)
-    uint32_t u = __builtin_bit_cast(uint32_t, d + 0.0f);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((uint64_t)u << 32) | pos;
-}
-
-// ascending bitonic sort of keys[0, P), P a power of two, by one workgroup
-__device__ void block_bitonic(uint64_t* keys, uint32_t P) {
-    for (uint32_t k = 2; k <= P; k <<= 1)
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            for (uint32_t t = threadIdx.x; t < (P >> 1); t += blockDim.x) {
-                const uint32_t i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), p = i | j;
-                const uint64_t x = keys[i], y = keys[p];
-                if ((x > y) == ((i & k) == 0)) {
-                    keys[i] = y;
-                    keys[p] = x;
-                }
-            }
-            __syncthreads();
-        }
-}
-
 struct ConsSelectArgs {
     const uint32_t* in_ids;  // gathered pools: stride in_stride, lengths in_cnt (0 = nothing to prune)
     const float* in_d;
@@ -291,13 +219,13 @@ struct ConsSelectArgs {
     uint64_t* keys;          // scratch, in_stride per item
     uint32_t keep;           // max_occlusion_size
     uint32_t tie_rust;
-    uint32_t* out_ids;       // stride kMaxConsPool
+    uint32_t* out_ids;       // stride kMaxPool
     float* out_d;
     uint32_t* out_cnt;
     unsigned long long* stats;
 };
 
-// Pools of more than kMaxConsPool candidates: SortedNeighbors::new sorts the pool and keeps the `keep` nearest.  The `keep`
+// Pools of more than kMaxPool candidates: SortedNeighbors::new sorts the pool and keeps the `keep` nearest.  The `keep`
 // smallest (distance, position) keys are selected exactly and handed on in pool order, so the prune kernels' own sort
 // of them yields the same list under DANN_TIE_POSITION, and under DANN_TIE_RUST wherever the selected head has no equal
 // distances (the pools where it has are counted: there Rust's order of the full pool is not reproduced).
@@ -306,9 +234,9 @@ __global__ __launch_bounds__(256) void cons_select_kernel(ConsSelectArgs a) {
     const uint32_t cnt = a.in_cnt[b];
     const uint32_t* ids = a.in_ids + (uint64_t)b * a.in_stride;
     const float* d = a.in_d + (uint64_t)b * a.in_stride;
-    uint32_t* oid = a.out_ids + (uint64_t)b * kMaxConsPool;
-    float* od = a.out_d + (uint64_t)b * kMaxConsPool;
-    if (cnt <= kMaxConsPool) {
+    uint32_t* oid = a.out_ids + (uint64_t)b * kMaxPool;
+    float* od = a.out_d + (uint64_t)b * kMaxPool;
+    if (cnt <= kMaxPool) {
         for (uint32_t i = t; i < cnt; i += blockDim.x) {
             oid[i] = ids[i];
             od[i] = d[i];
@@ -319,7 +247,7 @@ __global__ __launch_bounds__(256) void cons_select_kernel(ConsSelectArgs a) {
     uint64_t* keys = a.keys + (uint64_t)b * a.in_stride;
     uint32_t P = 64;
     while (P < cnt) P <<= 1;
-    for (uint32_t i = t; i < P; i += blockDim.x) keys[i] = i < cnt ? select_key(d[i], i) : ~0ull;
+    for (uint32_t i = t; i < P; i += blockDim.x) keys[i] = i < cnt ? dist_key(d[i], i) : ~0ull;
     __syncthreads();
     block_bitonic(keys, P);
     const uint32_t keep = min(a.keep, cnt);
@@ -345,27 +273,6 @@ __global__ __launch_bounds__(256) void cons_select_kernel(ConsSelectArgs a) {
         if (tied) atomicAdd(&st[5], 1ull);
     }
 }
-
-uint32_t pow2_at_least(uint32_t x) {
-    uint32_t p = 64;
-    while (p < x) p <<= 1;
-    return p;
-}
-
-// device memory of one call
-struct CallBuf {
-    void* p = nullptr;
-    ~CallBuf() { reset(); }
-    void reset() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-    template <class T>
-    T* as() {
-        return reinterpret_cast<T*>(p);
-    }
-};
 
 }  // namespace
 
@@ -408,7 +315,7 @@ int32_t dann_delete_points(dann_index* idx, const uint32_t* slots, uint32_t n) t
     }
     DeviceGuard guard(idx->device);
     if (int32_t rc = ensure_deleted_bitmap(idx)) return rc;
-    CallBuf d_slots;
+    DevBuf d_slots;
     DANN_HIP(d_slots.alloc((size_t)n * 4));
     hipStream_t st = idx->main.stream;
     DANN_HIP(hipMemcpyAsync(d_slots.p, slots, (size_t)n * 4, hipMemcpyHostToDevice, st));
@@ -448,25 +355,10 @@ int32_t dann_consolidate(dann_index* idx, const dann_build_config* cfg, const ui
     if (!idx || !cfg) return DANN_EINVAL;
     ::dann::ExclusiveGuard lock(idx);
     DANN_MUTATION(idx);
-    if (idx->cfg.dtype == DT_PQ) {
-        set_error("dann_consolidate: not defined on DANN_PQ rows (consolidate the full-precision index)");
-        return DANN_EUNSUPPORTED;
-    }
-    int op;
-    bool norm;
-    if (!resolve_metric(idx->cfg.dtype, idx->cfg.metric, &op, &norm)) {
-        set_error("metric %d is not defined for dtype %d", idx->cfg.metric, idx->cfg.dtype);
-        return DANN_EUNSUPPORTED;
-    }
-    if (cfg->pruned_degree == 0 || cfg->max_degree < cfg->pruned_degree || cfg->max_degree > idx->cfg.max_degree ||
-        !(cfg->alpha >= 1.0f) || (flags & ~(uint32_t)DANN_CONSOLIDATE_DROP_DELETED)) {
-        set_error("dann_consolidate: invalid config (pruned_degree %u, max_degree %u (provider %u), alpha %g, flags %u)",
-                  cfg->pruned_degree, cfg->max_degree, idx->cfg.max_degree, (double)cfg->alpha, flags);
+    if (int32_t rc = check_build_cfg(idx, cfg, "dann_consolidate", false)) return rc;
+    if (flags & ~(uint32_t)DANN_CONSOLIDATE_DROP_DELETED) {
+        set_error("dann_consolidate: unknown flags %u", flags);
         return DANN_EINVAL;
-    }
-    if (cfg->max_occlusion_size > kMaxConsPool) {
-        set_error("max_occlusion_size %u exceeds the supported %u", cfg->max_occlusion_size, kMaxConsPool);
-        return DANN_EUNSUPPORTED;
     }
     if (ids) {
         if (n == 0) return DANN_OK;
@@ -487,7 +379,7 @@ int32_t dann_consolidate(dann_index* idx, const dann_build_config* cfg, const ui
     }
     // per-call scratch: ids + claim bitmap, kinds, the two worklists, counts, striped stats, error word
     const size_t claim_words = ids ? (idx->nslots + 31u) / 32u : 0u;
-    CallBuf d_ids, d_claim, d_kinds, d_work, d_meta, d_stats;
+    DevBuf d_ids, d_claim, d_kinds, d_work, d_meta, d_stats;
     if (ids) {
         DANN_HIP(d_ids.alloc((size_t)n * 4));
         DANN_HIP(hipMemcpyAsync(d_ids.p, ids, (size_t)n * 4, hipMemcpyHostToDevice, st));
@@ -523,7 +415,7 @@ int32_t dann_consolidate(dann_index* idx, const dann_build_config* cfg, const ui
     // the matrix-core path keeps a Gram block per item in the index's build scratch: chunks of it stay at the build's
     // batch scale
     const uint32_t max_chunk = prune_pools_use_gram(idx) ? 2048u : 8192u;
-    CallBuf c_locs, c_ids, c_d, c_cnt, c_hash, c_keys, c_sel_ids, c_sel_d, c_sel_cnt;
+    DevBuf c_locs, c_ids, c_d, c_cnt, c_hash, c_keys, c_sel_ids, c_sel_d, c_sel_cnt;
     size_t c_elems = 0, c_items = 0;
     for (int cls = 0; cls < 3; ++cls) {
         const uint32_t nwork = h_counts[cls];
@@ -534,25 +426,21 @@ int32_t dann_consolidate(dann_index* idx, const dann_build_config* cfg, const ui
             std::min<uint32_t>(nwork, std::max<uint32_t>(huge ? 16u : 256u, std::min<uint32_t>(max_chunk, kChunkElems / pcap)));
         if ((size_t)chunk * pcap > c_elems || chunk > c_items) {
             // (earlier classes' buffers serve a later one when large enough; hipFree waits for the work queued on them)
-            c_ids.reset();
-            c_d.reset();
             c_elems = std::max<size_t>(c_elems, (size_t)chunk * pcap);
             DANN_HIP(c_ids.alloc(c_elems * 4));
             DANN_HIP(c_d.alloc(c_elems * 4));
             if (chunk > c_items) {
-                c_locs.reset();
-                c_cnt.reset();
                 c_items = chunk;
                 DANN_HIP(c_locs.alloc(c_items * 4));
                 DANN_HIP(c_cnt.alloc(c_items * 4));
                 DANN_HIP(hipMemsetAsync(c_locs.p, 0, c_items * 4, st));
             }
         }
-        if (huge) {  // global pools: hash sets, sort keys and the selected heads (stride kMaxConsPool)
+        if (huge) {  // global pools: hash sets, sort keys and the selected heads (stride kMaxPool)
             DANN_HIP(c_hash.alloc((size_t)chunk * pcap * 8));
             DANN_HIP(c_keys.alloc((size_t)chunk * pcap * 8));
-            DANN_HIP(c_sel_ids.alloc((size_t)chunk * kMaxConsPool * 4));
-            DANN_HIP(c_sel_d.alloc((size_t)chunk * kMaxConsPool * 4));
+            DANN_HIP(c_sel_ids.alloc((size_t)chunk * kMaxPool * 4));
+            DANN_HIP(c_sel_d.alloc((size_t)chunk * kMaxPool * 4));
             DANN_HIP(c_sel_cnt.alloc((size_t)chunk * 4));
         }
         ConsGatherArgs ga;
@@ -592,7 +480,7 @@ int32_t dann_consolidate(dann_index* idx, const dann_build_config* cfg, const ui
             if (huge) {
                 hipLaunchKernelGGL(cons_select_kernel, dim3(m), dim3(256), 0, st, sel);
                 DANN_HIP(hipGetLastError());
-                rc = prune_pools_into_rows(idx, *cfg, ga.locs, sel.out_ids, sel.out_d, sel.out_cnt, kMaxConsPool, m,
+                rc = prune_pools_into_rows(idx, *cfg, ga.locs, sel.out_ids, sel.out_d, sel.out_cnt, kMaxPool, m,
                                            &used_gram);
             } else {
                 rc = prune_pools_into_rows(idx, *cfg, ga.locs, ga.pool_ids, ga.pool_d, ga.counts, pcap, m, &used_gram);

@@ -18,6 +18,7 @@
 
 #include "../../include/dann.h"
 #include "../../include/dann_debug.h"
+#include "device_buffer.h"  // DevBuf, pow2_at_least
 #include "row_dispatch.h"  // visit_row_op, RowSet, kNoMetric / kNoRow
 #include "search_args.h"  // IndexView, ServerView, SearchArgs, VisitedCalib
 #include "small_calls.h"
@@ -411,6 +412,12 @@ bool server_quiesce(dann_index* idx);  // server.hip: the resident kernel leaves
         return DANN_EHIP;                                                                                             \
     }                                                                                                                 \
     (void)0
+// the prune kernels' largest candidate pool (their LDS layout); larger pools are refused, or cut to it first
+constexpr uint32_t kMaxPool = 4096;
+// build_kernels.hip: a dann_build_config against the index, for every entry point that prunes (`what` names it in the
+// message).  DANN_EUNSUPPORTED: PQ rows, a metric the row type does not have, max_occlusion_size > kMaxPool;
+// DANN_EINVAL: the rest.  Only the build path searches, so only it needs l_build.
+int32_t check_build_cfg(const dann_index* idx, const dann_build_config* cfg, const char* what, bool need_l_build);
 constexpr uint32_t kTieWorkBytes = 512 + 2048;
 constexpr uint32_t kMaxSearchCtx = 16;
 // a search context for one concurrent call: from the pool, created on demand (at most kMaxSearchCtx), else waits

@@ -8,6 +8,7 @@
 //                           diskann/src/graph/internal/prune.rs:212-215
 #include "dann_device.h"
 #include "dann_internal.h"
+#include "wave_lists.h"
 
 namespace dann {
 namespace {
@@ -135,30 +136,9 @@ __global__ __launch_bounds__(kWave) void rerank_kernel(IndexView ix, const void*
         }
     }
     __syncthreads();
-    for (uint32_t i = lane; i < pcap; i += kWave) {
-        uint64_t key = ~0ull;
-        if (i < n) {
-            uint32_t u = __builtin_bit_cast(uint32_t, cd[i] + 0.0f);
-            u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-            key = ((uint64_t)u << 32) | i;
-        }
-        keys[i] = key;
-    }
+    for (uint32_t i = lane; i < pcap; i += kWave) keys[i] = i < n ? dist_key(cd[i], i) : ~0ull;
     __syncthreads();
-    for (uint32_t kk = 2; kk <= pcap; kk <<= 1) {
-        for (uint32_t j = kk >> 1; j > 0; j >>= 1) {
-            for (uint32_t t = lane; t < (pcap >> 1); t += kWave) {
-                const uint32_t i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u));
-                const uint32_t p = i | j;
-                const uint64_t a = keys[i], b = keys[p];
-                if ((a > b) == ((i & kk) == 0)) {
-                    keys[i] = b;
-                    keys[p] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    block_bitonic(keys, pcap, kWave);
     for (uint32_t r = lane; r < k; r += kWave) {
         uint32_t id = kEmpty;
         float d = __builtin_inff();

@@ -47,9 +47,6 @@
 namespace dann {
 namespace {
 
-constexpr uint8_t kTagRetiring = 2;      // Tag::RETIRING (diskann-inmem/src/tag.rs:81-135)
-constexpr uint8_t kTagReadable = 254;    // Tag::can_read: tag >= PUBLISHED
-constexpr uint32_t kMaxIdelPool = 4096;  // the prune kernels' largest pool stride (build_kernels.hip kMaxPool)
 constexpr uint32_t kMaxIds = 1u << 20;   // id positions are 20 bits of an edge key
 constexpr uint32_t kWorkChunk = 256;     // ids per work-kernel launch of TwoHopAndOneHop (bounds the hash sets)
 constexpr uint32_t kMaxTwoHopDegree = 256;  // TwoHopAndOneHop: the union of up to R + R^2 candidates per id
@@ -59,31 +56,8 @@ constexpr uint32_t kMaxL = 2048;         // VisitedAndTopK: the largest l_value 
 constexpr uint32_t kStatWords = 8;
 
 __device__ __forceinline__ bool unreadable(const IndexView& ix, const uint32_t* bm, uint32_t id) {
-    if (id >= ix.nslots) return true;
-    if (bm && ((bm[id >> 5] >> (id & 31u)) & 1u)) return true;
+    if (id >= ix.nslots || in_bitmap(bm, id, ix.nslots)) return true;
     return ix.tag_off && ix.rows[(uint64_t)id * ix.row_stride + ix.tag_off] < kTagReadable;
-}
-
-__device__ __forceinline__ bool in_bitmap(const uint32_t* bm, uint32_t id, uint32_t nslots) {
-    return id < nslots && ((bm[id >> 5] >> (id & 31u)) & 1u);
-}
-
-// append this lane's value to list[*count ..] with one atomic per wavefront
-__device__ __forceinline__ void wave_push(bool p, uint32_t* list, uint32_t* count, uint32_t value) {
-    const uint64_t m = ballot64(p);
-    if (m == 0) return;
-    const uint32_t leader = (uint32_t)__ffsll((unsigned long long)m) - 1u;
-    uint32_t base = 0;
-    if (lane_id() == leader) base = atomicAdd(count, (uint32_t)__popcll(m));
-    base = (uint32_t)__shfl((int)base, (int)leader);
-    if (p) list[base + mbcnt(m)] = value;
-}
-
-// (order-preserving distance bits, payload); d + 0 makes the two zeros one value
-__device__ __forceinline__ unsigned long long dist_key(float d, uint32_t payload) {
-    uint32_t u = __builtin_bit_cast(uint32_t, d + 0.0f);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)u << 32) | payload;
 }
 
 // rust_order::sort_keys_unstable as a real call, as the search kernels hold it (search_kernel_impl.h)
@@ -255,37 +229,6 @@ struct WorkArgs {
     uint32_t* err;
 };
 
-// Appends the lanes' ids (kEmpty = none) that are not yet in the pool, each once from its lowest lane, and returns the
-// new length (consolidate.hip append_unique: `hash` is the pool's set, kEmpty = free, at most half full).
-__device__ __forceinline__ uint32_t append_unique(uint32_t* pool, uint32_t* hash, uint32_t hmask, uint32_t cnt, uint32_t pcap,
-                                                  uint32_t id, uint32_t* err) {
-    const uint32_t lane = lane_id();
-    bool take = id != kEmpty;
-    for (int k = 0; k < 64; ++k) {
-        const uint32_t o = (uint32_t)__shfl((int)id, k);
-        take &= !((uint32_t)k < lane && o == id);
-    }
-    if (take) {
-        uint32_t h = (id * 2654435761u) & hmask;
-        for (uint32_t probe = 0; probe <= hmask; ++probe) {
-            const uint32_t old = atomicCAS(&hash[h], kEmpty, id);
-            if (old == kEmpty) break;
-            if (old == id) {
-                take = false;
-                break;
-            }
-            h = (h + 1u) & hmask;
-        }
-    }
-    const uint64_t tm = ballot64(take);
-    const uint32_t pos = cnt + mbcnt(tm);
-    if (take) {
-        if (pos < pcap) pool[pos] = id;
-        else atomicOr(err, 1u);
-    }
-    return min(cnt + (uint32_t)__popcll(tm), pcap);
-}
-
 __global__ __launch_bounds__(kWave) void idel_work_kernel(WorkArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint32_t* one_l = reinterpret_cast<uint32_t*>(smem);  // max_degree
@@ -389,22 +332,6 @@ struct EdgeArgs {
     uint32_t* err;
 };
 
-// ascending bitonic sort of keys[0, P) (P a power of two) in LDS by one wavefront
-__device__ void wave_bitonic(unsigned long long* keys, uint32_t P) {
-    for (uint32_t k = 2; k <= P; k <<= 1)
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            for (uint32_t t = threadIdx.x; t < (P >> 1); t += kWave) {
-                const uint32_t i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), q = i | j;
-                const unsigned long long x = keys[i], y = keys[q];
-                if ((x > y) == ((i & k) == 0)) {
-                    keys[i] = y;
-                    keys[q] = x;
-                }
-            }
-            __syncthreads();
-        }
-}
-
 template <int DT, int OP, bool NORM>
 __global__ __launch_bounds__(kWave) void idel_edge_kernel(EdgeArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -457,7 +384,7 @@ __global__ __launch_bounds__(kWave) void idel_edge_kernel(EdgeArgs a) {
             while (Q < cnt) Q <<= 1;
             for (uint32_t j = lane; j < Q; j += kWave) keys[j] = j < cnt ? dist_key(pd[j], j) : ~0ull;
             __syncthreads();
-            wave_bitonic(keys, Q);
+            block_bitonic(keys, Q, kWave);
         }
         __syncthreads();
         uint32_t base = 0;
@@ -653,50 +580,6 @@ __global__ __launch_bounds__(kWave) void idel_drop_kernel(DropArgs a, uint32_t n
     if (lane == 0) row[0] = cnt;
 }
 
-// device memory of one call
-struct CallBuf {
-    void* p = nullptr;
-    ~CallBuf() { reset(); }
-    void reset() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-    template <class T>
-    T* as() {
-        return reinterpret_cast<T*>(p);
-    }
-};
-
-int32_t check_cfg(const dann_index* idx, const dann_build_config* cfg, const char* what) {
-    if (idx->cfg.dtype == DT_PQ) {
-        set_error("%s: not defined on DANN_PQ rows", what);
-        return DANN_EUNSUPPORTED;
-    }
-    int op;
-    bool norm;
-    if (!resolve_metric(idx->cfg.dtype, idx->cfg.metric, &op, &norm)) {
-        set_error("metric %d is not defined for dtype %d", idx->cfg.metric, idx->cfg.dtype);
-        return DANN_EUNSUPPORTED;
-    }
-    if (cfg->pruned_degree == 0 || cfg->max_degree < cfg->pruned_degree || cfg->max_degree > idx->cfg.max_degree ||
-        !(cfg->alpha >= 1.0f)) {
-        set_error("%s: invalid config (pruned_degree %u, max_degree %u (provider %u), alpha %g)", what, cfg->pruned_degree,
-                  cfg->max_degree, idx->cfg.max_degree, (double)cfg->alpha);
-        return DANN_EINVAL;
-    }
-    if (cfg->max_occlusion_size > kMaxIdelPool) {
-        set_error("max_occlusion_size %u exceeds the supported %u", cfg->max_occlusion_size, kMaxIdelPool);
-        return DANN_EUNSUPPORTED;
-    }
-    return DANN_OK;
-}
-
-uint32_t pow2_at_least(uint32_t x, uint32_t p = 64) {
-    while (p < x) p <<= 1;
-    return p;
-}
-
 }  // namespace
 }  // namespace dann
 
@@ -709,7 +592,7 @@ int32_t dann_inplace_delete(dann_index* idx, const dann_build_config* cfg, const
     if (!idx || !cfg || !prm) return DANN_EINVAL;
     ::dann::ExclusiveGuard lock(idx);
     DANN_MUTATION(idx);
-    if (int32_t rc = check_cfg(idx, cfg, "dann_inplace_delete")) return rc;
+    if (int32_t rc = check_build_cfg(idx, cfg, "dann_inplace_delete", false)) return rc;
     if (prm->method > DANN_INPLACE_ONE_HOP) {
         set_error("dann_inplace_delete: unknown method %u", prm->method);
         return DANN_EINVAL;
@@ -785,7 +668,7 @@ int32_t dann_inplace_delete(dann_index* idx, const dann_build_config* cfg, const
     const uint32_t hmask = twohop ? pow2_at_least(2u * icap) - 1u : 0u;
     const uint32_t wchunk = twohop ? std::min(kWorkChunk, nu) : nu;
     const uint32_t schunk = vtk ? (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>({nu, 1024u, (256ull << 20) / ((uint64_t)words * 4)})) : 0u;
-    CallBuf d_ids, d_callbm, d_one, d_one_cnt, d_rc, d_rc_cnt, d_in, d_in_cnt, d_hash, d_vis, d_meta, d_stats, d_old;
+    DevBuf d_ids, d_callbm, d_one, d_one_cnt, d_rc, d_rc_cnt, d_in, d_in_cnt, d_hash, d_vis, d_meta, d_stats, d_old;
     DANN_HIP(d_ids.alloc((size_t)nu * 4));
     DANN_HIP(hipMemcpyAsync(d_ids.p, uid.data(), (size_t)nu * 4, hipMemcpyHostToDevice, st));
     DANN_HIP(d_callbm.alloc((size_t)words * 4));
@@ -824,7 +707,7 @@ int32_t dann_inplace_delete(dann_index* idx, const dann_build_config* cfg, const
     };
 
     // 2. - 3. work lists, replacement edges, the sort: no row is written yet, so every failure is rolled back
-    CallBuf d_keys, d_keys2, d_vals, d_vals2, d_heads, d_tmp;
+    DevBuf d_keys, d_keys2, d_vals, d_vals2, d_heads, d_tmp;
     uint32_t E = 0, h_meta[4] = {0, 0, 0, 0};
     auto prepare = [&]() -> int32_t {
         if (vtk) {
@@ -925,9 +808,9 @@ int32_t dann_inplace_delete(dann_index* idx, const dann_build_config* cfg, const
             set_error("dann_inplace_delete: a work list outgrew its bound");
             return DANN_EINTERNAL;
         }
-        if (h_meta[1] && pow2_at_least(R + h_meta[2]) > kMaxIdelPool) {
+        if (h_meta[1] && pow2_at_least(R + h_meta[2]) > kMaxPool) {
             set_error("dann_inplace_delete: a vertex would receive %u new edges in one call (pool > %u): split the "
-                      "minibatch", h_meta[2], kMaxIdelPool);
+                      "minibatch", h_meta[2], kMaxPool);
             return DANN_EUNSUPPORTED;
         }
         return DANN_OK;
@@ -943,7 +826,7 @@ int32_t dann_inplace_delete(dann_index* idx, const dann_build_config* cfg, const
     // leaves the marks and the rows written so far.
     if (nsrc) {
         const uint32_t chunk = std::min<uint32_t>(nsrc, prune_pools_use_gram(idx) ? 2048u : 8192u);
-        CallBuf c_locs, c_ids, c_d, c_cnt;
+        DevBuf c_locs, c_ids, c_d, c_cnt;
         DANN_HIP(c_locs.alloc((size_t)chunk * 4));
         DANN_HIP(hipMemsetAsync(c_locs.p, 0, (size_t)chunk * 4, st));
         DANN_HIP(c_ids.alloc((size_t)chunk * pcap * 4));
@@ -1029,7 +912,7 @@ int32_t dann_drop_deleted_neighbors(dann_index* idx, const dann_build_config* cf
     DeviceGuard guard(idx->device);
     hipStream_t st = idx->main.stream;
     const IndexView ix = idx->view();
-    CallBuf d_ids, d_kinds;
+    DevBuf d_ids, d_kinds;
     if (ids) {
         DANN_HIP(d_ids.alloc((size_t)m * 4));
         DANN_HIP(hipMemcpyAsync(d_ids.p, uid.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));

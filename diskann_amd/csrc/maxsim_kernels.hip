@@ -23,6 +23,7 @@
 
 #include "dann_device.h"
 #include "dann_internal.h"
+#include "wave_lists.h"
 
 namespace dann {
 namespace {
@@ -310,30 +311,10 @@ __global__ __launch_bounds__(kMsThreads) void chamfer_sort_kernel(const uint32_t
         n += total;
         __syncthreads();
     }
-    for (uint32_t i = tid; i < pcap; i += kMsThreads) {
-        uint64_t key = ~0ull;
-        if (i < n) {
-            uint32_t u = __builtin_bit_cast(uint32_t, chamfer[(uint64_t)qi * stride + pos_of[i]] + 0.0f);
-            u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-            key = ((uint64_t)u << 32) | i;
-        }
-        keys[i] = key;
-    }
+    for (uint32_t i = tid; i < pcap; i += kMsThreads)
+        keys[i] = i < n ? dist_key(chamfer[(uint64_t)qi * stride + pos_of[i]], i) : ~0ull;
     __syncthreads();
-    for (uint32_t kk = 2; kk <= pcap; kk <<= 1) {
-        for (uint32_t j = kk >> 1; j > 0; j >>= 1) {
-            for (uint32_t t = tid; t < (pcap >> 1); t += kMsThreads) {
-                const uint32_t i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u));
-                const uint32_t q = i | j;
-                const uint64_t x = keys[i], y = keys[q];
-                if ((x > y) == ((i & kk) == 0)) {
-                    keys[i] = y;
-                    keys[q] = x;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    block_bitonic(keys, pcap, kMsThreads);
     for (uint32_t r = tid; r < k; r += kMsThreads) {
         uint32_t id = kEmpty;
         float d = __builtin_inff();

@@ -8,13 +8,6 @@
 namespace dann {
 namespace {
 
-struct MmBuf {
-    void* p = nullptr;
-    ~MmBuf() {
-        if (p) (void)hipFree(p);
-    }
-};
-
 // f32::min / f32::max: a NaN operand loses
 __device__ __forceinline__ float rust_min(float a, float b) { return a != a ? b : b != b ? a : (b < a ? b : a); }
 __device__ __forceinline__ float rust_max(float a, float b) { return a != a ? b : b != b ? a : (b > a ? b : a); }
@@ -117,11 +110,11 @@ extern "C" int32_t dann_minmax_compress(int32_t device, int32_t bits, const floa
     if (device >= 0) DANN_HIP(hipSetDevice(device));
     const size_t lb = kMmHeader + sq_code_bytes(48 + bits, dim);
     const size_t xb = (size_t)n * dim * 4, ob = (size_t)n * lb;
-    MmBuf dx, dout, dloss, dflag;
-    DANN_HIP(hipMalloc(&dx.p, xb));
-    DANN_HIP(hipMalloc(&dout.p, ob));
-    DANN_HIP(hipMalloc(&dloss.p, (size_t)n * 4));
-    DANN_HIP(hipMalloc(&dflag.p, 4));
+    DevBuf dx, dout, dloss, dflag;
+    DANN_HIP(dx.alloc(xb));
+    DANN_HIP(dout.alloc(ob));
+    DANN_HIP(dloss.alloc((size_t)n * 4));
+    DANN_HIP(dflag.alloc(4));
     DANN_HIP(hipMemcpy(dx.p, x, xb, hipMemcpyHostToDevice));
     DANN_HIP(hipMemset(dout.p, 0, ob));
     DANN_HIP(hipMemset(dflag.p, 0, 4));

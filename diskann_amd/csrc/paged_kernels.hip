@@ -324,17 +324,11 @@ int32_t launch_paged(const PagedArgs& a, hipStream_t stream) {
     return DANN_EUNSUPPORTED;
 }
 
-struct Dev {
-    void* p = nullptr;
-    ~Dev() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n, int fill = -1) {
-        hipError_t e = hipMalloc(&p, n ? n : 1);
-        if (e == hipSuccess && fill >= 0) e = hipMemset(p, fill, n ? n : 1);
-        return e;
-    }
-};
+// a session buffer of n bytes, every byte `fill`
+hipError_t alloc_filled(DevBuf& b, size_t n, int fill) {
+    const hipError_t e = b.alloc(n);
+    return e == hipSuccess ? hipMemset(b.p, fill, n ? n : 1) : e;
+}
 
 }  // namespace
 }  // namespace dann
@@ -344,8 +338,8 @@ using namespace dann;
 struct dann_paged {
     dann_index* idx = nullptr;
     PagedArgs a;
-    Dev q, ids0, ids1, d0, d1, which, base, size, vt, vtc, cids, cd, cn, cnext, stats;
-    Dev out_ids, out_d, out_n;
+    DevBuf q, ids0, ids1, d0, d1, which, base, size, vt, vtc, cids, cd, cn, cnext, stats;
+    DevBuf out_ids, out_d, out_n;
     uint32_t out_k = 0;
 };
 
@@ -397,16 +391,16 @@ int32_t dann_paged_begin(dann_index* idx, const void* queries, uint32_t nq, uint
     if ((e = s->ids1.alloc((size_t)nq * cap * 4)) != hipSuccess) return fail(e);
     if ((e = s->d0.alloc((size_t)nq * cap * 4)) != hipSuccess) return fail(e);
     if ((e = s->d1.alloc((size_t)nq * cap * 4)) != hipSuccess) return fail(e);
-    if ((e = s->which.alloc((size_t)nq * 4, 0)) != hipSuccess) return fail(e);
-    if ((e = s->base.alloc((size_t)nq * 4, 0)) != hipSuccess) return fail(e);
-    if ((e = s->size.alloc((size_t)nq * 4, 0)) != hipSuccess) return fail(e);
-    if ((e = s->vt.alloc(((size_t)nq << vbits) * 4, 0xFF)) != hipSuccess) return fail(e);
-    if ((e = s->vtc.alloc((size_t)nq * 4, 0)) != hipSuccess) return fail(e);
+    if ((e = alloc_filled(s->which, (size_t)nq * 4, 0)) != hipSuccess) return fail(e);
+    if ((e = alloc_filled(s->base, (size_t)nq * 4, 0)) != hipSuccess) return fail(e);
+    if ((e = alloc_filled(s->size, (size_t)nq * 4, 0)) != hipSuccess) return fail(e);
+    if ((e = alloc_filled(s->vt, ((size_t)nq << vbits) * 4, 0xFF)) != hipSuccess) return fail(e);
+    if ((e = alloc_filled(s->vtc, (size_t)nq * 4, 0)) != hipSuccess) return fail(e);
     if ((e = s->cids.alloc((size_t)nq * l_value * 4)) != hipSuccess) return fail(e);
     if ((e = s->cd.alloc((size_t)nq * l_value * 4)) != hipSuccess) return fail(e);
-    if ((e = s->cn.alloc((size_t)nq * 4, 0)) != hipSuccess) return fail(e);
-    if ((e = s->cnext.alloc((size_t)nq * 4, 0)) != hipSuccess) return fail(e);
-    if ((e = s->stats.alloc((size_t)nq * sizeof(dann_search_stats), 0)) != hipSuccess) return fail(e);
+    if ((e = alloc_filled(s->cn, (size_t)nq * 4, 0)) != hipSuccess) return fail(e);
+    if ((e = alloc_filled(s->cnext, (size_t)nq * 4, 0)) != hipSuccess) return fail(e);
+    if ((e = alloc_filled(s->stats, (size_t)nq * sizeof(dann_search_stats), 0)) != hipSuccess) return fail(e);
     if ((e = hipMemcpy(s->q.p, queries, (size_t)nq * qb, hipMemcpyHostToDevice)) != hipSuccess) return fail(e);
     a.queries = s->q.p;
     a.ids[0] = (uint32_t*)s->ids0.p;
@@ -458,12 +452,9 @@ int32_t dann_paged_next(dann_paged* s, uint32_t k, uint32_t* out_ids, float* out
     hipStream_t stream = lease.ctx->stream;
     const uint32_t nq = s->a.nq;
     if (s->out_k < k) {
-        if (s->out_ids.p) (void)hipFree(s->out_ids.p);
-        if (s->out_d.p) (void)hipFree(s->out_d.p);
-        s->out_ids.p = s->out_d.p = nullptr;
-        DANN_HIP(hipMalloc(&s->out_ids.p, (size_t)nq * k * 4));
-        DANN_HIP(hipMalloc(&s->out_d.p, (size_t)nq * k * 4));
-        if (!s->out_n.p) DANN_HIP(hipMalloc(&s->out_n.p, (size_t)nq * 4));
+        DANN_HIP(s->out_ids.alloc((size_t)nq * k * 4));
+        DANN_HIP(s->out_d.alloc((size_t)nq * k * 4));
+        if (!s->out_n.p) DANN_HIP(s->out_n.alloc((size_t)nq * 4));
         s->out_k = k;
     }
     {   // (the session's queries keep the layout they were staged with)

@@ -705,13 +705,6 @@ __global__ __launch_bounds__(256) void sq_chain_sum_kernel(const double* v, uint
     if (threadIdx.x == 0) *out = acc / (double)n;
 }
 
-struct Buf {
-    void* p = nullptr;
-    ~Buf() {
-        if (p) (void)hipFree(p);
-    }
-};
-
 // dann_pq_pack_neighbors: one wavefront per node.  Row = [len][ids x R][pad to 16][code row (16 bytes per 16 chunks) of neighbour 0 .. R-1]
 // (neighbours beyond the length, and ids beyond the index, get zero code rows: they are never candidates).
 __global__ __launch_bounds__(256) void pq_pack_kernel(IndexView ix, uint8_t* pack, uint32_t stride, uint32_t codes_off) {
@@ -766,12 +759,12 @@ int32_t dann_pq_build_lut(int32_t device, int32_t metric, const float* pivots, c
     if (nq == 0) return DANN_OK;
     if (device >= 0) DANN_HIP(hipSetDevice(device));
     if ((size_t)dim * 4 > 64 * 1024) return DANN_EUNSUPPORTED;
-    Buf dp, doff, dq, dl;
+    DevBuf dp, doff, dq, dl;
     const size_t lut_bytes = (size_t)nq * nchunks * 256 * 4;
-    DANN_HIP(hipMalloc(&dp.p, (size_t)256 * dim * 4));
-    DANN_HIP(hipMalloc(&doff.p, (size_t)(nchunks + 1) * 4));
-    DANN_HIP(hipMalloc(&dq.p, (size_t)nq * dim * 4));
-    DANN_HIP(hipMalloc(&dl.p, lut_bytes));
+    DANN_HIP(dp.alloc((size_t)256 * dim * 4));
+    DANN_HIP(doff.alloc((size_t)(nchunks + 1) * 4));
+    DANN_HIP(dq.alloc((size_t)nq * dim * 4));
+    DANN_HIP(dl.alloc(lut_bytes));
     DANN_HIP(hipMemcpy(dp.p, pivots, (size_t)256 * dim * 4, hipMemcpyHostToDevice));
     DANN_HIP(hipMemcpy(doff.p, chunk_offsets, (size_t)(nchunks + 1) * 4, hipMemcpyHostToDevice));
     DANN_HIP(hipMemcpy(dq.p, queries, (size_t)nq * dim * 4, hipMemcpyHostToDevice));
@@ -805,12 +798,12 @@ int32_t dann_pq_scan(int32_t device, const float* lut, uint32_t nq, uint32_t nch
         return DANN_EUNSUPPORTED;
     }
     if (device >= 0) DANN_HIP(hipSetDevice(device));
-    Buf dl, dc, di, doff, dout;
-    DANN_HIP(hipMalloc(&dl.p, (size_t)nq * lds));
-    DANN_HIP(hipMalloc(&dc.p, npoints * nchunks));
-    DANN_HIP(hipMalloc(&di.p, total * 4));
-    DANN_HIP(hipMalloc(&doff.p, (size_t)(nq + 1) * 8));
-    DANN_HIP(hipMalloc(&dout.p, total * 4));
+    DevBuf dl, dc, di, doff, dout;
+    DANN_HIP(dl.alloc((size_t)nq * lds));
+    DANN_HIP(dc.alloc(npoints * nchunks));
+    DANN_HIP(di.alloc(total * 4));
+    DANN_HIP(doff.alloc((size_t)(nq + 1) * 8));
+    DANN_HIP(dout.alloc(total * 4));
     DANN_HIP(hipMemcpy(dl.p, lut, (size_t)nq * lds, hipMemcpyHostToDevice));
     DANN_HIP(hipMemcpy(dc.p, codes, npoints * nchunks, hipMemcpyHostToDevice));
     DANN_HIP(hipMemcpy(di.p, ids, total * 4, hipMemcpyHostToDevice));
@@ -856,18 +849,18 @@ extern "C" int32_t dann_pq_compress(int32_t device, const float* pivots, uint32_
     if (lds > 64 * 1024)
         DANN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pq_compress_kernel),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    Buf dp, doff, dx, dc, dbad;
-    DANN_HIP(hipMalloc(&dp.p, (size_t)ncenters * dim * 4));
-    DANN_HIP(hipMalloc(&doff.p, (size_t)(nchunks + 1) * 4));
-    DANN_HIP(hipMalloc(&dbad.p, 8));
+    DevBuf dp, doff, dx, dc, dbad;
+    DANN_HIP(dp.alloc((size_t)ncenters * dim * 4));
+    DANN_HIP(doff.alloc((size_t)(nchunks + 1) * 4));
+    DANN_HIP(dbad.alloc(8));
     DANN_HIP(hipMemcpy(dp.p, pivots, (size_t)ncenters * dim * 4, hipMemcpyHostToDevice));
     DANN_HIP(hipMemcpy(doff.p, chunk_offsets, (size_t)(nchunks + 1) * 4, hipMemcpyHostToDevice));
     DANN_HIP(hipMemset(dbad.p, 0xFF, 8));
     // rows go through in slabs of <= 1 GiB
     const uint64_t slab_rows = std::max<uint64_t>(1, (1ull << 30) / ((uint64_t)dim * 4));
     const uint64_t cap = std::min<uint64_t>(n, slab_rows);
-    DANN_HIP(hipMalloc(&dx.p, cap * dim * 4));
-    DANN_HIP(hipMalloc(&dc.p, cap * nchunks));
+    DANN_HIP(dx.alloc(cap * dim * 4));
+    DANN_HIP(dc.alloc(cap * nchunks));
     for (uint64_t off = 0; off < n; off += cap) {
         const uint64_t m = std::min<uint64_t>(cap, n - off);
         DANN_HIP(hipMemcpy(dx.p, rows + off * dim, m * dim * 4, hipMemcpyHostToDevice));
@@ -922,25 +915,25 @@ int32_t pq_lloyds_device(const float* dx, uint64_t n, uint32_t dim, const uint32
     if (!mfma && lds_row > 64 * 1024)
         DANN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pq_assign_kernel),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_row));
-    Buf dcn, ddn, dasg, dbest, dres, dord, dord2, dkeys2, dcounts, dstarts, dtmp, dbad;
-    DANN_HIP(hipMalloc(&dcn.p, (size_t)nchunks * ncenters * 4));
-    DANN_HIP(hipMalloc(&ddn.p, (size_t)nchunks * n * 4));
-    DANN_HIP(hipMalloc(&dasg.p, (size_t)nchunks * n * 4));
-    DANN_HIP(hipMalloc(&dbest.p, (size_t)nchunks * n * 4));
-    DANN_HIP(hipMalloc(&dres.p, (size_t)nchunks * 4));
-    DANN_HIP(hipMalloc(&dord.p, n * 4));
-    DANN_HIP(hipMalloc(&dord2.p, (size_t)nchunks * n * 4));
-    DANN_HIP(hipMalloc(&dkeys2.p, n * 4));
-    DANN_HIP(hipMalloc(&dcounts.p, (size_t)nchunks * ncenters * 4));
-    DANN_HIP(hipMalloc(&dstarts.p, (size_t)nchunks * ncenters * 4));
-    DANN_HIP(hipMalloc(&dbad.p, 4));
+    DevBuf dcn, ddn, dasg, dbest, dres, dord, dord2, dkeys2, dcounts, dstarts, dtmp, dbad;
+    DANN_HIP(dcn.alloc((size_t)nchunks * ncenters * 4));
+    DANN_HIP(ddn.alloc((size_t)nchunks * n * 4));
+    DANN_HIP(dasg.alloc((size_t)nchunks * n * 4));
+    DANN_HIP(dbest.alloc((size_t)nchunks * n * 4));
+    DANN_HIP(dres.alloc((size_t)nchunks * 4));
+    DANN_HIP(dord.alloc(n * 4));
+    DANN_HIP(dord2.alloc((size_t)nchunks * n * 4));
+    DANN_HIP(dkeys2.alloc(n * 4));
+    DANN_HIP(dcounts.alloc((size_t)nchunks * ncenters * 4));
+    DANN_HIP(dstarts.alloc((size_t)nchunks * ncenters * 4));
+    DANN_HIP(dbad.alloc(4));
     DANN_HIP(hipMemsetAsync(dbad.p, 0, 4, 0));
     int key_bits = 1;
     while ((1u << key_bits) < ncenters && key_bits < 32) ++key_bits;
     size_t tmp_bytes = 0;
     DANN_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (const uint32_t*)dasg.p, (uint32_t*)dkeys2.p,
                                                 (const uint32_t*)dord.p, (uint32_t*)dord2.p, (int)n, 0, key_bits));
-    DANN_HIP(hipMalloc(&dtmp.p, tmp_bytes + 16));
+    DANN_HIP(dtmp.alloc(tmp_bytes + 16));
     const dim3 rows_grid((uint32_t)((n + 255) / 256), nchunks);
     hipLaunchKernelGGL(pq_data_norms_kernel, rows_grid, dim3(256), 0, 0, dx, n, dim, doff, (float*)ddn.p);
     hipLaunchKernelGGL(pq_center_norms_kernel, dim3((ncenters + 255) / 256, nchunks), dim3(256), 0, 0,
@@ -999,10 +992,10 @@ extern "C" int32_t dann_pq_lloyds(int32_t device, const float* data, uint64_t n,
     int32_t rc = pq_check_offsets(chunk_offsets, nchunks, dim, nullptr);
     if (rc != DANN_OK) return rc;
     if (device >= 0) DANN_HIP(hipSetDevice(device));
-    Buf dx, doff, dcen;
-    DANN_HIP(hipMalloc(&dx.p, n * dim * 4));
-    DANN_HIP(hipMalloc(&doff.p, (size_t)(nchunks + 1) * 4));
-    DANN_HIP(hipMalloc(&dcen.p, (size_t)ncenters * dim * 4));
+    DevBuf dx, doff, dcen;
+    DANN_HIP(dx.alloc(n * dim * 4));
+    DANN_HIP(doff.alloc((size_t)(nchunks + 1) * 4));
+    DANN_HIP(dcen.alloc((size_t)ncenters * dim * 4));
     DANN_HIP(hipMemcpy(dx.p, data, n * dim * 4, hipMemcpyHostToDevice));
     DANN_HIP(hipMemcpy(doff.p, chunk_offsets, (size_t)(nchunks + 1) * 4, hipMemcpyHostToDevice));
     DANN_HIP(hipMemcpy(dcen.p, centers, (size_t)ncenters * dim * 4, hipMemcpyHostToDevice));
@@ -1022,12 +1015,12 @@ extern "C" int32_t dann_sq8_train(int32_t device, const float* data, uint64_t n,
         return DANN_EINVAL;
     }
     if (device >= 0) DANN_HIP(hipSetDevice(device));
-    Buf dx, dm, dv, dn, dmn;
-    DANN_HIP(hipMalloc(&dx.p, n * dim * 4));
-    DANN_HIP(hipMalloc(&dm.p, (size_t)dim * 8));
-    DANN_HIP(hipMalloc(&dv.p, (size_t)dim * 8));
-    DANN_HIP(hipMalloc(&dn.p, n * 8));
-    DANN_HIP(hipMalloc(&dmn.p, 8));
+    DevBuf dx, dm, dv, dn, dmn;
+    DANN_HIP(dx.alloc(n * dim * 4));
+    DANN_HIP(dm.alloc((size_t)dim * 8));
+    DANN_HIP(dv.alloc((size_t)dim * 8));
+    DANN_HIP(dn.alloc(n * 8));
+    DANN_HIP(dmn.alloc(8));
     DANN_HIP(hipMemcpy(dx.p, data, n * dim * 4, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(sq_col_sum_kernel, dim3((dim + 63) / 64), dim3(64), 0, 0, (const float*)dx.p, n, dim,
                        (const double*)nullptr, (double*)dm.p);
@@ -1062,10 +1055,10 @@ extern "C" int32_t dann_sq_compress(int32_t device, int32_t bits, const float* x
     if (n == 0) return DANN_OK;
     if (device >= 0) DANN_HIP(hipSetDevice(device));
     const size_t row = ((size_t)dim * (uint32_t)bits + 7u) / 8u + 4u;
-    Buf dx, ds, dout;
-    DANN_HIP(hipMalloc(&dx.p, (size_t)n * dim * 4));
-    DANN_HIP(hipMalloc(&ds.p, (size_t)dim * 4));
-    DANN_HIP(hipMalloc(&dout.p, (size_t)n * row));
+    DevBuf dx, ds, dout;
+    DANN_HIP(dx.alloc((size_t)n * dim * 4));
+    DANN_HIP(ds.alloc((size_t)dim * 4));
+    DANN_HIP(dout.alloc((size_t)n * row));
     DANN_HIP(hipMemcpy(dx.p, x, (size_t)n * dim * 4, hipMemcpyHostToDevice));
     DANN_HIP(hipMemcpy(ds.p, shift, (size_t)dim * 4, hipMemcpyHostToDevice));
     const dim3 grid((n + 255) / 256), block(256);
@@ -1098,7 +1091,7 @@ namespace {
 int32_t pq_kmeanspp_device(const float* dx, uint64_t n, uint32_t dim, const uint32_t* doff, uint32_t nchunks,
                            uint32_t ncenters, const dann_rng* rng, float* dcen, std::vector<uint32_t>& sel) {
     const uint64_t nblocks = (n + 15) / 16;
-    Buf dnorm, dmins, dbs, dback, dfwd, dpicked, dlast, dlastn;
+    DevBuf dnorm, dmins, dbs, dback, dfwd, dpicked, dlast, dlastn;
     struct Pinned {
         void* p = nullptr;
         ~Pinned() {
@@ -1107,14 +1100,14 @@ int32_t pq_kmeanspp_device(const float* dx, uint64_t n, uint32_t dim, const uint
     } hback, hfwd;
     // back: [totals: nchunks f64][chosen: nchunks i64]; forward: [thresholds: nchunks f64][active: nchunks bytes]
     const size_t back_bytes = (size_t)nchunks * 16, fwd_bytes = (size_t)nchunks * 9;
-    DANN_HIP(hipMalloc(&dnorm.p, (size_t)nchunks * n * 4));
-    DANN_HIP(hipMalloc(&dmins.p, (size_t)nchunks * n * 4));
-    DANN_HIP(hipMalloc(&dbs.p, (size_t)nchunks * nblocks * 8));
-    DANN_HIP(hipMalloc(&dback.p, back_bytes));
-    DANN_HIP(hipMalloc(&dfwd.p, fwd_bytes));
-    DANN_HIP(hipMalloc(&dpicked.p, (size_t)nchunks * n));
-    DANN_HIP(hipMalloc(&dlast.p, (size_t)nchunks * dim * 4));
-    DANN_HIP(hipMalloc(&dlastn.p, (size_t)nchunks * 4));
+    DANN_HIP(dnorm.alloc((size_t)nchunks * n * 4));
+    DANN_HIP(dmins.alloc((size_t)nchunks * n * 4));
+    DANN_HIP(dbs.alloc((size_t)nchunks * nblocks * 8));
+    DANN_HIP(dback.alloc(back_bytes));
+    DANN_HIP(dfwd.alloc(fwd_bytes));
+    DANN_HIP(dpicked.alloc((size_t)nchunks * n));
+    DANN_HIP(dlast.alloc((size_t)nchunks * dim * 4));
+    DANN_HIP(dlastn.alloc((size_t)nchunks * 4));
     DANN_HIP(hipHostMalloc(&hback.p, back_bytes, hipHostMallocDefault));
     DANN_HIP(hipHostMalloc(&hfwd.p, fwd_bytes, hipHostMallocDefault));
     double* const dtot = (double*)dback.p;
@@ -1221,10 +1214,10 @@ extern "C" int32_t dann_pq_kmeanspp(int32_t device, const float* data, uint64_t 
     if (selected) memset(selected, 0, (size_t)nchunks * 4);
     if (n == 0 || ncenters == 0) return DANN_OK;  // DatasetTooSmall is recoverable: all centres stay zero
     if (device >= 0) DANN_HIP(hipSetDevice(device));
-    Buf dx, doff, dcen;
-    DANN_HIP(hipMalloc(&dx.p, n * dim * 4));
-    DANN_HIP(hipMalloc(&doff.p, (size_t)(nchunks + 1) * 4));
-    DANN_HIP(hipMalloc(&dcen.p, (size_t)ncenters * dim * 4));
+    DevBuf dx, doff, dcen;
+    DANN_HIP(dx.alloc(n * dim * 4));
+    DANN_HIP(doff.alloc((size_t)(nchunks + 1) * 4));
+    DANN_HIP(dcen.alloc((size_t)ncenters * dim * 4));
     DANN_HIP(hipMemcpy(dx.p, data, n * dim * 4, hipMemcpyHostToDevice));
     DANN_HIP(hipMemcpy(doff.p, chunk_offsets, (size_t)(nchunks + 1) * 4, hipMemcpyHostToDevice));
     std::vector<uint32_t> sel(nchunks, 0);
@@ -1246,10 +1239,10 @@ extern "C" int32_t dann_pq_train(int32_t device, const float* data, uint64_t n, 
     if (ncenters == 0) return DANN_EINVAL;
     if (n == 0) return DANN_EINVAL;
     if (device >= 0) DANN_HIP(hipSetDevice(device));
-    Buf dx, doff, dcen;
-    DANN_HIP(hipMalloc(&dx.p, n * dim * 4));
-    DANN_HIP(hipMalloc(&doff.p, (size_t)(nchunks + 1) * 4));
-    DANN_HIP(hipMalloc(&dcen.p, (size_t)ncenters * dim * 4));
+    DevBuf dx, doff, dcen;
+    DANN_HIP(dx.alloc(n * dim * 4));
+    DANN_HIP(doff.alloc((size_t)(nchunks + 1) * 4));
+    DANN_HIP(dcen.alloc((size_t)ncenters * dim * 4));
     DANN_HIP(hipMemcpy(dx.p, data, n * dim * 4, hipMemcpyHostToDevice));
     DANN_HIP(hipMemcpy(doff.p, chunk_offsets, (size_t)(nchunks + 1) * 4, hipMemcpyHostToDevice));
     std::vector<uint32_t> sel(nchunks, 0);

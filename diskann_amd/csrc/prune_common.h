@@ -4,6 +4,7 @@
 
 #include "dann_device.h"
 #include "dann_internal.h"
+#include "wave_lists.h"
 
 namespace dann {
 namespace {

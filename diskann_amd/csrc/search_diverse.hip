@@ -373,21 +373,12 @@ int32_t diverse_search_device(dann_index* idx, hipStream_t st, const void* d_que
         b.ht_prime = dv_prime_leq(h);
         b.gws_stride = (dv_ws_bytes(l_value, b.pool_cap, h) + 255u) & ~(uint64_t)255u;
         const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(failed.size(), (1ull << 30) / b.gws_stride));
-        uint8_t* gws = nullptr;
-        uint32_t* d_map = nullptr;
-        DANN_HIP(hipMalloc((void**)&gws, (size_t)chunk * b.gws_stride));
-        struct Free {
-            void* p;
-            void* m;
-            ~Free() {
-                (void)hipFree(p);
-                (void)hipFree(m);
-            }
-        } fr{gws, nullptr};
-        DANN_HIP(hipMalloc((void**)&d_map, failed.size() * 4));
-        fr.m = d_map;
+        DevBuf gws, map;
+        DANN_HIP(gws.alloc((size_t)chunk * b.gws_stride));
+        DANN_HIP(map.alloc(failed.size() * 4));
+        uint32_t* d_map = map.as<uint32_t>();
         DANN_HIP(hipMemcpyAsync(d_map, failed.data(), failed.size() * 4, hipMemcpyHostToDevice, st));
-        b.gws = gws;
+        b.gws = gws.as<uint8_t>();
         const size_t blds = dv_fixed_lds(a.ix, beam_width);
         for (size_t o = 0; o < failed.size(); o += chunk) {
             b.qmap = d_map + o;

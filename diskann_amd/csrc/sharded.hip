@@ -189,22 +189,6 @@ struct AbortOnError {
 
 namespace {
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        return hipMalloc(&p, n ? n : 1);
-    }
-    template <class T>
-    T* as() {
-        return reinterpret_cast<T*>(p);
-    }
-};
-
 // diskann/src/utils/async_tools.rs:289-365: contiguous ranges that differ in length by at most one
 void partition(uint32_t nitems, uint32_t ntasks, uint32_t task, uint32_t* lo, uint32_t* hi) {
     const uint32_t k = nitems / ntasks, m = nitems % ntasks;

@@ -42,13 +42,6 @@ namespace {
 
 constexpr uint32_t kMaxWork = 16384u;  // floats of one row's working vector: one 64 KB LDS stage
 
-struct TfBuf {
-    void* p = nullptr;
-    ~TfBuf() {
-        if (p) (void)hipFree(p);
-    }
-};
-
 struct TfArgs {
     const uint32_t* s0;
     const uint32_t* s1;   // DoubleHadamard only (length work)
@@ -448,9 +441,9 @@ extern "C" int32_t dann_transform_apply(const dann_transform* t, const float* x,
     DeviceGuard dev(t->device);
     if (!dev.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
     const size_t xb = (size_t)n * t->in_dim * 4, ob = (size_t)n * t->out_dim * 4;
-    TfBuf dx, dout;
-    DANN_HIP(hipMalloc(&dx.p, xb));
-    DANN_HIP(hipMalloc(&dout.p, ob));
+    DevBuf dx, dout;
+    DANN_HIP(dx.alloc(xb));
+    DANN_HIP(dout.alloc(ob));
     DANN_HIP(hipMemcpy(dx.p, x, xb, hipMemcpyHostToDevice));
     if (int32_t rc = launch_transform(*t, static_cast<const float*>(dx.p), t->in_dim, n, static_cast<float*>(dout.p),
                                       t->out_dim, nullptr))
@@ -477,12 +470,12 @@ extern "C" int32_t dann_minmax_quantize_device(const dann_transform* t, int32_t 
     if (!dev.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
     // the transformed rows, packed; images that are not packed in d_out are compressed into a packed scratch first (the
     // compressor ORs codes into zeroed images, and the bytes between the caller's images are not ours to clear)
-    TfBuf dtx, dimg, dflag;
-    DANN_HIP(hipMalloc(&dtx.p, (size_t)n * t->out_dim * 4));
-    DANN_HIP(hipMalloc(&dflag.p, 4));
+    DevBuf dtx, dimg, dflag;
+    DANN_HIP(dtx.alloc((size_t)n * t->out_dim * 4));
+    DANN_HIP(dflag.alloc(4));
     uint8_t* img = static_cast<uint8_t*>(d_out);
     if (out_stride != lb) {
-        DANN_HIP(hipMalloc(&dimg.p, (size_t)n * lb));
+        DANN_HIP(dimg.alloc((size_t)n * lb));
         img = static_cast<uint8_t*>(dimg.p);
     }
     if (int32_t rc = launch_transform(*t, d_x, x_stride, n, static_cast<float*>(dtx.p), t->out_dim, nullptr)) return rc;
@@ -514,10 +507,10 @@ extern "C" int32_t dann_minmax_quantize(const dann_transform* t, int32_t bits, f
     if (!dev.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
     const size_t lb = kMmHeader + sq_code_bytes(48 + bits, t->out_dim);
     const size_t xb = (size_t)n * t->in_dim * 4, ob = (size_t)n * lb;
-    TfBuf dx, dout, dloss;
-    DANN_HIP(hipMalloc(&dx.p, xb));
-    DANN_HIP(hipMalloc(&dout.p, ob));
-    if (out_loss) DANN_HIP(hipMalloc(&dloss.p, (size_t)n * 4));
+    DevBuf dx, dout, dloss;
+    DANN_HIP(dx.alloc(xb));
+    DANN_HIP(dout.alloc(ob));
+    if (out_loss) DANN_HIP(dloss.alloc((size_t)n * 4));
     DANN_HIP(hipMemcpy(dx.p, x, xb, hipMemcpyHostToDevice));
     const int32_t rc = dann_minmax_quantize_device(t, bits, grid_scale, static_cast<const float*>(dx.p), t->in_dim, n, dout.p,
                                                    lb, static_cast<float*>(dloss.p));

@@ -144,3 +144,35 @@ def test_concurrent_searches_on_a_shared_index():
     [t.join() for t in th]
     for t in range(8):
         assert np.array_equal(got[t][0], want[t][0]) and np.array_equal(bits(got[t][1]), bits(want[t][1]))
+
+
+def test_build_config_status_codes():
+    """The build, consolidation and in-place delete check their dann_build_config with one function.  Only the build
+    searches, so only it needs l_build; a max_occlusion_size above the prune kernels' 4096-entry pool is
+    DANN_EUNSUPPORTED and every other bad field DANN_EINVAL, whichever entry point is asked."""
+    rng = np.random.default_rng(11)
+    n, dim, R = 64, 8, 8
+    data = rand_vectors(rng, oracle.F32, n, dim)
+    adj = random_graph(rng, n, R)
+    _, gix = make_pair(oracle.F32, oracle.L2, data, adj, data[:1], R)
+
+    def status(call):
+        try:
+            call()
+        except da.DannError as e:
+            return e.status
+        return da._ffi.OK
+
+    def all_three(cfg):
+        return (status(lambda: gix.build(cfg, 0, n)), status(lambda: gix.consolidate(cfg)),
+                status(lambda: gix.inplace_delete(cfg, [5])))
+
+    E, U = da._ffi.EINVAL, da._ffi.EUNSUPPORTED
+    assert all_three(da.build_config(0, R, 10)) == (E, E, E)                             # pruned_degree 0
+    assert all_three(da.build_config(R, R - 1, 10)) == (E, E, E)                         # max_degree < pruned_degree
+    assert all_three(da.build_config(R, R + 1, 10)) == (E, E, E)                         # max_degree > the provider's
+    assert all_three(da.build_config(R, R, 10, alpha=0.5)) == (E, E, E)
+    assert all_three(da.build_config(R, R, 10, max_occlusion_size=4097)) == (U, U, U)
+    assert all_three(da.build_config(0, R, 10, max_occlusion_size=4097)) == (E, E, E)    # the bad field is named first
+    assert not gix.get_deleted().any()                                                   # nothing ran
+    assert all_three(da.build_config(R, R, 0)) == (E, da._ffi.OK, da._ffi.OK)            # l_build 0
