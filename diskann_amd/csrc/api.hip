@@ -1143,8 +1143,8 @@ int32_t dann_range_search_batch(dann_index* idx, const void* queries, uint32_t n
     uint32_t bad = nq;
     if (int32_t frc = fetch_stats(ctx.stream, bs.p, nq, out_stats, &bad)) return frc;
     if (bad < nq) {
-        set_error("query %u: range result list or visited scratch exhausted (list capacity %llu)", bad,
-                  (unsigned long long)cap);
+        set_error("query %u: more results than out_cap (%u), or range scratch list (%llu entries) or visited scratch "
+                  "exhausted; raise out_cap", bad, out_cap, (unsigned long long)cap);
         return DANN_EOVERFLOW;
     }
     return DANN_OK;

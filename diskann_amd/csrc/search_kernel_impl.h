@@ -2186,6 +2186,8 @@ __device__ __forceinline__ void beam_search_one(const SearchArgs& a, const uint3
                 }
                 range_written += (uint32_t)__popcll(m);
             }
+            // as FilteredRange above: the reference's output Vec is unbounded, a shortened list would pass for a whole one
+            if (range_written > a.k) status = (uint32_t)(-DANN_EOVERFLOW);
             range_written = range_written < a.k ? range_written : a.k;
             for (uint32_t r = range_written + lane; r < a.k; r += kWave) {
                 oi[r] = kEmpty;

@@ -264,7 +264,10 @@ int32_t dann_search_batch_device(dann_index* idx, const void* d_queries, uint32_
  * `radius` and fewer than max_returned -- breadth-first expansion of every point within
  * radius * range_slack.  Results (slot ids, start points dropped, `inner_radius < d <= radius`) go to
  * out_ids/out_dists (nq x out_cap, unwritten = 0xFFFFFFFF / +inf).  max_returned == 0: unlimited
- * (the GPU scratch list is then sized 4 * out_cap + 1024 per query; a longer list is DANN_EOVERFLOW).
+ * (the GPU scratch list is then sized min(4 * out_cap + 1024, capacity + starts) per query; a longer list is
+ * DANN_EOVERFLOW).  A query with more results than out_cap is DANN_EOVERFLOW too: the reference's output is unbounded,
+ * and a silently shortened list cannot be told from a complete one.  After DANN_EOVERFLOW the outputs are unspecified
+ * (out_stats[q].status names the queries); the same call with a larger out_cap succeeds.
  * Stats follow the reference's accounting (cmps of the first phase only, hops = initial + cumulative,
  * :308-314); out_second_round[q] = range_search_second_round.  Parameter errors == RangeSearchError. */
 int32_t dann_range_search_batch(dann_index* idx, const void* queries, uint32_t nq, uint32_t starting_l,
@@ -294,7 +297,10 @@ int32_t dann_filtered_search_batch(dann_index* idx, const void* queries, uint32_
                                    float* out_dists, dann_search_stats* out_stats);
 /* index.search(FilteredRange, ..) (search/filtered_range_search.rs:111-330); parameters and outputs as
  * dann_range_search_batch, filter->mode must be DANN_FILTER_INLINE, AdaptiveL is not used (:148-156).
- * cmps / hops accumulate over both rounds. */
+ * cmps / hops accumulate over both rounds.  DANN_EOVERFLOW as dann_range_search_batch: a query with more results than
+ * out_cap (the reference's output is unbounded, and a silently shortened list cannot be told from a complete one), more
+ * matched ids in the first round than filter->matched_cap, or a list of matched ids within the radius longer than
+ * max(max_returned ? max_returned : 4 * out_cap + 1024, matched_cap), at most capacity + starts. */
 int32_t dann_filtered_range_search_batch(dann_index* idx, const void* queries, uint32_t nq, uint32_t starting_l,
                                          uint32_t beam_width, float radius, int32_t has_inner_radius,
                                          float inner_radius, float initial_slack, float range_slack,
@@ -306,7 +312,9 @@ int32_t dann_filtered_range_search_batch(dann_index* idx, const void* queries, u
  * diskann/src/graph/search/paged.rs:53-149) for nq queries at once.  The session owns the reference's per-search
  * scratch on the device: the auto-resizable candidate list (nothing is ever dropped, queue.rs:95-121), the visited
  * set and the tail of the last computed page.  list_cap bounds the list per query (0 = min(capacity + starts,
- * max(16384, 64 * l_value))); exceeding it is DANN_EOVERFLOW.  next_page: k results per query (k <= l_value, errors
+ * max(16384, 64 * l_value)), never below 64 or above capacity + starts); a query whose list would outgrow it makes
+ * dann_paged_next return DANN_EOVERFLOW, from that call on (the session is over; open another with a larger list_cap --
+ * the index is untouched).  next_page: k results per query (k <= l_value, errors
  * as paged.rs:57-64), out_ids/out_dists nq x k (unwritten 0xFFFFFFFF / +inf), out_counts[q] = results of the page
  * (0 = exhausted).  Pages never overlap; within a page distances are non-decreasing.  Not for DANN_PQ. */
 typedef struct dann_paged dann_paged;

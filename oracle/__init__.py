@@ -263,7 +263,7 @@ class Index:
 
     # -- algorithms -----------------------------------------------------------
     def search(self, query, l_value, beam_width=1, k=10, record=False):
-        q = np.ascontiguousarray(query, dtype=NP_DTYPE[self.dtype])
+        q = np.ascontiguousarray(query, dtype=self.query_dtype)  # (PQ rows: the query stays f32)
         ids = np.empty(k, np.uint32)
         dists = np.empty(k, np.float32)
         stats = np.zeros(3, np.uint32)
@@ -298,7 +298,7 @@ class Index:
 
     def range_search(self, query, starting_l, radius, beam_width=1, inner_radius=None, initial_slack=1.0,
                      range_slack=1.0, max_returned=0, out_cap=None):
-        q = np.ascontiguousarray(query, dtype=NP_DTYPE[self.dtype])
+        q = np.ascontiguousarray(query, dtype=self.query_dtype)  # (PQ rows: the query stays f32)
         cap = out_cap or (max_returned if max_returned else self.capacity + self.nstart)
         ids = np.empty(cap, np.uint32)
         dists = np.empty(cap, np.float32)
@@ -325,7 +325,7 @@ class Index:
         return np.frombuffer(self.filter_bits(match), np.uint32).copy()
 
     def inline_filter_search(self, query, l_value, k, match, beam_width=1, adaptive=None):
-        q = np.ascontiguousarray(query, dtype=NP_DTYPE[self.dtype])
+        q = np.ascontiguousarray(query, dtype=self.query_dtype)  # (PQ rows: the query stays f32)
         bits = self._bits(match)
         ids = np.empty(k, np.uint32)
         dists = np.empty(k, np.float32)
@@ -338,7 +338,7 @@ class Index:
         return n, ids, dists, stats
 
     def multihop_search(self, query, l_value, k, match, beam_width=1):
-        q = np.ascontiguousarray(query, dtype=NP_DTYPE[self.dtype])
+        q = np.ascontiguousarray(query, dtype=self.query_dtype)  # (PQ rows: the query stays f32)
         bits = self._bits(match)
         ids = np.empty(k, np.uint32)
         dists = np.empty(k, np.float32)
@@ -351,7 +351,7 @@ class Index:
 
     def filtered_range_search(self, query, starting_l, radius, match, beam_width=1, inner_radius=None,
                               initial_slack=1.0, range_slack=1.0, max_returned=0, out_cap=None):
-        q = np.ascontiguousarray(query, dtype=NP_DTYPE[self.dtype])
+        q = np.ascontiguousarray(query, dtype=self.query_dtype)  # (PQ rows: the query stays f32)
         bits = self._bits(match)
         cap = out_cap or (max_returned if max_returned else self.capacity + self.nstart)
         ids = np.empty(cap, np.uint32)
@@ -366,7 +366,7 @@ class Index:
 
     def paged_search(self, query, l_value, page_size, max_pages=None):
         """all pages of index.paged_search(query, l_value) with next_page(page_size) until an empty page"""
-        q = np.ascontiguousarray(query, dtype=NP_DTYPE[self.dtype])
+        q = np.ascontiguousarray(query, dtype=self.query_dtype)  # (PQ rows: the query stays f32)
         h = lib().orc_paged_begin(C.byref(self._c), _p(q), l_value)
         if not h:
             raise RuntimeError("orc_paged_begin failed")
@@ -386,7 +386,7 @@ class Index:
         return pages
 
     def expand_beam(self, query, ids):
-        q = np.ascontiguousarray(query, dtype=NP_DTYPE[self.dtype])
+        q = np.ascontiguousarray(query, dtype=self.query_dtype)  # (PQ rows: the query stays f32)
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         oi = np.empty(ids.size, np.uint32)
         od = np.empty(ids.size, np.float32)

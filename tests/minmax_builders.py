@@ -57,7 +57,7 @@ class MmTwin:
     """twin rows (a = 1, b = 0: L2 is exactly the squared distance of the codes) and the oracle's U8 L2 index over the
     codes.  hi: codes drawn from [0, hi) -- the twin needs 2 * (hi - 1)^2 * dim < 2^24"""
 
-    def __init__(self, bits, dim, n, R, seed, adj=True, maxdeg=None, nstart=1, hi=None):
+    def __init__(self, bits, dim, n, R, seed, adj=True, maxdeg=None, nstart=1, hi=None, gpu=True):
         rng = np.random.default_rng(seed)
         self.bits, self.dim, self.n, self.R, self.rng, self.nstart = bits, dim, n, R, rng, nstart
         self.hi = hi or (1 << bits)
@@ -70,11 +70,17 @@ class MmTwin:
         self.oix.set_rows(0, self.codes)
         if adj:
             self.oix.adj[:] = self.adj
+        self.gix = None
+        if gpu:
+            self.attach_gpu()
+
+    def attach_gpu(self):
         da = _da()
-        self.gix = da.Provider(mm_dtype(bits), da.L2, dim, n, self.maxdeg, mm.twin_rows(self.scodes, bits))
+        self.gix = da.Provider(mm_dtype(self.bits), da.L2, self.dim, self.n, self.maxdeg, mm.twin_rows(self.scodes, self.bits))
         self.gix.set_elements(0, self.rows)
         if self.adj is not None:
             self.gix.upload_graph(self.adj)
+        return self.gix
 
     def queries(self, nq):
         qc = self.rng.integers(0, self.hi, (nq, self.dim), dtype=np.uint8)

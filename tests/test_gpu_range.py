@@ -52,7 +52,7 @@ def test_range_search_random_graph(dtype, metric):
             (8, 2, r_big, r_small, 0.25, 1.0, 0),
             (8, 1, r_big, None, 0.5, 1.3, 40),
             (16, 3, r_big, None, 0.0, 1.0, 100)):
-        cap = 1500
+        cap = n  # (room for every row: a result list longer than out_cap is DANN_EOVERFLOW, include/dann.h)
         gi, gd, gst, gsec = gix.range_search(queries, L, radius, W, inner, islack, rslack, maxret, out_cap=cap)
         for q in range(queries.shape[0]):
             oi, od, ost = oix.range_search(queries[q], L, radius, W, inner, islack, rslack, maxret, out_cap=cap)
@@ -90,12 +90,13 @@ def test_range_searches_of_concurrent_callers_overlap():
     d0 = np.array([oracle.distance(oracle.F32, oracle.L2, queries[0], data[i]) for i in range(300)])
     radius = float(np.quantile(d0, 0.02))
     Lr = 250
-    want = [oix.range_search(queries[q], Lr, radius, 1, None, 1.0, 1.0, 0, out_cap=2000) for q in range(len(queries))]
+    Lcap = 4000  # (the longest result list here has 2 610 entries; one longer than out_cap would be DANN_EOVERFLOW)
+    want = [oix.range_search(queries[q], Lr, radius, 1, None, 1.0, 1.0, 0, out_cap=Lcap) for q in range(len(queries))]
 
     def work(t, out):
         q = queries[t * per_call:(t + 1) * per_call]
         for _ in range(calls):
-            out[t] = gix.range_search(q, Lr, radius, 1, None, 1.0, 1.0, 0, out_cap=2000)
+            out[t] = gix.range_search(q, Lr, radius, 1, None, 1.0, 1.0, 0, out_cap=Lcap)
     res = [None] * nthreads
     work(0, res)  # warm: contexts, calibration
     ratios = []

@@ -126,7 +126,7 @@ def test_range_search_second_phase_with_16_bit_entries(dtype):
     seconds = 0
     for L, radius, inner, islack, rslack, maxret in ((20, r_small, None, 1.0, 1.0, 0), (8, r_big, None, 0.5, 1.3, 40),
                                                      (8, r_big, r_small, 0.25, 1.0, 0)):
-        cap = 1500
+        cap = n  # (room for every row: a result list longer than out_cap is DANN_EOVERFLOW, include/dann.h)
         gi, gd, gst, gsec = gix.range_search(queries, L, radius, 1, inner, islack, rslack, maxret, out_cap=cap)
         for q in range(queries.shape[0]):
             oi, od, ost = oix.range_search(queries[q], L, radius, 1, inner, islack, rslack, maxret, out_cap=cap)
