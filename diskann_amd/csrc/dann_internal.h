@@ -137,8 +137,9 @@ int32_t sched_build_pivots(dann_index* idx, hipStream_t st);
 // dann_debug_sched_pivots: the pivot slab as unscaled f32 (DANN_EINVAL before the first scheduled search)
 int32_t sched_copy_pivots(const dann_index* idx, float* out, uint32_t cap_floats, uint32_t* out_np, uint32_t* out_stride,
                           float* out_scale);
+// (its first kernel also clears zero[0 .. zero_words): the launch's spill-pool counters, with no operation of their own)
 int32_t sched_build_map(const dann_index* idx, hipStream_t st, const void* queries, uint32_t nq, uint32_t parts,
-                        uint32_t* scratch, uint32_t* qmap);
+                        uint32_t* scratch, uint32_t* qmap, uint32_t* zero, uint32_t zero_words);
 // one translation unit per row type (search_<type>.hip) holds the kernel instantiations
 #define DANN_DECL_LAUNCH(name) \
     int32_t launch_search_##name(const SearchArgs& a, uint32_t qcap, size_t lds, hipStream_t stream, int* regs_out)

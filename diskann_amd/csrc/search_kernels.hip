@@ -110,8 +110,10 @@ static int32_t plan_failed(int32_t rc, const PlanMsg& msg) {
 
 // everything a beam-search launch needs besides its arguments: the context's spill pool (zeroed counters), the size of
 // the LDS visited table (calibrated per (L, beam, mode), never affects results) and the tuning bits.  `inflight` is the
-// number of wavefronts the launch keeps resident.
-static int32_t prepare_launch(dann_index* idx, SearchCtx& ctx, SearchArgs& a, const LaunchKnobs& k, uint32_t inflight) {
+// number of wavefronts the launch keeps resident.  zero_pool = false leaves the pool's counters to the caller
+// (search_with_retry: a scheduled launch has them cleared by the scheduler's first kernel).
+static int32_t prepare_launch(dann_index* idx, SearchCtx& ctx, SearchArgs& a, const LaunchKnobs& k, uint32_t inflight,
+                              bool zero_pool = true) {
     hipStream_t st = ctx.stream;
     // failure flag in pinned host memory: written over the fabric only by a query that
     // overflows (rare), read by the host after the stream sync -- no memset / D2H copy
@@ -132,7 +134,7 @@ static int32_t prepare_launch(dann_index* idx, SearchCtx& ctx, SearchArgs& a, co
     // the pool's allocation counter and busy flags start every launch at zero -- except a team launch, which never
     // touches the pool (a team gives a query that outgrows its table back to the host): one device operation less on
     // the single-query path
-    if (!a.team) DANN_HIP(hipMemsetAsync(a.spill_next, 0, (16 + (size_t)ctx.spill_slices) * 4, st));
+    if (!a.team && zero_pool) DANN_HIP(hipMemsetAsync(a.spill_next, 0, (16 + (size_t)ctx.spill_slices) * 4, st));
     // calibration state of this (L, beam, mode) -- shared by concurrent callers: read and written under stat_mu
     VisitedCalib cal;
     const bool autosize = a.ht_entries == 0;
@@ -210,7 +212,8 @@ int32_t search_with_retry(dann_index* idx, SearchCtx& ctx, SearchArgs a) {
     const uint32_t inflight = launch_capped(a, k) ? k.max_concurrency : a.nq;
     const bool autosize = a.ht_entries == 0;
     const uint64_t key = calib_key(a);
-    if (int32_t prc = prepare_launch(idx, ctx, a, k, inflight)) return prc;
+    if (int32_t prc = prepare_launch(idx, ctx, a, k, inflight, false)) return prc;
+    const uint32_t pool_words = a.team ? 0u : 16u + ctx.spill_slices;  // (the counters this launch starts from zero)
     cap_grid(a, k);  // (the counter lives behind the spill pool prepare_launch has just attached)
     if (a.grid) a.team = 0;  // persistent waves over a block: one wave per query
     // locality scheduling (query_schedule.hip): a large Knn launch of f32 / f16 rows runs its queries grouped by nearest
@@ -219,6 +222,7 @@ int32_t search_with_retry(dann_index* idx, SearchCtx& ctx, SearchArgs a) {
     // DANN_DBG_SCHED_MIN_QUERIES: development switches.
     const uint32_t* const caller_qmap = a.qmap;
     const uint32_t sched_min = idx->dbg_u32(DANN_DBG_SCHED_MIN_QUERIES, 16384u);
+    bool pool_zeroed = false;
     if (a.nq >= sched_min) {
         const bool sched = !a.qmap && a.queries && !a.qslots && !a.rec_ids && !a.range_ids && !a.srv.ring && !a.team &&
                            !a.pair && !a.pqlut && a.filter_mode == 0 && (a.ix.dtype == DT_F32 || a.ix.dtype == DT_F16) &&
@@ -239,15 +243,18 @@ int32_t search_with_retry(dann_index* idx, SearchCtx& ctx, SearchArgs a) {
                     idx->sched_stale = false;
                 }
             }
-            if (int32_t mrc = sched_build_map(idx, st, a.queries, a.nq, a.grid ? 1u : 8u, ctx.d_sched + a.nq, ctx.d_sched))
+            if (int32_t mrc = sched_build_map(idx, st, a.queries, a.nq, a.grid ? 1u : 8u, ctx.d_sched + a.nq, ctx.d_sched,
+                                              a.spill_next, pool_words))
                 return mrc;
             a.qmap = ctx.d_sched;
+            pool_zeroed = true;
         }
         if (idx->verbose())
             fprintf(stderr, "[dann] schedule: %u queries %s\n", a.nq,
                     sched ? (a.grid ? "sorted by nearest pivot (persistent waves)" : "sorted by nearest pivot, 8 XCD runs")
                           : "in caller order");
     }
+    if (pool_words && !pool_zeroed) DANN_HIP(hipMemsetAsync(a.spill_next, 0, (size_t)pool_words * 4, st));
     volatile uint32_t* hflag = ctx.h_flag;
     *hflag = 0;
     a.fail_flag = ctx.h_flag;
