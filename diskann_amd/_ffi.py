@@ -151,6 +151,8 @@ SYMBOLS = {
     "dann_mvset_create": (_i32, [_i32, _i32, _u32, _u32, _vp, _vp, _P(_vp)]),
     "dann_mvset_destroy": (_i32, [_vp]),
     "dann_mvset_info": (_i32, [_vp, _P(_i32), _P(_u32), _P(_u32), _P(_u64)]),
+    "dann_mvset_set_query_dtype": (_i32, [_vp, _i32]),
+    "dann_mvset_get_query_dtype": (_i32, [_vp, _P(_i32)]),
     "dann_maxsim_batch": (_i32, [_vp, _i32, _vp, _vp, _u32, _vp, _u32, _vp, _vp]),
     "dann_maxsim_batch_device": (_i32, [_vp, _i32, _vp, _vp, _u32, _vp, _u32, _vp, _vp]),
     "dann_chamfer_rerank_batch": (_i32, [_vp, _i32, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),

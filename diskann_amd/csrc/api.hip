@@ -9,6 +9,7 @@
 #include <time.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <memory>
 #include <mutex>
@@ -1500,13 +1501,16 @@ int32_t dann_rerank_batch(dann_index* idx, const void* queries, uint32_t nq, con
 
 // ---- multi-vector sets (maxsim_kernels.hip) ------------------------------------------------------------------------------
 // Rows are kept at a stride of whole 16-byte units with the tail zeroed -- the layout the kernels stage from -- and the
-// queries of a call are brought to the same stride on their way to the device.
+// queries of a call are brought to the same stride on their way to the device.  MinMax sets (maxsim_mm_kernels.hip): the
+// rows are canonical images on the way in; the device keeps their packed codes at such a stride and a header record per row.
 struct dann_mvset {
     int device = 0;
     int32_t dtype = 0;
+    std::atomic<int32_t> qdtype{0};           // dann_mvset_set_query_dtype; read once at the entry of a scoring call
     uint32_t dim = 0, ndocs = 0, stride = 0;  // stride: bytes of a row on the device
     uint64_t nrows = 0;
     uint8_t* d_rows = nullptr;
+    dann::MmRowHeader* d_hdr = nullptr;       // MinMax sets only
     uint64_t* d_off = nullptr;
     // HIP-event time of the scoring launches (dann_debug_mvset_kernel_time); clock_mu also keeps one call's pair of
     // events to itself
@@ -1515,6 +1519,7 @@ struct dann_mvset {
     mutable dann::KernelClock clock;
     ~dann_mvset() {
         if (d_rows) (void)hipFree(d_rows);
+        if (d_hdr) (void)hipFree(d_hdr);
         if (d_off) (void)hipFree(d_off);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
@@ -1531,9 +1536,33 @@ int32_t mv_copy_rows(uint8_t* d_dst, uint32_t stride, const void* src, uint32_t 
     return DANN_OK;
 }
 
+// bytes of a row on the device: f32 / f16 elements, or a MinMax row's packed codes, in whole 16-byte units
+uint32_t mv_stride(int32_t dtype, uint32_t dim) {
+    const uint32_t row_bytes = dt_is_mm(dtype) ? sq_code_bytes(dtype, dim) : dim * (dtype == DT_F32 ? 4u : 2u);
+    return (row_bytes + 15u) & ~15u;
+}
+
+// packed MinMax images (host or device) -> codes at `stride` and header records on the device
+int32_t mv_repack_rows(int32_t dtype, uint32_t dim, uint8_t* d_codes, uint32_t stride, MmRowHeader* d_hdr, const void* src,
+                       uint64_t nrows, bool src_device) {
+    if (nrows == 0) return DANN_OK;
+    const uint32_t image_bytes = layer_bytes_of(dtype, dim);
+    DevBuf img;
+    const uint8_t* d_src = static_cast<const uint8_t*>(src);
+    if (!src_device) {
+        DANN_HIP(img.alloc((size_t)nrows * image_bytes));
+        DANN_HIP(hipMemcpy(img.p, src, (size_t)nrows * image_bytes, hipMemcpyHostToDevice));
+        d_src = img.as<uint8_t>();
+    }
+    if (int32_t rc = launch_mm_repack(dtype, d_src, image_bytes, nrows, dim, d_codes, stride, d_hdr, nullptr)) return rc;
+    DANN_HIP(hipStreamSynchronize(nullptr));  // (`img` is freed on return)
+    return DANN_OK;
+}
+
 // the arguments of one scoring call, on the device
 struct MvCall {
-    DevBuf q, qoff, cand, status;
+    DevBuf q, qhdr, qoff, cand, status;
+    int32_t qdtype = 0;
     std::vector<uint32_t> h_qoff;
     MaxSimArgs a{};
     uint64_t qrows_total = 0;
@@ -1573,9 +1602,18 @@ int32_t mv_prepare(const dann_mvset* s, int32_t order, const void* queries, cons
     }
     c.qrows_total = c.h_qoff[nq];
     if (c.qrows_total && !queries) return DANN_EINVAL;
-    DANN_HIP(c.q.alloc((size_t)c.qrows_total * s->stride + 16));
-    const uint32_t row_bytes = s->dim * (s->dtype == DT_F32 ? 4u : 2u);
-    if (int32_t rc = mv_copy_rows(c.q.as<uint8_t>(), s->stride, queries, row_bytes, c.qrows_total, on_device)) return rc;
+    c.qdtype = s->qdtype.load();
+    const uint32_t qstride = mv_stride(c.qdtype, s->dim);
+    DANN_HIP(c.q.alloc((size_t)c.qrows_total * qstride + 16));
+    if (dt_is_mm(s->dtype)) {
+        DANN_HIP(c.qhdr.alloc(((size_t)c.qrows_total + 1) * sizeof(MmRowHeader)));
+        if (int32_t rc = mv_repack_rows(c.qdtype, s->dim, c.q.as<uint8_t>(), qstride, c.qhdr.as<MmRowHeader>(), queries,
+                                        c.qrows_total, on_device))
+            return rc;
+    } else {
+        const uint32_t row_bytes = s->dim * (s->dtype == DT_F32 ? 4u : 2u);
+        if (int32_t rc = mv_copy_rows(c.q.as<uint8_t>(), qstride, queries, row_bytes, c.qrows_total, on_device)) return rc;
+    }
     DANN_HIP(c.status.alloc(4));
     DANN_HIP(hipMemset(c.status.p, 0, 4));
     if (!on_device) {
@@ -1589,6 +1627,9 @@ int32_t mv_prepare(const dann_mvset* s, int32_t order, const void* queries, cons
     c.a.ndocs = s->ndocs;
     c.a.dim = s->dim;
     c.a.stride = s->stride;
+    c.a.qstride = qstride;
+    c.a.dhdr = s->d_hdr;
+    c.a.qhdr = c.qhdr.as<MmRowHeader>();
     c.a.qrows = c.q.as<uint8_t>();
     c.a.qoff = on_device ? q_offsets : c.qoff.as<uint32_t>();
     c.a.cand = on_device ? cand : c.cand.as<uint32_t>();
@@ -1603,7 +1644,9 @@ int32_t mv_score(const dann_mvset* s, int32_t order, MvCall& c, uint32_t nq, flo
     c.a.out_scores = d_scores;
     std::lock_guard<std::mutex> lk(s->clock_mu);
     DANN_HIP(hipEventRecord(s->ev0, nullptr));
-    if (int32_t rc = launch_maxsim(s->dtype, order, c.a, nq, nullptr)) return rc;
+    if (int32_t rc = dt_is_mm(s->dtype) ? launch_maxsim_mm(c.qdtype, s->dtype, order, c.a, nq, nullptr)
+                                        : launch_maxsim(s->dtype, order, c.a, nq, nullptr))
+        return rc;
     DANN_HIP(hipEventRecord(s->ev1, nullptr));
     uint32_t st = 0;
     DANN_HIP(hipMemcpy(&st, c.status.p, 4, hipMemcpyDeviceToHost));  // (waits for the launch)
@@ -1677,8 +1720,8 @@ int32_t dann_mvset_create(int32_t device, int32_t dtype, uint32_t dim, uint32_t 
     if (!out) return DANN_EINVAL;
     *out = nullptr;
     if (!row_offsets) return DANN_EINVAL;
-    if (dtype != DT_F32 && dtype != DT_F16) {
-        set_error("multi-vector sets hold DANN_F32 or DANN_F16 rows (got dtype %d)", dtype);
+    if (dtype != DT_F32 && dtype != DT_F16 && !dt_is_mm(dtype)) {
+        set_error("multi-vector sets hold DANN_F32, DANN_F16 or DANN_MM1 / MM2 / MM4 / MM8 rows (got dtype %d)", dtype);
         return DANN_EINVAL;
     }
     if (dim == 0) {
@@ -1703,17 +1746,23 @@ int32_t dann_mvset_create(int32_t device, int32_t dtype, uint32_t dim, uint32_t 
     std::unique_ptr<dann_mvset> s(new dann_mvset());
     if (device >= 0) DANN_HIP(hipSetDevice(device));
     DANN_HIP(hipGetDevice(&s->device));
-    const uint32_t row_bytes = dim * (dtype == DT_F32 ? 4u : 2u);
     s->dtype = dtype;
+    s->qdtype = dtype;
     s->dim = dim;
     s->ndocs = ndocs;
     s->nrows = nrows;
-    s->stride = (row_bytes + 15u) & ~15u;
+    s->stride = mv_stride(dtype, dim);
     DANN_HIP(hipEventCreate(&s->ev0));
     DANN_HIP(hipEventCreate(&s->ev1));
     DANN_HIP(hipMalloc((void**)&s->d_rows, (size_t)nrows * s->stride + 16));
     DANN_HIP(hipMalloc((void**)&s->d_off, ((size_t)ndocs + 1) * 8));
-    if (int32_t rc = mv_copy_rows(s->d_rows, s->stride, rows, row_bytes, nrows, false)) return rc;
+    if (dt_is_mm(dtype)) {
+        DANN_HIP(hipMalloc((void**)&s->d_hdr, ((size_t)nrows + 1) * sizeof(MmRowHeader)));
+        if (int32_t rc = mv_repack_rows(dtype, dim, s->d_rows, s->stride, s->d_hdr, rows, nrows, false)) return rc;
+    } else {
+        const uint32_t row_bytes = dim * (dtype == DT_F32 ? 4u : 2u);
+        if (int32_t rc = mv_copy_rows(s->d_rows, s->stride, rows, row_bytes, nrows, false)) return rc;
+    }
     DANN_HIP(hipMemcpy(s->d_off, row_offsets, ((size_t)ndocs + 1) * 8, hipMemcpyHostToDevice));
     *out = s.release();
     return DANN_OK;
@@ -1732,6 +1781,30 @@ int32_t dann_mvset_info(const dann_mvset* set, int32_t* dtype, uint32_t* dim, ui
     if (dim) *dim = set->dim;
     if (ndocs) *ndocs = set->ndocs;
     if (nrows) *nrows = set->nrows;
+    return DANN_OK;
+} DANN_CATCH_ALL
+
+int32_t dann_mvset_set_query_dtype(dann_mvset* set, int32_t dtype) try {
+    if (!set) return DANN_EINVAL;
+    if (dtype != set->dtype) {
+        if (!dt_is_mm(set->dtype) || !dt_is_mm(dtype)) {
+            set_error("query dtype %d on a multi-vector set of dtype %d: %s", dtype, set->dtype,
+                      dt_is_mm(set->dtype) ? "a MinMax set takes MinMax queries" : "queries have the set's own dtype");
+            return DANN_EINVAL;
+        }
+        if (dtype != DT_MM8) {  // the reference's mixed pairs are (8, 4), (8, 2), (8, 1) (bits/distances.rs:1621)
+            set_error("MinMax queries of dtype %d on rows of dtype %d: the supported pairs are equal widths and DANN_MM8 "
+                      "queries on narrower rows", dtype, set->dtype);
+            return DANN_EUNSUPPORTED;
+        }
+    }
+    set->qdtype = dtype;
+    return DANN_OK;
+} DANN_CATCH_ALL
+
+int32_t dann_mvset_get_query_dtype(const dann_mvset* set, int32_t* out) try {
+    if (!set || !out) return DANN_EINVAL;
+    *out = set->qdtype.load();
     return DANN_OK;
 } DANN_CATCH_ALL
 

@@ -1381,14 +1381,20 @@ __device__ __forceinline__ float finish_spherical(float ip, const uint8_t* x, co
 // association.  NOT symmetric in its arguments: (t0 + x.n * y.b) + y.n * x.b rounds differently when x and y swap, so
 // `x` must be the reference's first argument (the query; in prunes the candidate under test) and `y` its second.  The
 // headers are 4-byte aligned (image starts are 16-byte aligned in global memory, slot + 12 in LDS).
+// minmax_value is the one statement of the kernel's five operations, on header values: finish_minmax reads them from two
+// images, the multi-vector kernels (maxsim_mm_kernels.hip) from their own header records.
+__device__ __forceinline__ float minmax_value(float raw, float xb, float xn, float xa, float yb, float yn, float ya,
+                                              uint32_t dim) {
+    const float t0 = (xa * ya) * raw;
+    return ((t0 + xn * yb) + yn * xb) + (xb * yb) * (float)dim;
+}
 template <int OP, bool NORM>
 __device__ __forceinline__ float finish_minmax(float raw, const uint8_t* x, const uint8_t* y, uint32_t dim) {
     const float* hx = reinterpret_cast<const float*>(x);
     const float* hy = reinterpret_cast<const float*>(y);
     const float xb = hx[1], xn = hx[2], xa = hx[3], xs = hx[4];
     const float yb = hy[1], yn = hy[2], ya = hy[3], ys = hy[4];
-    const float t0 = (xa * ya) * raw;
-    const float vv = ((t0 + xn * yb) + yn * xb) + (xb * yb) * (float)dim;
+    const float vv = minmax_value(raw, xb, xn, xa, yb, yn, ya, dim);
     if constexpr (OP == OP_L2) return (-2.0f * vv + xs) + ys;
     else if constexpr (OP == OP_COS) return 1.0f - vv / (__builtin_sqrtf(xs) * __builtin_sqrtf(ys));  // no zero-norm guard
     else return NORM ? 1.0f - vv : -vv;

@@ -194,12 +194,20 @@ int32_t launch_minmax_compress(int32_t bits, const float* d_x, uint32_t n, uint3
                                float* d_out_loss, uint32_t* d_nan_flag, hipStream_t stream);
 
 // maxsim_kernels.hip: multi-vector scores (dann_maxsim_batch, dann_chamfer_rerank_batch).  Rows of documents and of
-// queries sit at `stride` bytes, a multiple of 16, the bytes behind `dim` zero.
+// queries sit at `stride` / `qstride` bytes, multiples of 16, the bytes behind `dim` zero.  MinMax sets
+// (maxsim_mm_kernels.hip): the rows are the packed codes alone, and each row has a 16-byte MmRowHeader beside them.
 constexpr uint32_t kMaxSimQueryRows = 1024, kMaxSimDim = 4096, kMaxSimCands = 4096, kMaxSimQueries = 65535;
+struct MmRowHeader {
+    float b, n, a;             // MinMaxCompensation's b, n, a (norm_squared is not needed by the inner product)
+    int32_t sum;               // sum over k < dim of the code as the matrix cores see it: c - 128 for 8-bit codes, else c
+};
 struct MaxSimArgs {
     const uint8_t* drows;      // the set's rows
     const uint64_t* doff;      // ndocs + 1 row offsets
     uint32_t ndocs, dim, stride;
+    uint32_t qstride;          // == stride unless a MinMax query is wider than the set's rows
+    const MmRowHeader* dhdr;   // MinMax sets: one per row of drows / qrows; else null
+    const MmRowHeader* qhdr;
     const uint8_t* qrows;      // the queries' rows
     const uint32_t* qoff;      // nq + 1 row offsets
     const uint32_t* cand;      // nq x cand_stride document ids
@@ -209,6 +217,11 @@ struct MaxSimArgs {
     uint32_t* status;          // set to 1 by a candidate id >= ndocs
 };
 int32_t launch_maxsim(int32_t dtype, int32_t order, const MaxSimArgs& a, uint32_t nq, hipStream_t stream);
+// maxsim_mm_kernels.hip.  MinMax images (d_images: nrows x image_bytes, any alignment) -> zero-padded codes at `stride`
+// and header records; and the scores of a (query width, row width) pair the reference has.
+int32_t launch_mm_repack(int32_t dtype, const uint8_t* d_images, uint32_t image_bytes, uint64_t nrows, uint32_t dim,
+                         uint8_t* d_codes, uint32_t stride, MmRowHeader* d_hdr, hipStream_t stream);
+int32_t launch_maxsim_mm(int32_t qdtype, int32_t dtype, int32_t order, const MaxSimArgs& a, uint32_t nq, hipStream_t stream);
 int32_t launch_chamfer_sort(const uint32_t* d_cand, const float* d_chamfer, uint32_t nq, uint32_t stride, uint32_t ndocs,
                             uint32_t k, uint32_t* d_out_ids, float* d_out_d, uint32_t* d_out_counts, hipStream_t stream);
 

@@ -23,6 +23,7 @@
 
 #include "dann_device.h"
 #include "dann_internal.h"
+#include "maxsim_pair.h"
 #include "wave_lists.h"
 
 namespace dann {
@@ -30,8 +31,6 @@ namespace {
 
 typedef float ms_f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr uint32_t kMsThreads = 256;   // four wavefronts: one 32-row query tile each
-constexpr uint32_t kMsWaves = kMsThreads / 64;
 constexpr uint32_t kMsSlabK = 128;     // k values of one LDS slab
 constexpr uint32_t kMsSlabFloats = kMsSlabK * 32u;
 
@@ -83,62 +82,6 @@ __device__ __forceinline__ void ms_stage(float* slab, const uint8_t* rows, uint3
         float* dst = slab + (req * E) * 32u + (row ^ ((req & 7u) << 2));
 #pragma unroll
         for (uint32_t j = 0; j < E; ++j) dst[j * 32u] = ok[p] ? f[j] : 0.0f;
-    }
-}
-
-struct MsPair {
-    const uint8_t* q;    // the query's first row
-    const uint8_t* d;    // the document's first row
-    uint32_t qn;         // query rows (<= kMaxSimQueryRows)
-    uint64_t dn;         // document rows
-    float* chamfer;      // the pair's Chamfer cell
-    float* scores;       // the pair's qn score cells, or null
-    bool live;           // false: nothing more to do for this workgroup (cells already written)
-};
-
-// What every kernel here does first: find the pair, and settle the cases that take no arithmetic.  Skipped candidates
-// (0xFFFFFFFF) and ids >= ndocs write +infinity (the latter also raise the status word: DANN_EBOUNDS on the host -- an
-// argument check INSTEAD of the read); an empty document writes f32::MAX scores and Chamfer 0.0.
-__device__ __forceinline__ MsPair ms_pair(const MaxSimArgs& a) {
-    const uint32_t c = blockIdx.x, qi = blockIdx.y;
-    const uint32_t q0 = a.qoff[qi], qn = a.qoff[qi + 1] - q0;
-    MsPair p;
-    p.qn = qn;
-    p.q = a.qrows + (uint64_t)q0 * a.stride;
-    p.chamfer = a.out_chamfer + (uint64_t)qi * a.cand_stride + c;
-    p.scores = a.out_scores ? a.out_scores + (uint64_t)q0 * a.cand_stride + (uint64_t)c * qn : nullptr;
-    p.d = a.drows;
-    p.dn = 0;
-    p.live = false;
-    const uint32_t id = a.cand[(uint64_t)qi * a.cand_stride + c];
-    float fill, cham;
-    if (id == kEmpty || id >= a.ndocs) {
-        if (id != kEmpty && threadIdx.x == 0) *a.status = 1u;  // (every writer writes the same word)
-        fill = cham = __builtin_inff();
-    } else {
-        const uint64_t d0 = a.doff[id];
-        p.dn = a.doff[id + 1] - d0;
-        p.d = a.drows + d0 * a.stride;
-        if (p.dn != 0 && qn != 0) {
-            p.live = true;
-            return p;
-        }
-        fill = FLT_MAX;  // (qn == 0: no cell to fill)
-        cham = 0.0f;
-    }
-    if (p.scores)
-        for (uint32_t i = threadIdx.x; i < qn; i += blockDim.x) p.scores[i] = fill;
-    if (threadIdx.x == 0) *p.chamfer = cham;
-    return p;
-}
-
-// Chamfer::evaluate (fallback.rs:196-204): one lane, query-row order, from 0.0 -- not a tree, not an atomic
-__device__ __forceinline__ void ms_chamfer(const MsPair& p, const float* sc) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float sum = 0.0f;
-        for (uint32_t i = 0; i < p.qn; ++i) sum += sc[i];
-        *p.chamfer = sum;
     }
 }
 

@@ -4,14 +4,20 @@ A document and a query are small matrices of token rows.  MaxSim: per query row,
 rows, as a similarity score (negated); Chamfer: their sum over the query's rows.  `order` picks whose bits come back
 (include/dann.h): MAXSIM_KERNEL = MaxSimKernel::compute_max_sim (matrix cores), MAXSIM_REFERENCE = MaxSim::evaluate /
 Chamfer::evaluate (the pair distance function).
+
+MinMax-quantised sets (MM1 / MM2 / MM4 / MM8, diskann-quantization/src/minmax/multi/): documents and queries are
+(rows, dann_layer_bytes(dtype, dim)) uint8 matrices of canonical images, as dann_minmax_compress writes them; `dim` must be
+given.  `query_dtype` is the queries' width: the set's own, or MM8 on a narrower set.  Both orders return the same bits
+there; MAXSIM_KERNEL runs the int8 matrix cores, MAXSIM_REFERENCE a plain kernel.
 """
 import ctypes as C
 
 import numpy as np
 
-from ._ffi import F16, F32, MAXSIM_KERNEL, MAXSIM_REFERENCE, check, lib
+from ._ffi import F16, F32, MAXSIM_KERNEL, MAXSIM_REFERENCE, MM1, MM2, MM4, MM8, check, lib
 
 _NP = {F32: np.float32, F16: np.float16}
+_MM = (MM1, MM2, MM4, MM8)
 SKIP = 0xFFFFFFFF  # a cand_ids entry that is not scored
 
 
@@ -32,20 +38,41 @@ def csr(mats, np_dtype, dim, offset_dtype):
 class MultiVectorSet:
     """An immutable, device-resident set of multi-vector documents (dann_mvset)."""
 
-    def __init__(self, dtype, docs, device=-1, dim=None):
-        if dtype not in _NP:
-            raise ValueError("multi-vector sets hold F32 or F16 rows")
+    def __init__(self, dtype, docs, device=-1, dim=None, query_dtype=None):
+        if dtype not in _NP and dtype not in _MM:
+            raise ValueError("multi-vector sets hold F32, F16 or MM1 / MM2 / MM4 / MM8 rows")
         if dim is None:
+            if dtype in _MM:
+                raise ValueError("dim is needed for a MinMax set: it cannot be read off the images' shape")
             if not len(docs):
                 raise ValueError("dim is needed for a set without documents")
             dim = np.asarray(docs[0]).shape[-1]
         self.dtype, self.dim, self.ndocs = dtype, int(dim), len(docs)
-        off, rows = csr(docs, _NP[dtype], self.dim, np.uint64)
+        off, rows = csr(docs, *self._row_shape(dtype), np.uint64)
         self.nrows = int(off[-1])
         h = C.c_void_p()
         check(lib().dann_mvset_create(device, dtype, self.dim, self.ndocs, _vp(off), _vp(rows), C.byref(h)),
               "dann_mvset_create")
         self._h = h
+        if query_dtype is not None:
+            self.query_dtype = query_dtype
+
+    def _row_shape(self, dtype):
+        """(numpy element type, elements per row) of the rows of `dtype` that the C calls take"""
+        if dtype in _MM:
+            return np.uint8, check(lib().dann_layer_bytes(dtype, self.dim), "dann_layer_bytes")
+        return _NP[dtype], self.dim
+
+    @property
+    def query_dtype(self):
+        """the dtype of the queries' rows (dann_mvset_get_query_dtype): the set's own unless set otherwise"""
+        out = C.c_int32()
+        check(lib().dann_mvset_get_query_dtype(self._h, C.byref(out)), "dann_mvset_get_query_dtype")
+        return out.value
+
+    @query_dtype.setter
+    def query_dtype(self, dtype):
+        check(lib().dann_mvset_set_query_dtype(self._h, dtype), "dann_mvset_set_query_dtype")
 
     def close(self):
         if getattr(self, "_h", None):
@@ -70,7 +97,7 @@ class MultiVectorSet:
         return dt.value, dim.value, nd.value, nr.value
 
     def _call_args(self, queries, cand_ids):
-        qoff, qrows = csr(queries, _NP[self.dtype], self.dim, np.uint32)
+        qoff, qrows = csr(queries, *self._row_shape(self.query_dtype), np.uint32)
         cand = np.ascontiguousarray(cand_ids, dtype=np.uint32)
         if cand.ndim == 1:
             cand = np.ascontiguousarray(np.broadcast_to(cand, (len(queries), cand.shape[0])))

@@ -755,16 +755,35 @@ int32_t dann_drop_deleted_neighbors(dann_index* idx, const dann_build_config* cf
  * (q, c) are the q_rows(q) floats at q_offsets[q] * cand_stride + c * q_rows(q).
  * Limits: 1 <= dim <= 4096; at most 1024 rows per query; any number of rows per document; cand_stride 1 .. 4096;
  * nq <= 65535 per call.  Beyond them: DANN_EUNSUPPORTED.
- * Errors: DANN_EINVAL for null pointers, an order that is not a DANN_MAXSIM_*, a dtype other than DANN_F32 / DANN_F16,
+ * Errors: DANN_EINVAL for null pointers, an order that is not a DANN_MAXSIM_*, a dtype other than DANN_F32 / DANN_F16 /
+ * DANN_MM1 / MM2 / MM4 / MM8,
  * dim == 0, k == 0; DANN_ELENGTH for offsets that decrease or do not start at 0; DANN_EBOUNDS for a candidate id >= ndocs
  * (found on the device instead of the read; the outputs of that call are then unspecified).
- * The calls are host-synchronous.  The _device forms take queries, offsets, candidates and outputs on the set's device. */
+ * The calls are host-synchronous.  The _device forms take queries, offsets, candidates and outputs on the set's device.
+ *
+ * MinMax-quantised sets (diskann-quantization/src/minmax/multi/: MinMaxMeta<NBITS>, MinMaxKernel::max_sim_kernel):
+ * dtype DANN_MM1 / MM2 / MM4 / MM8.  `rows` and `queries` are then packed canonical images of dann_layer_bytes(dtype, dim)
+ * bytes each -- the 20-byte MinMaxCompensation, then ceil(dim * bits / 8) code bytes: what dann_minmax_compress writes.
+ * With query row x the FIRST argument and document row y the second (minmax/vectors.rs:206-269; the epilogue is not
+ * symmetric), raw the exact u32 inner product of the codes and every f32 operation on its own:
+ *   v = (((x.a * y.a) * (f32)raw + x.n * y.b) + y.n * x.b) + (x.b * y.b) * (f32)dim
+ *   scores[i] = min_j -v(i, j), the minimum from f32::MAX; Chamfer and documents or queries without rows as above.
+ * `dim` is the set's; an image's u32 dim field is not read, nor are code bits at or beyond dim * bits.  raw is an integer
+ * and has no summation order, so both orders return the same bits and `order` only picks the kernel: DANN_MAXSIM_KERNEL
+ * the int8 matrix cores (v_mfma_i32_32x32x32_i8), DANN_MAXSIM_REFERENCE a plain loop over the packed codes.
+ * Outside the contract: NaN or infinite header fields; a query row whose candidate minima include zeros of both signs.
+ * dann_mvset_set_query_dtype: the dtype of the queries' images, read once at the entry of a scoring call.  Default: the
+ * set's own.  On an MM4 / MM2 / MM1 set DANN_MM8 is also allowed (the reference's mixed pairs (8,4), (8,2), (8,1),
+ * bits/distances.rs:1621); any other MinMax pair is DANN_EUNSUPPORTED, a non-MinMax dtype on a MinMax set and any dtype
+ * but the set's own on an f32 / f16 set DANN_EINVAL. */
 typedef struct dann_mvset dann_mvset;
 enum { DANN_MAXSIM_KERNEL = 0, DANN_MAXSIM_REFERENCE = 1 };
 int32_t dann_mvset_create(int32_t device, int32_t dtype, uint32_t dim, uint32_t ndocs, const uint64_t* row_offsets,
                           const void* rows, dann_mvset** out);
 int32_t dann_mvset_destroy(dann_mvset* set);
 int32_t dann_mvset_info(const dann_mvset* set, int32_t* dtype, uint32_t* dim, uint32_t* ndocs, uint64_t* nrows);
+int32_t dann_mvset_set_query_dtype(dann_mvset* set, int32_t dtype);
+int32_t dann_mvset_get_query_dtype(const dann_mvset* set, int32_t* out);
 int32_t dann_maxsim_batch(const dann_mvset* set, int32_t order, const void* queries, const uint32_t* q_offsets,
                           uint32_t nq, const uint32_t* cand_ids, uint32_t cand_stride, float* out_chamfer,
                           float* out_scores);
