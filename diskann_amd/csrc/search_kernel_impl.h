@@ -195,6 +195,42 @@ __device__ __forceinline__ int ht16_insert_open(uint32_t* htw, const Ht16& t, ui
     }
     return res;
 }
+// Insert into the open 16-bit table, written without a per-lane branch: the hop is bound by instruction issue (every
+// `if` on a lane condition costs an exec-mask save / branch / restore), so the probe is one straight body that all lanes
+// run until the last one is done.  Same probe sequence, same table contents as ht16_insert_open.  Returns 1 = inserted
+// (the id was new), 2 = no room among its probes (the caller freezes the table), 0 = already present / inactive.
+// `own`: a dword of LDS that belongs to this lane alone -- a lane that has nothing (more) to insert swaps THAT word for
+// itself: compare-and-swaps of many lanes on one address (the lanes beyond a list's length all carry the same id) are
+// served one after the other, like a bank conflict.
+__device__ __forceinline__ uint32_t ht16_insert_flat(uint32_t* htw, const Ht16& t, uint32_t id, bool active, uint32_t* own) {
+    const uint32_t tagmask = (1u << t.tb) - 1u;
+    uint32_t x = id * kHt16A;
+    const uint32_t step = id * kHt16B2;
+    uint32_t k = 0, res = 0;
+    bool pending = active;
+    do {
+        const uint32_t val = ht16_tag(t, x, tagmask) | (k << t.tb);
+        uint32_t* const wp = pending ? htw + ht16_bucket(t, x) : own;
+        const uint32_t w = *wp;
+        const uint32_t lo = w & 0xFFFFu, hi = w >> 16;
+        const bool present = (lo == val) | (hi == val);
+        const bool e0 = lo == 0xFFFFu, empty = e0 | (hi == 0xFFFFu);
+        const bool tryins = pending & !present & empty;
+        const uint32_t put = (0xFFFFu ^ val) << (e0 ? 0u : 16u);  // the first empty half: low, then high
+        const uint32_t neww = tryins ? (w ^ put) : w;
+        const uint32_t old = atomicCAS(wp, w, neww);  // (a lost swap -- the other half changed -- reads the bucket again)
+        const bool inserted = tryins & (old == w);
+        res = inserted ? 1u : res;
+        const bool next = pending & !present & !empty;  // both halves hold other ids: next probe
+        k += next ? 1u : 0u;
+        x += next ? step : 0u;
+        const bool exh = next & (k >= t.kmax);
+        res = exh ? 2u : res;
+        pending = pending & !present & !inserted & !exh;
+    } while (ballot64(pending));
+    return res;
+}
+
 // lookup in the frozen table: true when `id` is present
 __device__ __forceinline__ bool ht16_contains(const uint32_t* htw, const Ht16& t, uint32_t id) {
     const uint32_t tagmask = (1u << t.tb) - 1u;
@@ -2452,6 +2488,12 @@ __global__ __launch_bounds__(kWave * TEAM) DANN_SEARCH_KERNEL_ATTR void beam_sea
     }
 }
 
+}  // namespace
+}  // namespace dann
+#include "search_plain_impl.h"  // beam_search_plain_kernel: the plain float hop, written for the scalar unit
+namespace dann {
+namespace {
+
 #ifndef DANN_TEAM_WAVES
 #define DANN_TEAM_WAVES 5
 #endif
@@ -2477,6 +2519,13 @@ int32_t launch_one(const SearchArgs& a, size_t lds, hipStream_t stream, int* reg
     if (a.ht16 && !HT16 && !regs_out) {
         set_error("internal: 16-bit visited table requested for a kernel that has none");
         return DANN_EINTERNAL;
+    }
+    // float rows of 128 elements in plain mode, one wave per query, at most 128 queue entries: a Knn search of queries in
+    // memory runs the same search with the hop of search_plain_impl.h (the same family, launch plan and LDS layout)
+    if constexpr ((DT == DT_F32 || DT == DT_F16) && DIM == 128 && MODE == kModePlain && TEAM == 1 && QS <= 2 && LOOP <= 1) {
+        if (!regs_out && plain_hop_serves(a))
+            return launch_kernel<beam_search_plain_kernel<DT, OP, NORM, QS, LOOP, HT16>, kLds160Once>(
+                "beam_search_kernel launch", dim3(LOOP == 1 ? a.grid : a.nq), dim3(kWave), lds, stream, a);
     }
     constexpr auto kern = beam_search_kernel<DT, OP, NORM, QS, DIM, MODE, LOOP, TEAM, HT16>;
     if (regs_out) {  // query only: VGPRs of the instantiation this launch would use

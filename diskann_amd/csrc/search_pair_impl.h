@@ -34,41 +34,8 @@ namespace {
 
 __device__ __forceinline__ uint32_t rl_u32(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
 
-// Insert into the open 16-bit table, written without a per-lane branch: the hop is bound by instruction issue (every
-// `if` on a lane condition costs an exec-mask save / branch / restore), so the probe is one straight body that all lanes
-// run until the last one is done.  Same probe sequence, same table contents as ht16_insert_open.  Returns 1 = inserted
-// (the id was new), 2 = no room among its probes (the caller freezes the table), 0 = already present / inactive.
-// `own`: a dword of LDS that belongs to this lane alone -- a lane that has nothing (more) to insert swaps THAT word for
-// itself: compare-and-swaps of many lanes on one address (the lanes beyond a list's length all carry the same id) are
-// served one after the other, like a bank conflict.
-__device__ __forceinline__ uint32_t ht16_insert_flat(uint32_t* htw, const Ht16& t, uint32_t id, bool active, uint32_t* own) {
-    const uint32_t tagmask = (1u << t.tb) - 1u;
-    uint32_t x = id * kHt16A;
-    const uint32_t step = id * kHt16B2;
-    uint32_t k = 0, res = 0;
-    bool pending = active;
-    do {
-        const uint32_t val = ht16_tag(t, x, tagmask) | (k << t.tb);
-        uint32_t* const wp = pending ? htw + ht16_bucket(t, x) : own;
-        const uint32_t w = *wp;
-        const uint32_t lo = w & 0xFFFFu, hi = w >> 16;
-        const bool present = (lo == val) | (hi == val);
-        const bool e0 = lo == 0xFFFFu, empty = e0 | (hi == 0xFFFFu);
-        const bool tryins = pending & !present & empty;
-        const uint32_t put = (0xFFFFu ^ val) << (e0 ? 0u : 16u);  // the first empty half: low, then high
-        const uint32_t neww = tryins ? (w ^ put) : w;
-        const uint32_t old = atomicCAS(wp, w, neww);  // (a lost swap -- the other half changed -- reads the bucket again)
-        const bool inserted = tryins & (old == w);
-        res = inserted ? 1u : res;
-        const bool next = pending & !present & !empty;  // both halves hold other ids: next probe
-        k += next ? 1u : 0u;
-        x += next ? step : 0u;
-        const bool exh = next & (k >= t.kmax);
-        res = exh ? 2u : res;
-        pending = pending & !present & !inserted & !exh;
-    } while (ballot64(pending));
-    return res;
-}
+// (ht16_insert_flat, the open-table insert without a per-lane branch, is in search_kernel_impl.h: the plain float hop
+// uses it too)
 
 // The overflow table of a 16-bit visited table (SearchArgs::ht_ov words, a power of two, 32-bit ids, linear probing):
 // it takes the ids whose kmax probes of the 16-bit table are all taken.  With 2^21 index slots and more a 16-bit entry
