@@ -96,6 +96,12 @@ class TransformParts(C.Structure):
                 ("subsample", C.c_void_p), ("subsample_len", C.c_uint32)]
 
 
+class SphericalParts(C.Structure):
+    """dann_spherical_parts: metric, shift (host pointer, copied by dann_spherical_create) and pre_scale of a
+    SphericalQuantizer."""
+    _fields_ = [("metric", C.c_int32), ("shift", C.c_void_p), ("pre_scale", C.c_float)]
+
+
 class SearchStats(C.Structure):
     _fields_ = [("cmps", C.c_uint32), ("hops", C.c_uint32), ("result_count", C.c_uint32), ("status", C.c_uint32),
                 ("written", C.c_uint32)]
@@ -197,6 +203,13 @@ SYMBOLS = {
     "dann_transform_apply_device": (_i32, [_vp, _vp, _u64, _u32, _vp, _u64]),
     "dann_minmax_quantize": (_i32, [_vp, _i32, _f32, _vp, _u32, _vp, _vp]),
     "dann_minmax_quantize_device": (_i32, [_vp, _i32, _f32, _vp, _u64, _u32, _vp, _u64, _vp]),
+    "dann_spherical_create": (_i32, [_vp, _P(SphericalParts), _P(_vp)]),
+    "dann_spherical_destroy": (_i32, [_vp]),
+    "dann_spherical_shift_norm_sq": (_i32, [_vp, _P(_f32)]),
+    "dann_spherical_compress": (_i32, [_vp, _i32, _vp, _u32, _vp]),
+    "dann_spherical_compress_device": (_i32, [_vp, _i32, _vp, _u64, _u32, _vp, _u64]),
+    "dann_spherical_compress_queries": (_i32, [_vp, _i32, _i32, _vp, _u32, _vp]),
+    "dann_spherical_compress_queries_device": (_i32, [_vp, _i32, _i32, _vp, _u64, _u32, _vp, _u64]),
     "dann_pq_build_lut": (_i32, [_i32, _i32, _vp, _vp, _u32, _u32, _vp, _u32, _vp]),
     "dann_pq_compress": (_i32, [_i32, _vp, _u32, _vp, _u32, _u32, _vp, _u64, _vp]),
     "dann_pq_lloyds": (_i32, [_i32, _vp, _u64, _u32, _vp, _u32, _u32, _vp, _u32, _vp, _vp]),

@@ -21,21 +21,7 @@
 
 #include "dann_device.h"
 #include "dann_internal.h"
-
-struct dann_transform {
-    int device = 0;
-    int32_t kind = 0;
-    uint32_t in_dim = 0, out_dim = 0;
-    uint32_t work = 0;  // PaddingHadamard: padded_dim; DoubleHadamard: max(input_dim, output_dim)
-    uint32_t t = 0;     // length of one Hadamard transform (DoubleHadamard: the largest power of two <= work)
-    float m = 1.0f, rescale = 1.0f;
-    uint32_t *d_signs0 = nullptr, *d_signs1 = nullptr, *d_sub = nullptr;
-    ~dann_transform() {
-        if (d_signs0) (void)hipFree(d_signs0);
-        if (d_signs1) (void)hipFree(d_signs1);
-        if (d_sub) (void)hipFree(d_sub);
-    }
-};
+#include "transform.h"
 
 namespace dann {
 namespace {
@@ -325,6 +311,8 @@ int32_t upload(uint32_t** d, const uint32_t* h, uint32_t n) {
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+}  // namespace
+
 // n rows d_x -> d_out on the current device (the transform's), queued on `st`
 int32_t launch_transform(const dann_transform& t, const float* d_x, uint64_t xs, uint32_t n, float* d_out, uint64_t os,
                          hipStream_t st) {
@@ -365,6 +353,8 @@ int32_t launch_transform(const dann_transform& t, const float* d_x, uint64_t xs,
     DANN_HIP(hipGetLastError());
     return DANN_OK;
 }
+
+namespace {
 
 bool bad_bits(const char* who, int32_t bits, float grid_scale) {
     if (bits != 1 && bits != 2 && bits != 4 && bits != 8) {

@@ -794,6 +794,82 @@ def minmax_quantize_device(t, x_ptr, n, bits, out_ptr, grid_scale=1.0, x_stride=
           "dann_minmax_quantize_device")
 
 
+class SphericalCompressor:
+    """The compressing half of a SphericalQuantizer on the transform's device: SphericalQuantizer::compress_into for rows
+    (SPH1 / SPH2 / SPH4 images) and for queries under a query layout, byte for byte the reference's results.  `shift` is
+    SphericalQuantizer::shift() (input_dim floats), `metric` L2 / INNER_PRODUCT / COSINE.  The handle copies what it needs
+    from `transform`, which may be closed afterwards."""
+
+    def __init__(self, transform, metric, shift, pre_scale=1.0):
+        shift = np.ascontiguousarray(shift, dtype=np.float32).reshape(-1)
+        if shift.size != transform.input_dim:
+            raise ValueError(f"shift has {shift.size} elements, the transform takes {transform.input_dim}")
+        parts = _ffi.SphericalParts(metric=int(metric), shift=_p(shift), pre_scale=float(pre_scale))
+        h = C.c_void_p()
+        check(_ffi.lib().dann_spherical_create(transform._h, C.byref(parts), C.byref(h)), "dann_spherical_create")
+        self._h = h
+        self.metric = int(metric)
+        self.input_dim, self.output_dim = transform.input_dim, transform.output_dim
+        out = C.c_float()
+        check(_ffi.lib().dann_spherical_shift_norm_sq(h, C.byref(out)), "dann_spherical_shift_norm_sq")
+        self.shift_norm_sq = out.value  # CompensatedIP::squared_shift_norm: Config.sq_shift_norm_sq of an SPH index
+
+    def row_bytes(self, bits):
+        return (self.output_dim * int(bits) + 7) // 8 + 6
+
+    def query_bytes(self, bits, layout):
+        """bytes of one query image (what dann_query_bytes reports for such an index); layouts the width does not have
+        are refused by the library"""
+        if layout == _ffi.QUERY_FOUR_BIT_TRANSPOSED:
+            return (self.output_dim + 63) // 64 * 32 + 16
+        if layout == _ffi.QUERY_SCALAR_QUANTIZED:
+            return (self.output_dim * int(bits) + 7) // 8 + 16
+        return self.row_bytes(bits)
+
+    def compress(self, x, bits):
+        """(n, input_dim) f32 host rows -> (n, row_bytes(bits)) images"""
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, self.input_dim)
+        out = np.empty((x.shape[0], self.row_bytes(bits) if bits in (1, 2, 4) else 0), np.uint8)
+        check(_ffi.lib().dann_spherical_compress(self._h, int(bits), _p(x), x.shape[0], _p(out)), "dann_spherical_compress")
+        return out
+
+    def compress_device(self, x_ptr, n, bits, out_ptr, x_stride=0, out_stride=0):
+        """n rows at device address x_ptr (x_stride floats apart, 0 = packed) -> images at out_ptr (out_stride bytes
+        apart, 0 = packed), ready for Provider.set_elements_device"""
+        check(_ffi.lib().dann_spherical_compress_device(self._h, int(bits), C.c_void_p(int(x_ptr)),
+                                                        int(x_stride) or self.input_dim, int(n), C.c_void_p(int(out_ptr)),
+                                                        int(out_stride) or self.row_bytes(bits)),
+              "dann_spherical_compress_device")
+
+    def queries(self, x, bits, layout):
+        """(n, input_dim) f32 host queries -> (n, query_bytes(bits, layout)) images"""
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, self.input_dim)
+        ok = bits in (1, 2, 4) and layout in (_ffi.QUERY_SAME_AS_DATA, _ffi.QUERY_FOUR_BIT_TRANSPOSED, _ffi.QUERY_SCALAR_QUANTIZED)
+        out = np.empty((x.shape[0], self.query_bytes(bits, layout) if ok else 0), np.uint8)
+        check(_ffi.lib().dann_spherical_compress_queries(self._h, int(bits), int(layout), _p(x), x.shape[0], _p(out)),
+              "dann_spherical_compress_queries")
+        return out
+
+    def queries_device(self, x_ptr, n, bits, layout, out_ptr, x_stride=0, out_stride=0):
+        """the same device to device, the images ready as the d_queries of the device search entry points"""
+        check(_ffi.lib().dann_spherical_compress_queries_device(self._h, int(bits), int(layout), C.c_void_p(int(x_ptr)),
+                                                                int(x_stride) or self.input_dim, int(n),
+                                                                C.c_void_p(int(out_ptr)),
+                                                                int(out_stride) or self.query_bytes(bits, layout)),
+              "dann_spherical_compress_queries_device")
+
+    def close(self):
+        if self._h:
+            _ffi.lib().dann_spherical_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def pq_build_lut(metric, pivots, chunk_offsets, queries, device=-1):
     piv = np.ascontiguousarray(pivots, dtype=np.float32)
     off = np.ascontiguousarray(chunk_offsets, dtype=np.uint32)

@@ -65,8 +65,9 @@ typedef enum {
      * Metrics: DANN_L2, DANN_INNER_PRODUCT, DANN_COSINE (SupportedMetric; DANN_COSINE_NORMALIZED: DANN_EINVAL).
      * Distances are CompensatedSquaredL2 / CompensatedIP / CompensatedCosine (:494-528 the kernel, :584-636 L2,
      * :744-801 inner product, :867-892 cosine), bit for bit.  sq_shift_norm_sq carries CompensatedIP::squared_shift_norm
-     * (inner product and cosine), sq_scale is ignored.  The host keeps the SphericalQuantizer and hands over byte images
-     * of rows and queries; the form of a query is set with dann_set_query_layout().  Elements at or beyond dim never
+     * (inner product and cosine), sq_scale is ignored.  The index takes byte images of rows and queries; dann_spherical_compress(_device)
+     * and dann_spherical_compress_queries(_device) make them from f32 vectors on the GPU (the host keeps training the
+     * quantiser); the form of a query is set with dann_set_query_layout().  Elements at or beyond dim never
      * take part, whatever the padding bits hold. */
     DANN_SPH1 = 33,
     DANN_SPH2 = 34,
@@ -550,6 +551,44 @@ int32_t dann_minmax_quantize(const dann_transform* t, int32_t bits, float grid_s
  * One 4-byte NaN flag is read back, nothing else crosses PCIe; complete on return. */
 int32_t dann_minmax_quantize_device(const dann_transform* t, int32_t bits, float grid_scale, const float* d_x,
                                     uint64_t x_stride, uint32_t n, void* d_out, uint64_t out_stride, float* d_out_loss);
+
+/* ---- SphericalQuantizer::compress_into on the GPU (diskann-quantization/src/spherical/quantizer.rs): rows
+ * (spherical::Data<bits>, :805-918 with the 1-bit finish :596-647 and maximize_cosine_similarity :991-1100 over SliceHeap)
+ * and queries (:1128-1212) from f32 vectors, byte for byte the reference's x86-64 V3 results: preprocess (:338-381) with
+ * every f32 operation on its own and both inner products in the V3 order, the transform of the handle, then the width's
+ * finish.  A dann_spherical is the compressing half of a SphericalQuantizer, resident on the transform's device.
+ * Training (centroid, mean norm), RandomRotation, the FullQuery layout and 8-bit data stay with the host.
+ * dann_spherical_create COPIES what it needs from `t` (signs, subsample, dims): the transform may be destroyed first.
+ * Errors: DANN_EINVAL for a metric outside SupportedMetric, a shift that is not finite, pre_scale <= 0 or not finite,
+ * bits outside {1, 2, 4}, a layout value that is no dann_query_layout, strides below a row / an image, a vector whose
+ * shifted norm is not finite (InputContainsNaN: a NaN or an overflowing input), and a DataMeta field that does not fit
+ * (EncodingError: DataMetaError::InnerProductCorrection / MetricSpecific / BitSum, vectors.rs:265-290; the variant is
+ * named in dann_last_error); DANN_EUNSUPPORTED for DANN_QUERY_FULL_PRECISION and for a layout the width does not have.
+ * After DANN_EINVAL from a vector the images of the other vectors are complete, the refused one's unspecified.
+ * A vector at the centroid (shifted norm 0) gives an image of zero bytes, codes and meta.  n == 0 is DANN_OK. */
+typedef struct {
+    int32_t metric;        /* DANN_L2 | DANN_INNER_PRODUCT | DANN_COSINE (SupportedMetric) */
+    const float* shift;    /* input_dim floats, host: SphericalQuantizer::shift() (the centroid as the quantiser stores it) */
+    float pre_scale;       /* SphericalQuantizer::pre_scale(), > 0 and finite */
+} dann_spherical_parts;
+typedef struct dann_spherical dann_spherical;
+int32_t dann_spherical_create(const dann_transform* t, const dann_spherical_parts* parts, dann_spherical** out);
+int32_t dann_spherical_destroy(dann_spherical* q);
+/* CompensatedIP::new: FastL2NormSquared(shift) -- what dann_config.sq_shift_norm_sq of the index wants */
+int32_t dann_spherical_shift_norm_sq(const dann_spherical* q, float* out);
+/* rows: x n rows of input_dim floats -> n images of dann_layer_bytes(32 + bits, output_dim), padding bits zero; bits in
+ * {1, 2, 4}.  Host pointers. */
+int32_t dann_spherical_compress(const dann_spherical* q, int32_t bits, const float* x, uint32_t n, void* out);
+/* Device form: rows x_stride floats apart, images out_stride bytes apart (bytes between images are left untouched), ready
+ * for dann_set_elements_device.  One 4-byte flag word is read back, nothing else crosses PCIe; complete on return. */
+int32_t dann_spherical_compress_device(const dann_spherical* q, int32_t bits, const float* d_x, uint64_t x_stride,
+                                       uint32_t n, void* d_out, uint64_t out_stride);
+/* queries under a dann_query_layout: SAME_AS_DATA (== the rows), FOUR_BIT_TRANSPOSED (bits == 1),
+ * SCALAR_QUANTIZED (bits in {2, 4}); images of the size dann_query_bytes() reports for such an index */
+int32_t dann_spherical_compress_queries(const dann_spherical* q, int32_t bits, int32_t layout, const float* x,
+                                        uint32_t n, void* out);
+int32_t dann_spherical_compress_queries_device(const dann_spherical* q, int32_t bits, int32_t layout, const float* d_x,
+                                               uint64_t x_stride, uint32_t n, void* d_out, uint64_t out_stride);
 
 /* build-path options (never change the resulting graph).  The matrix-core path evaluates the pair similarities a
  * RobustPrune asks for (prune.rs:196-232) as the lower triangle of one Gram matrix per candidate list
