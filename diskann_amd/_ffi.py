@@ -26,6 +26,7 @@ MAXSIM_KERNEL, MAXSIM_REFERENCE = 0, 1  # the two orders of dann_maxsim_batch / 
 BUILD_MFMA_BACKEDGE, BUILD_MFMA_POOL, BUILD_ROW_KERNEL_ONLY = 1, 2, 4
 CONSOLIDATE_COMPLETE, CONSOLIDATE_DELETED = 0, 1  # ConsolidateKind (dann_consolidate out_kind)
 CONSOLIDATE_DROP_DELETED = 1  # dann_consolidate flag
+FLAT_SKIP_DELETED = 1  # dann_flat_search_batch flag
 INPLACE_VISITED_AND_TOPK, INPLACE_TWO_HOP_AND_ONE_HOP, INPLACE_ONE_HOP = 0, 1, 2  # dann_inplace_delete_params.method
 INPLACE_COUNTERS = 9
 # dann_transform_parts.kind (TransformKind); RANDOM_ROTATION is reserved (DANN_EUNSUPPORTED)
@@ -153,6 +154,8 @@ SYMBOLS = {
     "dann_paged_end": (_i32, [_vp]),
     "dann_rerank_batch": (_i32, [_vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp]),
     "dann_rerank_batch_device": (_i32, [_vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp]),
+    "dann_flat_search_batch": (_i32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "dann_flat_search_batch_device": (_i32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     "dann_search_record_batch": (_i32, [_vp, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp]),
     "dann_mvset_create": (_i32, [_i32, _i32, _u32, _u32, _vp, _vp, _P(_vp)]),
     "dann_mvset_destroy": (_i32, [_vp]),
@@ -266,7 +269,8 @@ DBG_KEYS = {"tune_off": 0, "tune_on": 1, "pair_min_queries": 2, "team_max_querie
             "sweep_one_by_one": 5, "pool_gram": 6, "gram_cols": 7, "gram_escale": 8, "backedge_gram_rows": 9,
             "server_max_resident_us": 10, "verbose": 11, "ht16_open_eighths": 12, "backedge_single_pool": 13,
             "ht16_max_probes": 14, "host_chunk": 15, "gram_f16_widen": 16, "time_small_launches": 17,
-            "sched_min_queries": 18, "diverse_pool": 19, "sched_lloyd_iters": 20}
+            "sched_min_queries": 18, "diverse_pool": 19, "sched_lloyd_iters": 20, "flat_chunk_rows": 21}
+DBG_FLAT_CHUNK_ROWS = DBG_KEYS["flat_chunk_rows"]
 FAMILIES = ("one_wave", "team", "pair", "persistent", "server", "pq_lut", "diverse")
 
 _lib = None

@@ -18,6 +18,7 @@
 
 #include "dann_device.h"
 #include "dann_internal.h"
+#include "flat_plan.h"
 #include "wave_lists.h"  // kTagReadable
 
 namespace dann {
@@ -1496,6 +1497,137 @@ int32_t dann_rerank_batch(dann_index* idx, const void* queries, uint32_t nq, con
     DANN_HIP(hipMemcpyAsync(out_ids, bi.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, idx->main.stream));
     DANN_HIP(hipMemcpyAsync(out_dists, bd.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, idx->main.stream));
     DANN_HIP(hipStreamSynchronize(idx->main.stream));
+    return DANN_OK;
+} DANN_CATCH_ALL
+
+// ---- exhaustive scan (flat_kernels.hip): FlatIndex::knn_search ---------------------------------------------------------
+}  // extern "C"
+namespace {
+// the checks both forms share; DANN_OK with *done set: nothing to launch and nothing to write
+int32_t flat_check(const dann_index* idx, const void* queries, uint32_t nq, uint32_t first_slot, uint32_t n, uint32_t k,
+                   uint32_t flags, const uint32_t* out_ids, const float* out_dists, bool* done) {
+    *done = false;
+    if (flags & ~(uint32_t)DANN_FLAT_SKIP_DELETED) {
+        set_error("dann_flat_search_batch: unknown flag bits 0x%x", flags & ~(uint32_t)DANN_FLAT_SKIP_DELETED);
+        return DANN_EINVAL;
+    }
+    if (k == 0) {
+        set_error("dann_flat_search_batch: k cannot be zero");
+        return DANN_EINVAL;
+    }
+    if (idx->cfg.dtype == DT_PQ) {
+        set_error("dann_flat_search_batch: not defined on DANN_PQ rows (dann_pq_scan scores PQ codes)");
+        return DANN_EUNSUPPORTED;
+    }
+    if (k > kFlatMaxK) {
+        set_error("dann_flat_search_batch: k = %u exceeds the supported maximum of %u", k, kFlatMaxK);
+        return DANN_EUNSUPPORTED;
+    }
+    if ((uint64_t)first_slot + n > idx->nslots) {
+        set_error("dann_flat_search_batch: slots [%u, %llu) leave the index's %u slots", first_slot,
+                  (unsigned long long)first_slot + n, idx->nslots);
+        return DANN_EBOUNDS;
+    }
+    if (nq == 0) {
+        *done = true;
+        return DANN_OK;
+    }
+    if (!queries || !out_ids || !out_dists) {
+        set_error("dann_flat_search_batch: null pointer");
+        return DANN_EINVAL;
+    }
+    return DANN_OK;
+}
+
+// how the scan of `nq` queries is cut up (flat_plan.h)
+int32_t flat_make_plan(const dann_index* idx, uint32_t nq, uint32_t n, uint32_t k, FlatPlan* plan) {
+    const IndexView ix = idx->qview();
+    *plan = flat_plan(n, nq, k, flat_query_slot_bytes(ix), idx->num_cus, idx->dbg_u32(DANN_DBG_FLAT_CHUNK_ROWS, 0u));
+    if (plan->tile == 0) {
+        set_error("dann_flat_search_batch: a query of %u bytes with k = %u does not fit the LDS", ix.qbytes, k);
+        return DANN_EUNSUPPORTED;
+    }
+    if (idx->verbose())
+        fprintf(stderr, "[dann] flat scan: n %u nq %u k %u -> tile %u, %u chunks of %u slots, %u queries per launch\n", n, nq, k,
+                plan->tile, plan->nchunks, plan->chunk_rows, plan->batch);
+    return DANN_OK;
+}
+
+// the scan of nq queries (at most as many as the plan was made for) on device buffers, plan.batch queries per launch;
+// `scratch`: plan.scratch_bytes()
+int32_t flat_run(dann_index* idx, hipStream_t st, const FlatPlan& plan, void* scratch, const void* d_queries, uint32_t nq,
+                 uint32_t first_slot, uint32_t n, uint32_t flags, uint32_t* d_ids, float* d_dists, dann_search_stats* d_stats) {
+    const IndexView ix = idx->qview();
+    const uint32_t* deleted = (flags & DANN_FLAT_SKIP_DELETED) ? idx->d_deleted : nullptr;
+    for (uint32_t off = 0; off < nq; off += plan.batch) {
+        const uint32_t m = std::min(plan.batch, nq - off);
+        int32_t rc = launch_flat_search(ix, plan, (const uint8_t*)d_queries + (size_t)off * ix.qbytes, m, first_slot, n, deleted,
+                                        scratch, d_ids + (size_t)off * plan.k, d_dists + (size_t)off * plan.k,
+                                        d_stats ? d_stats + off : nullptr, st);
+        if (rc != DANN_OK) return rc;
+    }
+    return DANN_OK;
+}
+}  // namespace
+extern "C" {
+
+int32_t dann_flat_search_batch_device(dann_index* idx, const void* d_queries, uint32_t nq, uint32_t first_slot, uint32_t n,
+                                      uint32_t k, uint32_t flags, uint32_t* d_out_ids, float* d_out_dists,
+                                      dann_search_stats* d_out_stats) try {
+    CHECK_IDX_SHARED(idx);
+    ArenaTrim _trim{ctx};
+    bool done = false;
+    if (int32_t rc = flat_check(idx, d_queries, nq, first_slot, n, k, flags, d_out_ids, d_out_dists, &done)) return rc;
+    if (done) return DANN_OK;
+    if (n == 0) {
+        if (int32_t rc = launch_flat_empty(nq, k, d_out_ids, d_out_dists, d_out_stats, ctx.stream)) return rc;
+    } else {
+        FlatPlan plan;
+        if (int32_t rc = flat_make_plan(idx, nq, n, k, &plan)) return rc;
+        if (int32_t rc = grow_stage(ctx, 4, plan.scratch_bytes())) return rc;
+        if (int32_t rc = flat_run(idx, ctx.stream, plan, ctx.stage[4], d_queries, nq, first_slot, n, flags, d_out_ids,
+                                  d_out_dists, d_out_stats))
+            return rc;
+    }
+    DANN_HIP(hipStreamSynchronize(ctx.stream));
+    return DANN_OK;
+} DANN_CATCH_ALL
+
+int32_t dann_flat_search_batch(dann_index* idx, const void* queries, uint32_t nq, uint32_t first_slot, uint32_t n,
+                               uint32_t k, uint32_t flags, uint32_t* out_ids, float* out_dists,
+                               dann_search_stats* out_stats) try {
+    CHECK_IDX_SHARED(idx);
+    ArenaTrim _trim{ctx};
+    bool done = false;
+    if (int32_t rc = flat_check(idx, queries, nq, first_slot, n, k, flags, out_ids, out_dists, &done)) return rc;
+    if (done) return DANN_OK;
+    hipStream_t st = ctx.stream;
+    const size_t qb = idx->query_bytes();
+    // the call's queries go through the arena in pieces of at most 65536: queries | ids | distances | stats | chunk lists
+    const uint32_t piece = std::min<uint32_t>(nq, 65536u);
+    FlatPlan plan;
+    if (n != 0)
+        if (int32_t rc = flat_make_plan(idx, piece, n, k, &plan)) return rc;
+    Carve cv;
+    const size_t o_q = cv.take((size_t)piece * qb + 16), o_i = cv.take((size_t)piece * k * 4),
+                 o_d = cv.take((size_t)piece * k * 4), o_s = cv.take((size_t)piece * sizeof(dann_search_stats)),
+                 o_x = cv.take(n != 0 ? plan.scratch_bytes() : 0);
+    if (int32_t grc = grow_stage(ctx, 4, cv.off)) return grc;
+    void* const ar = ctx.stage[4];
+    const ArenaPtr bq{ar, o_q}, bi{ar, o_i}, bd{ar, o_d}, bs{ar, o_s}, bx{ar, o_x};
+    for (uint32_t off = 0; off < nq; off += piece) {
+        const uint32_t m = std::min(piece, nq - off);
+        DANN_HIP(hipMemcpyAsync(bq.p, (const uint8_t*)queries + (size_t)off * qb, (size_t)m * qb, hipMemcpyHostToDevice, st));
+        int32_t rc = n == 0 ? launch_flat_empty(m, k, bi.as<uint32_t>(), bd.as<float>(), bs.as<dann_search_stats>(), st)
+                            : flat_run(idx, st, plan, bx.p, bq.p, m, first_slot, n, flags, bi.as<uint32_t>(), bd.as<float>(),
+                                       bs.as<dann_search_stats>());
+        if (rc != DANN_OK) return rc;
+        DANN_HIP(hipMemcpyAsync(out_ids + (size_t)off * k, bi.p, (size_t)m * k * 4, hipMemcpyDeviceToHost, st));
+        DANN_HIP(hipMemcpyAsync(out_dists + (size_t)off * k, bd.p, (size_t)m * k * 4, hipMemcpyDeviceToHost, st));
+        if (out_stats)
+            DANN_HIP(hipMemcpyAsync(out_stats + off, bs.p, (size_t)m * sizeof(dann_search_stats), hipMemcpyDeviceToHost, st));
+        DANN_HIP(hipStreamSynchronize(st));
+    }
     return DANN_OK;
 } DANN_CATCH_ALL
 

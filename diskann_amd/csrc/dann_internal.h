@@ -236,6 +236,16 @@ int32_t launch_pq_pack(const IndexView& ix, uint8_t* d_pack, uint32_t stride, ui
 // raw rows x[i] vs y[i] (pair kernel numerics), n pairs of `bytes` each
 int32_t launch_distance_raw(const IndexView& ix, const void* d_x, const void* d_y, uint64_t stride, uint32_t n,
                             float* d_out, hipStream_t stream);
+// flat_kernels.hip: the exhaustive scan of dann_flat_search_batch(_device), cut up as flat_plan.h says.  One launch pair
+// serves at most plan.batch queries over slots [first, first + n), n > 0; `scratch` holds plan.scratch_bytes();
+// d_deleted: the deleted bitmap when it is to be honoured, else null.
+struct FlatPlan;
+uint32_t flat_query_slot_bytes(const IndexView& ix);  // bytes of one staged query in LDS
+int32_t launch_flat_search(const IndexView& ix, const FlatPlan& plan, const void* d_queries, uint32_t nq, uint32_t first,
+                           uint32_t n, const uint32_t* d_deleted, void* scratch, uint32_t* d_ids, float* d_dists,
+                           dann_search_stats* d_stats, hipStream_t stream);
+int32_t launch_flat_empty(uint32_t nq, uint32_t k, uint32_t* d_ids, float* d_dists, dann_search_stats* d_stats,
+                          hipStream_t stream);
 
 }  // namespace dann
 

@@ -356,6 +356,32 @@ class Provider:
               "dann_rerank_batch")
         return ids, d
 
+    # -- FlatIndex::knn_search ------------------------------------------------------
+    def flat_search(self, queries, k, first=0, n=None, skip_deleted=False, stats=False):
+        """Exhaustive k-NN over the slots [first, first + n) (n None: the rest of the capacity, start points not included):
+        the first k rows under (distance ascending, slot descending).  Returns (ids[nq, k], dists[nq, k]), with
+        stats=True also the SearchStats records; places behind the last result hold 0xFFFFFFFF / +inf."""
+        q = np.ascontiguousarray(queries, dtype=self.query_dtype).reshape(-1, self.query_elems)
+        nq = q.shape[0]
+        n = self.capacity - first if n is None else n
+        ids = np.empty((nq, k), np.uint32)
+        dists = np.empty((nq, k), np.float32)
+        st = np.zeros(nq, STATS_DTYPE)
+        flags = _ffi.FLAT_SKIP_DELETED if skip_deleted else 0
+        check(_ffi.lib().dann_flat_search_batch(self._h, _p(q), nq, int(first), int(n), int(k), flags, _p(ids), _p(dists),
+                                                _p(st) if stats else None), "dann_flat_search_batch")
+        return (ids, dists, st) if stats else (ids, dists)
+
+    def flat_search_device(self, d_queries, nq, k, d_ids, d_dists, first=0, n=None, skip_deleted=False, d_stats=0):
+        """the same on device addresses (ints) of the index's device: nq query images, nq x k ids and distances, and
+        optionally nq SearchStats records; complete on return"""
+        n = self.capacity - first if n is None else n
+        flags = _ffi.FLAT_SKIP_DELETED if skip_deleted else 0
+        check(_ffi.lib().dann_flat_search_batch_device(self._h, C.c_void_p(int(d_queries)), int(nq), int(first), int(n), int(k),
+                                                       flags, C.c_void_p(int(d_ids)), C.c_void_p(int(d_dists)),
+                                                       C.c_void_p(int(d_stats)) if d_stats else None),
+              "dann_flat_search_batch_device")
+
     def search_record(self, slots, l_value, rec_stride=None):
         s = np.ascontiguousarray(slots, dtype=np.uint32)
         rec_stride = rec_stride or 4 * (l_value + self.num_start_points) + 64

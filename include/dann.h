@@ -333,6 +333,32 @@ int32_t dann_rerank_batch(dann_index* idx, const void* queries, uint32_t nq, con
 /* device-pointer form (queries, cand_ids, outputs on the index's device) */
 int32_t dann_rerank_batch_device(dann_index* idx, const void* d_queries, uint32_t nq, const uint32_t* d_cand_ids,
                                  uint32_t cand_stride, uint32_t k, uint32_t* d_out_ids, float* d_out_dists);
+/* Exhaustive (flat) k-NN: diskann::flat::FlatIndex::knn_search (diskann/src/flat/index.rs:57-99) for nq queries over
+ * the slots [first_slot, first_slot + n), every row scored with the index's own distance (any row type but DANN_PQ, for
+ * which DANN_EUNSUPPORTED; the queries are images of dann_query_bytes() bytes in the current query layout).  The
+ * reference streams the elements in ascending id order through NeighborPriorityQueue::insert on a queue of capacity k
+ * (diskann/src/neighbor/queue.rs:130-171): a NaN distance is dropped; a candidate is dropped only when the queue is full
+ * and its last distance is smaller; otherwise it goes in at the first entry whose distance is >= its own, the last entry
+ * leaving a full queue.  The result is therefore the first k non-NaN elements under the strict total order
+ *     (distance ascending, with -0.0 == +0.0; scan position descending),
+ * listed in that order: among equal distances the slot scanned later comes first, and wins the k-th place.
+ * The caller names the populated range (start-point slots may be part of it).  On an inline_tags index a slot whose
+ * tag is below Tag::PUBLISHED is skipped and not counted, as in the searches; with DANN_FLAT_SKIP_DELETED so is a slot
+ * marked by dann_delete_points (without the flag the deleted state is not consulted).
+ * out_ids / out_dists: nq x k, the places behind the last result hold 0xFFFFFFFF / +infinity.  out_stats (optional): cmps =
+ * rows evaluated (those with a NaN distance included), hops = 0, result_count = written = min(k, rows inserted) -- the
+ * Translate post-processor's k - 1 is not part of this path.
+ * Errors: DANN_EINVAL for k == 0, a null pointer with nq > 0 or an unknown flag bit; DANN_EBOUNDS when the range
+ * leaves [0, capacity + num_start_points); DANN_EUNSUPPORTED for k > 1024.  nq == 0 writes nothing; with n == 0 every
+ * result is empty. */
+enum { DANN_FLAT_SKIP_DELETED = 1 };
+int32_t dann_flat_search_batch(dann_index* idx, const void* queries, uint32_t nq, uint32_t first_slot, uint32_t n,
+                               uint32_t k, uint32_t flags, uint32_t* out_ids, float* out_dists,
+                               dann_search_stats* out_stats);
+/* device-pointer form (queries and outputs on the index's device; complete on return) */
+int32_t dann_flat_search_batch_device(dann_index* idx, const void* d_queries, uint32_t nq, uint32_t first_slot, uint32_t n,
+                                      uint32_t k, uint32_t flags, uint32_t* d_out_ids, float* d_out_dists,
+                                      dann_search_stats* d_out_stats);
 /* insert-time search: also returns the VisitedSearchRecord (record.rs:86-93) per query:
  * rec_ids/rec_dists: nq x rec_stride, rec_n: nq */
 int32_t dann_search_record_batch(dann_index* idx, const uint32_t* slots, uint32_t nq, uint32_t l_value,

@@ -75,7 +75,10 @@ enum {
     DANN_DBG_SCHED_LLOYD_ITERS = 20,     /* Lloyd iterations that move the scheduling pivots from rows taken at a fixed stride
                                             to centres of a row sample, when the pivots are (re)built (0: the rows
                                             themselves; at most 64; default 4) */
-    DANN_DBG_COUNT = 21
+    DANN_DBG_FLAT_CHUNK_ROWS = 21,       /* test hook: slots per chunk of the exhaustive scan (dann_flat_search_batch; default 0:
+                                            sized so that chunks x query tiles fill the device): small ranges cross chunk
+                                            boundaries with it */
+    DANN_DBG_COUNT = 22
 };
 int32_t dann_debug_set(dann_index* idx, int32_t key, double value);
 int32_t dann_debug_get(const dann_index* idx, int32_t key, double* value);
