@@ -7,9 +7,9 @@ ARCH    ?= gfx950
 FLAGS   := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-gpu-flush-denormals-to-zero
 CSRC    := diskann_amd/csrc
 OBJDIR  := diskann_amd/build
-SOURCES := api host_search search_kernels search_f32 search_f16 search_u8 search_i8 search_sq8 search_sq4 search_sq1 search_sph1 search_sph1t search_sph2 search_sph4 search_mm1 search_mm2 search_mm4 search_mm8 search_pq search_pqlut search_pqlut2 search_pqlut3 search_pqlut4 search_pair server sharded paged_kernels \
-           distance_kernels flat_kernels maxsim_kernels maxsim_mm_kernels minmax_kernels transform_kernels spherical_kernels build_kernels pq_kernels query_schedule consolidate inplace_delete search_diverse
-OBJS    := $(SOURCES:%=$(OBJDIR)/%.o)
+# every .hip file of the source directory is a translation unit of the library (sorted: a stable link order)
+SOURCES := $(sort $(wildcard $(CSRC)/*.hip))
+OBJS    := $(SOURCES:$(CSRC)/%.hip=$(OBJDIR)/%.o)
 HEADERS := $(wildcard $(CSRC)/*.h) include/dann.h
 LIB     := diskann_amd/libdann_hip.so
 

@@ -8,9 +8,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libdann_hip.so")
-SOURCES = ["api.hip", "host_search.hip", "search_kernels.hip", "search_f32.hip", "search_f16.hip", "search_u8.hip", "search_i8.hip",
-           "search_sq8.hip", "search_sq4.hip", "search_sq1.hip", "search_sph1.hip", "search_sph1t.hip", "search_sph2.hip", "search_sph4.hip", "search_mm1.hip", "search_mm2.hip", "search_mm4.hip", "search_mm8.hip", "search_pq.hip", "search_pqlut.hip", "search_pqlut2.hip", "search_pqlut3.hip", "search_pqlut4.hip", "search_pair.hip", "server.hip", "sharded.hip", "paged_kernels.hip", "distance_kernels.hip", "flat_kernels.hip", "maxsim_kernels.hip", "maxsim_mm_kernels.hip", "minmax_kernels.hip", "transform_kernels.hip", "spherical_kernels.hip", "build_kernels.hip", "pq_kernels.hip",
-           "query_schedule.hip", "consolidate.hip", "inplace_delete.hip", "search_diverse.hip"]
+# every .hip file of csrc is a translation unit of the library (sorted: a stable link order)
+SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fgpu-flush-denormals-to-zero=0" if False else "-fno-gpu-flush-denormals-to-zero", "-Wall",
          "-Wno-unused-function"]
@@ -66,7 +65,9 @@ def build(force=False, verbose=False):
         return obj
 
     if jobs:
-        with cf.ThreadPoolExecutor(max_workers=min(max(os.cpu_count() or 4, 4), len(jobs))) as ex:
+        # (not os.cpu_count(): on a shared machine it reports the whole box)
+        workers = int(os.environ.get("MAX_JOBS") or 16)
+        with cf.ThreadPoolExecutor(max_workers=max(1, min(workers, len(jobs)))) as ex:
             list(ex.map(cc, jobs))
     objs = [os.path.join(objdir, s.replace(".hip", ".o")) for s in SOURCES]
     if jobs or force or _stale(OUT, objs):

@@ -119,8 +119,8 @@ struct SearchCtx {
     uint32_t spill_slices = 0, spill_bits = 0;
     uint32_t* h_flag = nullptr;  // pinned, device-visible: set by a query that exhausts its scratch
     // grow-only device staging for the host-pointer search entry (no hipMalloc / hipFree per call)
-    // [0] queries, [1] outputs, [2] stats, [3] unused, [4] the scratch arena of the
-    // range / filtered searches (one block, carved per call)
+    // [0] queries, [1] outputs, [2] stats, [3] unused, [4] the arena of the staged host-pointer calls (host_stage.h: range,
+    // filtered, diverse, flat; on `main`: rerank, record) and the flat scan's chunk lists (one block, laid out per call)
     void* stage[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     size_t stage_bytes[5] = {0, 0, 0, 0, 0};
     void* h_stage = nullptr;     // pinned host staging (small batches: one H2D + one D2H per call; large: chunk ring)
@@ -466,12 +466,12 @@ struct DeviceGuard {
         if (prev >= 0 && prev != cur) (void)hipSetDevice(prev);  // hipSetDevice costs ~0.5 ms on ROCm 7.2
     }
 };
-// api.hip: one Knn search launch (with the overflow retry) on device buffers, on context `ctx`
+// api_search.hip: one Knn search launch (with the overflow retry) on device buffers, on context `ctx`
 int32_t search_device(dann_index* idx, SearchCtx& ctx, const void* d_queries, const uint32_t* d_qslots, uint32_t nq,
                       uint32_t l_value, uint32_t beam, uint32_t k, uint32_t* d_ids, float* d_dists,
                       dann_search_stats* d_stats, uint32_t* d_rec_ids, float* d_rec_d, uint32_t rec_stride,
                       uint32_t* d_rec_n);
-// api.hip: grow the context's device staging block `i` to at least `need` bytes (grow-only, 25 % headroom)
+// api_index.hip: grow the context's device staging block `i` to at least `need` bytes (grow-only, 25 % headroom)
 int32_t grow_stage(SearchCtx& ctx, int i, size_t need);
 }  // namespace dann
 

@@ -18,8 +18,7 @@
 #include <mutex>
 #include <vector>
 
-#include "dann_device.h"
-#include "dann_internal.h"
+#include "api_common.h"
 
 namespace dann {
 namespace {
@@ -358,13 +357,8 @@ int32_t dann_paged_begin(dann_index* idx, const void* queries, uint32_t nq, uint
         return DANN_EUNSUPPORTED;
     }
     // read-only on the index: sessions of different callers run side by side, each call on a leased context
-    std::shared_lock<std::shared_mutex> rd(idx->rw);
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    if (prev != idx->device) DANN_HIP(hipSetDevice(idx->device));
-    ::dann::CtxLease lease(idx);
-    if (lease.status != DANN_OK) return lease.status;
-    hipStream_t stream = lease.ctx->stream;
+    CHECK_IDX_SHARED(idx);
+    hipStream_t stream = ctx.stream;
     dann_paged* s = new dann_paged();
     s->idx = idx;
     const uint32_t nslots = idx->nslots;
@@ -443,13 +437,8 @@ int32_t dann_paged_next(dann_paged* s, uint32_t k, uint32_t* out_ids, float* out
         return DANN_EINVAL;
     }
     dann_index* idx = s->idx;
-    std::shared_lock<std::shared_mutex> rd(idx->rw);
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    if (prev != idx->device) DANN_HIP(hipSetDevice(idx->device));
-    ::dann::CtxLease lease(idx);
-    if (lease.status != DANN_OK) return lease.status;
-    hipStream_t stream = lease.ctx->stream;
+    CHECK_IDX_SHARED(idx);
+    hipStream_t stream = ctx.stream;
     const uint32_t nq = s->a.nq;
     if (s->out_k < k) {
         DANN_HIP(s->out_ids.alloc((size_t)nq * k * 4));

@@ -42,7 +42,7 @@ FILTERED_TYPES = ("F32", "U8", "SQ8", "SQ1", "SPH1")
 VISITED_TYPES = ("F32", "SQ4", "SPH1")
 DOOR_TYPES = ("U8", "SQ4", "SPH2")
 SELECTIVITY, ADAPTIVE_SELECTIVITY = 0.3, 0.05
-# AdaptiveL at L = 60, one start point: api.hip sizes the queue for the largest L the decision table holds, L * scale
+# AdaptiveL at L = 60, one start point: api_search.hip sizes the queue for the largest L the decision table holds, L * scale
 # (no match among the samples), so qcap_max = max(60 * scale, 61): 240 -> QS = 4, 480 -> QS = 8
 ADAPTIVE_L, ADAPTIVE = 60, ((50, 4.0), (50, 8.0))
 
@@ -177,7 +177,7 @@ TABLE = build_table()
 
 
 def adaptive_qcap_max(L, nstart, adaptive, beam=1, max_degree=R):
-    """SearchArgs::qcap_max as api.hip (filtered_search) computes it: the largest entry of the decision table"""
+    """SearchArgs::qcap_max as api_search.hip (filtered_search) computes it: the largest entry of the decision table"""
     import math
     samples, scale = adaptive
     cmax = max((beam * max_degree + 63) & ~63, (nstart + 63) & ~63)

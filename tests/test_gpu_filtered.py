@@ -208,6 +208,45 @@ def test_inline_many_queries_cross_chunks():
         assert (int(st["cmps"][qi]), int(st["hops"][qi])) == (int(ws[0]), int(ws[1]))
 
 
+def _range_cross_chunks_case():
+    """graph, queries and per-query bitmaps of test_filtered_range_many_queries_cross_chunks, and the queries one chunk
+    holds: filtered_search's per_query bound (api_search.hip) under the default tie order"""
+    L, radius, out_cap, matched_cap = 16, 14.0, 256, 3001
+    rng = np.random.default_rng(29)
+    n, dim, R = 3000, 16, 16
+    m_cap = min(max(matched_cap, 64), n + 1)
+    key_cap = 1 << (m_cap + L - 1).bit_length()
+    rcap = max(min(max(4 * out_cap + 1024, m_cap), n + 1), 1)
+    chunk = (1 << 30) // (m_cap * 8 + key_cap * 8 + rcap * 8 + 64 + 2560)
+    nq = chunk + 700
+    data = rng.standard_normal((n, dim)).astype(np.float32)
+    adj = random_graph(rng, n, R)
+    queries = rng.standard_normal((nq, dim)).astype(np.float32)
+    match = rng.random((nq, n + 1)) < 0.2
+    return data, adj, R, queries, match, chunk, (L, radius, out_cap, matched_cap)
+
+
+def test_filtered_range_many_queries_cross_chunks():
+    """the filtered-range twin of test_inline_many_queries_cross_chunks: ids, distances, the second-round flags and the
+    stats of the later chunks land at their queries' places.  (At this radius the oracle gives no query more than 147
+    results, over half of the queries have some and 1 824 run a second round: none comes near out_cap.)"""
+    data, adj, R, queries, match, chunk, (L, radius, out_cap, matched_cap) = _range_cross_chunks_case()
+    nq = len(queries)
+    assert chunk < nq
+    ox, px = make_pair(oracle.F32, oracle.L2, data, adj, data[:1].copy(), R)
+    px.kernel_time_reset()
+    ids, dists, st, sec = px.filtered_range_search(queries, L, radius, match, out_cap=out_cap, matched_cap=matched_cap)
+    _, launches = px.kernel_time(0)
+    assert launches >= 2
+    assert not st["status"].any()
+    for qi in range(nq):  # (the oracle answers a query in some 50 us: every query, both sides of the boundary included)
+        wi, wd, ws = ox.filtered_range_search(queries[qi], L, radius, match[qi])
+        m = int(st["written"][qi])
+        assert m == len(wi), qi
+        assert np.array_equal(ids[qi, :m], wi) and np.array_equal(dists[qi, :m].view(np.uint32), wd.view(np.uint32)), qi
+        assert (int(st["cmps"][qi]), int(st["hops"][qi]), int(sec[qi])) == (int(ws[0]), int(ws[1]), int(ws[3])), qi
+
+
 @pytest.mark.parametrize("mode", ["inline", "multihop"])
 def test_equal_distances_follow_the_references_unstable_sort(mode):
     """`matched_results.sort_unstable_by(fast_distance)` (inline_filter_search.rs:274) and the multihop search's

@@ -213,6 +213,26 @@ def test_empty_range_and_no_queries(u8_ties):
     assert ids.shape == (0, 4) and d.shape == (0, 4)
 
 
+def test_host_form_across_its_query_piece(u8_ties):
+    """the host form stages its queries in pieces of 65 536: 65 536 + 7 queries (16 distinct ones, tiled) over 64 slots
+    equal the model on both sides of the boundary, and so do the padded answers of an empty scan"""
+    oix, gix, _ = u8_ties
+    distinct = np.random.default_rng(6).integers(0, 2, (16, 8), dtype=np.uint8)
+    nq, n, k = 65536 + 7, 64, 3
+    D, seen = oracle_distances(oix, distinct, np.arange(n, dtype=np.uint32))
+    wi, wd, wn = expect(D, seen, (k,))[k]
+    q = np.ascontiguousarray(np.tile(distinct, (nq // 16 + 1, 1))[:nq])
+    ids, d, st = gix.flat_search(q, k, first=0, n=n, stats=True)
+    rep = np.arange(nq) % 16
+    assert np.array_equal(ids, wi[rep])
+    assert np.array_equal(fbits(d), fbits(wd[rep]))
+    assert (st["cmps"] == n).all() and (st["hops"] == 0).all() and (st["status"] == 0).all()
+    assert np.array_equal(st["written"], wn[rep]) and np.array_equal(st["result_count"], wn[rep])
+    ids, d, st = gix.flat_search(q, k, first=0, n=0, stats=True)
+    assert ids.shape == (nq, k) and (ids == 0xFFFFFFFF).all() and np.isposinf(d).all()
+    assert not st["cmps"].any() and not st["written"].any() and not st["result_count"].any()
+
+
 def test_nan_row_is_counted_and_never_returned():
     rng = np.random.default_rng(11)
     n, dim = 300, 24

@@ -241,7 +241,7 @@ def test_refusals_are_where_the_design_puts_them():
 
 
 def test_adaptive_queue_sizes_cross_a_class():
-    """qcap_max as api.hip computes it: 60 -> 240 (QS = 4) and 60 -> 480 (QS = 8), both from QS = 1"""
+    """qcap_max as api_search.hip computes it: 60 -> 240 (QS = 4) and 60 -> 480 (QS = 8), both from QS = 1"""
     got = [sm.adaptive_qcap_max(sm.ADAPTIVE_L, 1, a) for a in sm.ADAPTIVE]
     assert got == [240, 480] and qs_of(sm.ADAPTIVE_L + 1) == 1 and [qs_of(q) for q in got] == [4, 8]
 
