@@ -58,6 +58,11 @@ RNG_INDEX_FN = C.CFUNCTYPE(C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64)
 RNG_F64_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_uint32, C.c_double)
 
 
+class FlatFilter(C.Structure):
+    """dann_flat_filter: the bitmaps of an exhaustive scan (host memory; device memory in the _device forms)"""
+    _fields_ = [("bits", C.c_void_p), ("stride_words", C.c_uint64)]
+
+
 class Diverse(C.Structure):
     """dann_diverse: DiverseSearchParams without the attribute provider (dann_set_attributes holds the values)"""
     _fields_ = [("diverse_k", C.c_uint32), ("total_k", C.c_uint32)]
@@ -156,6 +161,13 @@ SYMBOLS = {
     "dann_rerank_batch_device": (_i32, [_vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp]),
     "dann_flat_search_batch": (_i32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     "dann_flat_search_batch_device": (_i32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "dann_flat_filtered_search_batch": (_i32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _P(FlatFilter), _vp, _vp, _vp]),
+    "dann_flat_range_search_batch": (_i32, [_vp, _vp, _u32, _u32, _u32, _f32, _i32, _f32, _u32, _P(FlatFilter), _u32, _vp,
+                                            _vp, _vp, _vp]),
+    "dann_flat_filtered_search_batch_device": (_i32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _P(FlatFilter), _vp, _vp,
+                                                      _vp]),
+    "dann_flat_range_search_batch_device": (_i32, [_vp, _vp, _u32, _u32, _u32, _f32, _i32, _f32, _u32, _P(FlatFilter), _u32,
+                                                   _vp, _vp, _vp, _vp]),
     "dann_search_record_batch": (_i32, [_vp, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp]),
     "dann_mvset_create": (_i32, [_i32, _i32, _u32, _u32, _vp, _vp, _P(_vp)]),
     "dann_mvset_destroy": (_i32, [_vp]),

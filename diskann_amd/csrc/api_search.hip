@@ -4,6 +4,7 @@
 #include <cmath>
 
 #include "api_common.h"
+#include "flat_gt_launch.h"
 #include "flat_plan.h"
 #include "wave_lists.h"  // kTagReadable
 
@@ -666,6 +667,137 @@ int32_t flat_run(dann_index* idx, hipStream_t st, const FlatPlan& plan, void* sc
     }
     return DANN_OK;
 }
+
+// -- the same under a filter and within a radius (flat_gt_kernels.hip)
+// the filter of a call as the kernels take it: null bits = every slot matches
+struct FlatFilterArg {
+    const uint32_t* bits = nullptr;
+    uint64_t stride = 0;
+};
+
+int32_t flat_filter_check(const char* who, const dann_index* idx, const dann_flat_filter* filter, FlatFilterArg* f) {
+    f->bits = filter ? filter->bits : nullptr;
+    f->stride = f->bits ? filter->stride_words : 0;
+    const uint64_t words = ((uint64_t)idx->nslots + 31) / 32;
+    if (f->stride && f->stride < words) {
+        set_error("%s: filter stride %llu words is shorter than one bitmap (%llu words)", who, (unsigned long long)f->stride,
+                  (unsigned long long)words);
+        return DANN_EINVAL;
+    }
+    return DANN_OK;
+}
+
+int32_t flat_filtered_make_plan(const dann_index* idx, uint32_t nq, uint32_t n, uint32_t k, FlatFilteredPlan* plan) {
+    const IndexView ix = idx->qview();
+    *plan = flat_filtered_plan(n, nq, k, flat_query_slot_bytes(ix), idx->num_cus, idx->dbg_u32(DANN_DBG_FLAT_CHUNK_ROWS, 0u));
+    if (plan->p.tile == 0) {
+        set_error("dann_flat_filtered_search_batch: a query of %u bytes with k = %u does not fit the LDS", ix.qbytes, k);
+        return DANN_EUNSUPPORTED;
+    }
+    if (idx->verbose())
+        fprintf(stderr, "[dann] filtered flat scan: n %u nq %u k %u -> tile %u, %u chunks of %u slots, %u queries per launch\n",
+                n, nq, k, plan->p.tile, plan->p.nchunks, plan->p.chunk_rows, plan->p.batch);
+    return DANN_OK;
+}
+
+// the filtered scan of nq queries on device buffers, plan.p.batch queries per launch; d_bits: the bitmaps of these queries
+int32_t flat_filtered_run(dann_index* idx, hipStream_t st, const FlatFilteredPlan& plan, void* scratch, const void* d_queries,
+                          uint32_t nq, uint32_t first_slot, uint32_t n, uint32_t flags, const uint32_t* d_bits, uint64_t stride,
+                          uint32_t* d_ids, float* d_dists, dann_search_stats* d_stats) {
+    const IndexView ix = idx->qview();
+    const uint32_t* deleted = (flags & DANN_FLAT_SKIP_DELETED) ? idx->d_deleted : nullptr;
+    const uint32_t k = plan.p.k;
+    for (uint32_t off = 0; off < nq; off += plan.p.batch) {
+        const uint32_t m = std::min(plan.p.batch, nq - off);
+        int32_t rc = launch_flat_filtered_search(ix, plan, (const uint8_t*)d_queries + (size_t)off * ix.qbytes, m, first_slot, n,
+                                                 deleted, d_bits + (size_t)off * stride, stride, scratch, d_ids + (size_t)off * k,
+                                                 d_dists + (size_t)off * k, d_stats ? d_stats + off : nullptr, st);
+        if (rc != DANN_OK) return rc;
+    }
+    return DANN_OK;
+}
+
+struct FlatRangeCall {
+    uint32_t first_slot, n;
+    float radius, inner_radius;
+    bool has_inner;
+    uint32_t flags, out_cap;
+};
+
+// the checks both forms of the range scan share; DANN_OK with *done set: nothing to launch and nothing to write
+int32_t flat_range_check(const dann_index* idx, const void* queries, uint32_t nq, const FlatRangeCall& c, const uint32_t* out_ids,
+                         const float* out_dists, const uint32_t* out_counts, bool* done) {
+    *done = false;
+    if (c.flags & ~(uint32_t)DANN_FLAT_SKIP_DELETED) {
+        set_error("dann_flat_range_search_batch: unknown flag bits 0x%x", c.flags & ~(uint32_t)DANN_FLAT_SKIP_DELETED);
+        return DANN_EINVAL;
+    }
+    if (c.radius != c.radius) {
+        set_error("dann_flat_range_search_batch: the radius is NaN");
+        return DANN_EINVAL;
+    }
+    if (c.has_inner && !(c.inner_radius <= c.radius)) {  // RangeSearchError::InnerRadiusGreaterThanRadius; a NaN too
+        set_error("dann_flat_range_search_batch: inner radius %g must not exceed the radius %g", c.inner_radius, c.radius);
+        return DANN_EINVAL;
+    }
+    if (idx->cfg.dtype == DT_PQ) {
+        set_error("dann_flat_range_search_batch: not defined on DANN_PQ rows (dann_pq_scan scores PQ codes)");
+        return DANN_EUNSUPPORTED;
+    }
+    if ((uint64_t)c.first_slot + c.n > idx->nslots) {
+        set_error("dann_flat_range_search_batch: slots [%u, %llu) leave the index's %u slots", c.first_slot,
+                  (unsigned long long)c.first_slot + c.n, idx->nslots);
+        return DANN_EBOUNDS;
+    }
+    if (nq == 0) {
+        *done = true;
+        return DANN_OK;
+    }
+    if (!queries || !out_counts || (c.out_cap && (!out_ids || !out_dists))) {
+        set_error("dann_flat_range_search_batch: null pointer");
+        return DANN_EINVAL;
+    }
+    return DANN_OK;
+}
+
+int32_t flat_range_make_plan(const dann_index* idx, uint32_t nq, uint32_t n, FlatRangePlan* plan) {
+    const IndexView ix = idx->qview();
+    *plan = flat_range_plan(n, nq, flat_query_slot_bytes(ix), idx->num_cus, idx->dbg_u32(DANN_DBG_FLAT_CHUNK_ROWS, 0u));
+    if (plan->tile == 0) {
+        set_error("dann_flat_range_search_batch: a query of %u bytes does not fit the LDS", ix.qbytes);
+        return DANN_EUNSUPPORTED;
+    }
+    if (idx->verbose())
+        fprintf(stderr, "[dann] flat range scan: n %u nq %u -> tile %u, %u chunks of %u slots, %u queries per launch\n", n, nq,
+                plan->tile, plan->nchunks, plan->chunk_rows, plan->batch);
+    return DANN_OK;
+}
+
+// the range scan of nq queries on device buffers, plan.batch queries per launch; the overflow flag behind the counts is
+// cleared first and stays set once any query had more matches than out_cap
+int32_t flat_range_run(dann_index* idx, hipStream_t st, const FlatRangePlan& plan, void* scratch, const void* d_queries,
+                       uint32_t nq, const FlatRangeCall& c, const uint32_t* d_bits, uint64_t stride, uint32_t* d_ids,
+                       float* d_dists, uint32_t* d_counts, dann_search_stats* d_stats) {
+    const IndexView ix = idx->qview();
+    const uint32_t* deleted = (c.flags & DANN_FLAT_SKIP_DELETED) ? idx->d_deleted : nullptr;
+    DANN_HIP(hipMemsetAsync(flat_range_overflow_flag(plan, scratch), 0, 4, st));
+    for (uint32_t off = 0; off < nq; off += plan.batch) {
+        const uint32_t m = std::min(plan.batch, nq - off);
+        int32_t rc = launch_flat_range_search(
+            ix, plan, (const uint8_t*)d_queries + (size_t)off * ix.qbytes, m, c.first_slot, c.n, c.radius, c.has_inner,
+            c.inner_radius, deleted, d_bits ? d_bits + (size_t)off * stride : nullptr, stride, c.out_cap, scratch,
+            d_ids ? d_ids + (size_t)off * c.out_cap : nullptr, d_dists ? d_dists + (size_t)off * c.out_cap : nullptr,
+            d_counts + off, d_stats ? d_stats + off : nullptr, st);
+        if (rc != DANN_OK) return rc;
+    }
+    return DANN_OK;
+}
+
+int32_t flat_range_overflowed(uint32_t out_cap) {
+    set_error("dann_flat_range_search_batch: a query has more matches than out_cap = %u (out_counts holds the true counts, "
+              "out_stats[q].status names the queries)", out_cap);
+    return DANN_EOVERFLOW;
+}
 }  // namespace
 extern "C" {
 
@@ -714,6 +846,134 @@ int32_t dann_flat_search_batch(dann_index* idx, const void* queries, uint32_t nq
                       : flat_run(idx, ctx.stream, plan, hs.extra<void>(0), hs.in(0), m, first_slot, n, flags,
                                  hs.out<uint32_t>(0), hs.out<float>(1), hs.stats());
     });
+} DANN_CATCH_ALL
+
+// ---- exhaustive scans under a filter and within a radius (flat_gt_kernels.hip; helpers next to flat_check above) ----
+
+int32_t dann_flat_filtered_search_batch_device(dann_index* idx, const void* d_queries, uint32_t nq, uint32_t first_slot,
+                                               uint32_t n, uint32_t k, uint32_t flags, const dann_flat_filter* d_filter,
+                                               uint32_t* d_out_ids, float* d_out_dists, dann_search_stats* d_out_stats) try {
+    if (!d_filter || !d_filter->bits)  // every slot matches: the unfiltered scan
+        return dann_flat_search_batch_device(idx, d_queries, nq, first_slot, n, k, flags, d_out_ids, d_out_dists, d_out_stats);
+    CHECK_IDX_SHARED(idx);
+    ArenaTrim _trim{ctx};
+    bool done = false;
+    if (int32_t rc = flat_check(idx, d_queries, nq, first_slot, n, k, flags, d_out_ids, d_out_dists, &done)) return rc;
+    FlatFilterArg f;
+    if (int32_t rc = flat_filter_check("dann_flat_filtered_search_batch", idx, d_filter, &f)) return rc;
+    if (done) return DANN_OK;
+    if (n == 0) {
+        if (int32_t rc = launch_flat_empty(nq, k, d_out_ids, d_out_dists, d_out_stats, ctx.stream)) return rc;
+    } else {
+        FlatFilteredPlan plan;
+        if (int32_t rc = flat_filtered_make_plan(idx, nq, n, k, &plan)) return rc;
+        if (int32_t rc = grow_stage(ctx, 4, plan.scratch_bytes())) return rc;
+        if (int32_t rc = flat_filtered_run(idx, ctx.stream, plan, ctx.stage[4], d_queries, nq, first_slot, n, flags, f.bits,
+                                           f.stride, d_out_ids, d_out_dists, d_out_stats))
+            return rc;
+    }
+    DANN_HIP(hipStreamSynchronize(ctx.stream));
+    return DANN_OK;
+} DANN_CATCH_ALL
+
+int32_t dann_flat_filtered_search_batch(dann_index* idx, const void* queries, uint32_t nq, uint32_t first_slot, uint32_t n,
+                                        uint32_t k, uint32_t flags, const dann_flat_filter* filter, uint32_t* out_ids,
+                                        float* out_dists, dann_search_stats* out_stats) try {
+    if (!filter || !filter->bits)  // every slot matches: the unfiltered scan
+        return dann_flat_search_batch(idx, queries, nq, first_slot, n, k, flags, out_ids, out_dists, out_stats);
+    CHECK_IDX_SHARED(idx);
+    ArenaTrim _trim{ctx};
+    bool done = false;
+    if (int32_t rc = flat_check(idx, queries, nq, first_slot, n, k, flags, out_ids, out_dists, &done)) return rc;
+    FlatFilterArg f;
+    if (int32_t rc = flat_filter_check("dann_flat_filtered_search_batch", idx, filter, &f)) return rc;
+    if (done) return DANN_OK;
+    // pieces by flat_host_piece, the plan made for one piece; a shared bitmap goes up once.  extras: the plan's chunk lists, the shared bitmap
+    const size_t words = ((size_t)idx->nslots + 31) / 32;
+    const uint32_t piece = flat_host_piece(nq, f.stride, 0);
+    FlatFilteredPlan plan;
+    if (n != 0)
+        if (int32_t rc = flat_filtered_make_plan(idx, piece, n, k, &plan)) return rc;
+    const size_t scratch = n != 0 ? plan.scratch_bytes() : 0;
+    HostStage hs;
+    const int32_t lrc =
+        f.stride ? hs.layout(ctx, nq, piece, {{queries, idx->query_bytes()}, {f.bits, (size_t)f.stride * 4}},
+                             {{out_ids, (size_t)k * 4}, {out_dists, (size_t)k * 4}}, HostStage::kCopyStats, {scratch})
+                 : hs.layout(ctx, nq, piece, {{queries, idx->query_bytes()}},
+                             {{out_ids, (size_t)k * 4}, {out_dists, (size_t)k * 4}}, HostStage::kCopyStats, {scratch, words * 4});
+    if (lrc) return lrc;
+    if (!f.stride) DANN_HIP(hipMemcpyAsync(hs.extra<void>(1), f.bits, words * 4, hipMemcpyHostToDevice, ctx.stream));
+    return hs.walk(out_stats, nullptr, [&](uint32_t, uint32_t m) {
+        return n == 0 ? launch_flat_empty(m, k, hs.out<uint32_t>(0), hs.out<float>(1), hs.stats(), ctx.stream)
+                      : flat_filtered_run(idx, ctx.stream, plan, hs.extra<void>(0), hs.in(0), m, first_slot, n, flags,
+                                          f.stride ? hs.in<uint32_t>(1) : hs.extra<uint32_t>(1), f.stride, hs.out<uint32_t>(0),
+                                          hs.out<float>(1), hs.stats());
+    });
+} DANN_CATCH_ALL
+
+int32_t dann_flat_range_search_batch_device(dann_index* idx, const void* d_queries, uint32_t nq, uint32_t first_slot,
+                                            uint32_t n, float radius, int32_t has_inner_radius, float inner_radius,
+                                            uint32_t flags, const dann_flat_filter* d_filter, uint32_t out_cap,
+                                            uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
+                                            dann_search_stats* d_out_stats) try {
+    CHECK_IDX_SHARED(idx);
+    ArenaTrim _trim{ctx};
+    const FlatRangeCall c{first_slot, n, radius, inner_radius, has_inner_radius != 0, flags, out_cap};
+    bool done = false;
+    if (int32_t rc = flat_range_check(idx, d_queries, nq, c, d_out_ids, d_out_dists, d_out_counts, &done)) return rc;
+    FlatFilterArg f;
+    if (int32_t rc = flat_filter_check("dann_flat_range_search_batch", idx, d_filter, &f)) return rc;
+    if (done) return DANN_OK;
+    FlatRangePlan plan;
+    if (int32_t rc = flat_range_make_plan(idx, nq, n, &plan)) return rc;
+    if (int32_t rc = grow_stage(ctx, 4, plan.scratch_bytes())) return rc;
+    if (int32_t rc = flat_range_run(idx, ctx.stream, plan, ctx.stage[4], d_queries, nq, c, f.bits, f.stride, d_out_ids,
+                                    d_out_dists, d_out_counts, d_out_stats))
+        return rc;
+    uint32_t over = 0;
+    DANN_HIP(hipMemcpyAsync(&over, flat_range_overflow_flag(plan, ctx.stage[4]), 4, hipMemcpyDeviceToHost, ctx.stream));
+    DANN_HIP(hipStreamSynchronize(ctx.stream));
+    return over ? flat_range_overflowed(out_cap) : DANN_OK;
+} DANN_CATCH_ALL
+
+int32_t dann_flat_range_search_batch(dann_index* idx, const void* queries, uint32_t nq, uint32_t first_slot, uint32_t n,
+                                     float radius, int32_t has_inner_radius, float inner_radius, uint32_t flags,
+                                     const dann_flat_filter* filter, uint32_t out_cap, uint32_t* out_ids, float* out_dists,
+                                     uint32_t* out_counts, dann_search_stats* out_stats) try {
+    CHECK_IDX_SHARED(idx);
+    ArenaTrim _trim{ctx};
+    const FlatRangeCall c{first_slot, n, radius, inner_radius, has_inner_radius != 0, flags, out_cap};
+    bool done = false;
+    if (int32_t rc = flat_range_check(idx, queries, nq, c, out_ids, out_dists, out_counts, &done)) return rc;
+    FlatFilterArg f;
+    if (int32_t rc = flat_filter_check("dann_flat_range_search_batch", idx, filter, &f)) return rc;
+    if (done) return DANN_OK;
+    // pieces by flat_host_piece
+    const size_t words = ((size_t)idx->nslots + 31) / 32;
+    const uint32_t piece = flat_host_piece(nq, f.stride, out_cap);
+    FlatRangePlan plan;
+    if (int32_t rc = flat_range_make_plan(idx, piece, n, &plan)) return rc;
+    const size_t row = (size_t)out_cap * 4;
+    uint32_t* const h_ids = out_cap ? out_ids : nullptr;
+    float* const h_dists = out_cap ? out_dists : nullptr;
+    HostStage hs;
+    const int32_t lrc =
+        f.stride ? hs.layout(ctx, nq, piece, {{queries, idx->query_bytes()}, {f.bits, (size_t)f.stride * 4}},
+                             {{h_ids, row}, {h_dists, row}, {out_counts, 4}}, HostStage::kCopyStats, {plan.scratch_bytes()})
+                 : hs.layout(ctx, nq, piece, {{queries, idx->query_bytes()}}, {{h_ids, row}, {h_dists, row}, {out_counts, 4}},
+                             HostStage::kCopyStats, {plan.scratch_bytes(), f.bits ? words * 4 : 0});
+    if (lrc) return lrc;
+    if (f.bits && !f.stride) DANN_HIP(hipMemcpyAsync(hs.extra<void>(1), f.bits, words * 4, hipMemcpyHostToDevice, ctx.stream));
+    if (int32_t rc = hs.walk(out_stats, nullptr, [&](uint32_t, uint32_t m) {
+            const uint32_t* d_bits = !f.bits ? nullptr : f.stride ? hs.in<uint32_t>(1) : hs.extra<uint32_t>(1);
+            return flat_range_run(idx, ctx.stream, plan, hs.extra<void>(0), hs.in(0), m, c, d_bits, f.stride,
+                                  out_cap ? hs.out<uint32_t>(0) : nullptr, out_cap ? hs.out<float>(1) : nullptr,
+                                  hs.out<uint32_t>(2), hs.stats());
+        }))
+        return rc;
+    for (uint32_t i = 0; out_cap && i < nq; ++i)
+        if (out_counts[i] > out_cap) return flat_range_overflowed(out_cap);
+    return DANN_OK;
 } DANN_CATCH_ALL
 
 // dann_search_record_batch / dann_search_record_queries: beam-1 searches that keep their visit records.  The queries are

@@ -12,58 +12,14 @@
 //   flat_merge_kernel  one workgroup per query merges its chunk lists in rounds of sort and cut, evaluates the
 //                      distances of the k rows that are left (a key folds -0.0 into +0.0; the result carries the
 //                      distance itself) and writes ids, distances and statistics
-#include "dann_device.h"
-#include "dann_internal.h"
-#include "flat_plan.h"
-#include "wave_lists.h"
+#include "flat_impl.h"
 
 namespace dann {
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kU = 4;  // rows per lane group and step
-constexpr uint64_t kNoKey = ~0ull;
-
-struct FlatArgs {
-    const void* queries;      // nq images of ix.qbytes
-    uint32_t nq;
-    uint32_t first, n, k;
-    uint32_t chunk_rows, nchunks;
-    uint32_t tile, cap, qslot;
-    uint32_t merge_cap;
-    const uint32_t* deleted;  // the deleted bitmap when it is to be honoured, else null
-    uint64_t* lists;          // [nq][nchunks][k] keys, ascending, kNoKey behind the last
-    uint32_t* chunk_cmps;     // [nchunks] rows evaluated (the same for every query)
-    uint32_t* out_ids;
-    float* out_dists;
-    dann_search_stats* stats;  // may be null
-};
-
-template <int DT, int OP>
-__device__ __forceinline__ void stage_query(const IndexView& ix, const void* queries, uint32_t qi, uint8_t* slot) {
-    using S = Scheme<DT, OP, false>;
-    using RT = typename RowType<DT>::type;
-    const uint8_t* qsrc = reinterpret_cast<const uint8_t*>(queries) + (uint64_t)qi * ix.qbytes;
-    uint8_t* qs = slot + query_stage_off(DT);
-    if constexpr (S::kInt) {
-        for (uint32_t i = threadIdx.x; i < ix.qbytes; i += blockDim.x) qs[i] = qsrc[i];
-    } else {
-        const RT* src = reinterpret_cast<const RT*>(qsrc);
-        for (uint32_t i = threadIdx.x; i < ix.dim; i += blockDim.x) reinterpret_cast<float*>(qs)[i] = load1(src + i);
-    }
-}
-
-// sorts keys[0, cap) (the first `fill` are set) and returns min(fill, k) through *count, the k-th key through *thr
-__device__ __forceinline__ void cut_to_k(uint64_t* keys, uint32_t cap, uint32_t fill, uint32_t k, uint32_t* count,
-                                         uint64_t* thr) {
-    for (uint32_t i = fill + threadIdx.x; i < cap; i += kFlatThreads) keys[i] = kNoKey;
-    __syncthreads();
-    block_bitonic(keys, cap, kFlatThreads);
-    if (threadIdx.x == 0) {
-        *count = fill < k ? fill : k;
-        *thr = fill < k ? kNoKey : keys[k - 1];
-    }
-}
+constexpr int kWave = kFlatWave;
+constexpr int kU = kFlatU;
+constexpr uint64_t kNoKey = kFlatNoKey;
 
 template <int DT, int OP, bool NORM>
 __global__ __launch_bounds__(kFlatThreads) void flat_scan_kernel(IndexView ix, FlatArgs a) {
@@ -87,7 +43,7 @@ __global__ __launch_bounds__(kFlatThreads) void flat_scan_kernel(IndexView ix, F
     const uint64_t hi = lo + a.chunk_rows < end ? lo + a.chunk_rows : end;
     const SqParams sqp{ix.sq_k, ix.sq_shift_norm_sq};
 
-    for (uint32_t t = 0; t < tq; ++t) stage_query<DT, OP>(ix, a.queries, q0 + t, qbase + (size_t)t * a.qslot);
+    for (uint32_t t = 0; t < tq; ++t) flat_stage_query<DT, OP>(ix, a.queries, q0 + t, qbase + (size_t)t * a.qslot);
     if (threadIdx.x < a.tile) {
         thr[threadIdx.x] = kNoKey;
         cnt[threadIdx.x] = 0;
@@ -136,7 +92,7 @@ __global__ __launch_bounds__(kFlatThreads) void flat_scan_kernel(IndexView ix, F
         __syncthreads();
         for (uint32_t t = 0; t < tq; ++t) {
             const uint32_t fill = cnt[t];  // (the same for the whole workgroup)
-            if (fill + kStep > a.cap) cut_to_k(bufs + (size_t)t * a.cap, a.cap, fill, a.k, &cnt[t], &thr[t]);
+            if (fill + kStep > a.cap) flat_cut_to_k(bufs + (size_t)t * a.cap, a.cap, fill, a.k, &cnt[t], &thr[t]);
         }
         __syncthreads();
     }
@@ -144,7 +100,7 @@ __global__ __launch_bounds__(kFlatThreads) void flat_scan_kernel(IndexView ix, F
     for (uint32_t t = 0; t < tq; ++t) {
         const uint32_t fill = cnt[t];
         uint64_t* keys = bufs + (size_t)t * a.cap;
-        cut_to_k(keys, a.cap, fill, a.k, &cnt[t], &thr[t]);
+        flat_cut_to_k(keys, a.cap, fill, a.k, &cnt[t], &thr[t]);
         uint64_t* out = a.lists + ((uint64_t)(q0 + t) * a.nchunks + chunk) * a.k;
         for (uint32_t i = threadIdx.x; i < a.k; i += kFlatThreads) out[i] = keys[i];  // (cap > k: pads are in place)
     }
@@ -156,7 +112,7 @@ __global__ __launch_bounds__(kFlatThreads) void flat_scan_kernel(IndexView ix, F
 }
 
 template <int DT, int OP, bool NORM>
-__global__ __launch_bounds__(kFlatThreads) void flat_merge_kernel(IndexView ix, FlatArgs a) {
+__global__ __launch_bounds__(kFlatThreads) void flat_merge_kernel(IndexView ix, FlatArgs a, uint32_t cmps_stride) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     using S = Scheme<DT, OP, false>;
     constexpr int G = S::G, GROUPS = kFlatThreads / G;
@@ -164,7 +120,7 @@ __global__ __launch_bounds__(kFlatThreads) void flat_merge_kernel(IndexView ix, 
     uint64_t* const keys = reinterpret_cast<uint64_t*>(smem);
     uint8_t* const qslot = smem + (size_t)a.merge_cap * 8;
     const uint32_t qi = blockIdx.x, k = a.k, P = a.merge_cap;
-    stage_query<DT, OP>(ix, a.queries, qi, qslot);
+    flat_stage_query<DT, OP>(ix, a.queries, qi, qslot);
     // keys[0, k): the best so far; keys[k, P): the next P - k keys of the query's lists
     const uint64_t* lists = a.lists + (uint64_t)qi * a.nchunks * k;
     const uint64_t total = (uint64_t)a.nchunks * k;
@@ -211,7 +167,7 @@ __global__ __launch_bounds__(kFlatThreads) void flat_merge_kernel(IndexView ix, 
     if (a.stats && threadIdx.x == 0) {
         for (uint32_t r = 0; r < k; ++r) written += keys[r] != kNoKey ? 1u : 0u;
         uint32_t cmps = 0;
-        for (uint32_t c = 0; c < a.nchunks; ++c) cmps += a.chunk_cmps[c];
+        for (uint32_t c = 0; c < a.nchunks; ++c) cmps += a.chunk_cmps[(uint64_t)qi * cmps_stride + c];
         dann_search_stats st;
         st.cmps = cmps;
         st.hops = 0;
@@ -275,10 +231,21 @@ int32_t launch_flat_search(const IndexView& ix, const FlatPlan& plan, const void
                                                                           dim3(kFlatThreads), plan.scan_lds, stream, ix, a);
         if (e != DANN_OK) return e;
         return launch_kernel<flat_merge_kernel<R::dt, R::op, R::norm>>("flat_merge_kernel launch", dim3(nq), dim3(kFlatThreads),
-                                                                       plan.merge_lds, stream, ix, a);
+                                                                       plan.merge_lds, stream, ix, a, 0u);
     });
     if (rc != kNoRow) return rc;
     set_error("dann_flat_search_batch: not defined on rows of dtype %d", ix.dtype);
+    return DANN_EUNSUPPORTED;
+}
+
+int32_t launch_flat_merge(const IndexView& ix, const FlatArgs& a, uint32_t cmps_stride, size_t merge_lds, hipStream_t stream) {
+    const int32_t rc = dispatch_row_op<kRowsQuery>(ix.dtype, ix.metric, [&](auto r) {
+        using R = decltype(r);
+        return launch_kernel<flat_merge_kernel<R::dt, R::op, R::norm>>("flat_merge_kernel launch", dim3(a.nq), dim3(kFlatThreads),
+                                                                       merge_lds, stream, ix, a, cmps_stride);
+    });
+    if (rc != kNoRow) return rc;
+    set_error("flat merge: not defined on rows of dtype %d", ix.dtype);
     return DANN_EUNSUPPORTED;
 }
 

@@ -356,11 +356,20 @@ class Provider:
               "dann_rerank_batch")
         return ids, d
 
-    # -- FlatIndex::knn_search ------------------------------------------------------
-    def flat_search(self, queries, k, first=0, n=None, skip_deleted=False, stats=False):
+    # -- FlatIndex::knn_search and the ground-truth scans ------------------------------
+    def _flat_filter(self, match, nq):
+        """dann_flat_filter of a bool array over slots (shared) or nq x nslots (per query); keep `bits` alive for the call"""
+        _, bits = self._filter(FILTER_INLINE, match, nq)
+        f = _ffi.FlatFilter()
+        f.bits = bits.ctypes.data
+        f.stride_words = 0 if bits.shape[0] == 1 else bits.shape[1]
+        return f, bits
+
+    def flat_search(self, queries, k, first=0, n=None, skip_deleted=False, stats=False, match=None):
         """Exhaustive k-NN over the slots [first, first + n) (n None: the rest of the capacity, start points not included):
-        the first k rows under (distance ascending, slot descending).  Returns (ids[nq, k], dists[nq, k]), with
-        stats=True also the SearchStats records; places behind the last result hold 0xFFFFFFFF / +inf."""
+        the first k rows under (distance ascending, slot descending).  match: a bool array over the slots [0, capacity +
+        start points), shared or one row per query -- only matching slots are evaluated.  Returns (ids[nq, k], dists[nq, k]),
+        with stats=True also the SearchStats records; places behind the last result hold 0xFFFFFFFF / +inf."""
         q = np.ascontiguousarray(queries, dtype=self.query_dtype).reshape(-1, self.query_elems)
         nq = q.shape[0]
         n = self.capacity - first if n is None else n
@@ -368,19 +377,75 @@ class Provider:
         dists = np.empty((nq, k), np.float32)
         st = np.zeros(nq, STATS_DTYPE)
         flags = _ffi.FLAT_SKIP_DELETED if skip_deleted else 0
-        check(_ffi.lib().dann_flat_search_batch(self._h, _p(q), nq, int(first), int(n), int(k), flags, _p(ids), _p(dists),
-                                                _p(st) if stats else None), "dann_flat_search_batch")
+        if match is None:
+            check(_ffi.lib().dann_flat_search_batch(self._h, _p(q), nq, int(first), int(n), int(k), flags, _p(ids), _p(dists),
+                                                    _p(st) if stats else None), "dann_flat_search_batch")
+        else:
+            f, keep = self._flat_filter(match, nq)
+            check(_ffi.lib().dann_flat_filtered_search_batch(self._h, _p(q), nq, int(first), int(n), int(k), flags, C.byref(f),
+                                                             _p(ids), _p(dists), _p(st) if stats else None),
+                  "dann_flat_filtered_search_batch")
+            del keep
         return (ids, dists, st) if stats else (ids, dists)
 
-    def flat_search_device(self, d_queries, nq, k, d_ids, d_dists, first=0, n=None, skip_deleted=False, d_stats=0):
+    def flat_search_device(self, d_queries, nq, k, d_ids, d_dists, first=0, n=None, skip_deleted=False, d_stats=0, d_bits=0,
+                           stride_words=0):
         """the same on device addresses (ints) of the index's device: nq query images, nq x k ids and distances, and
-        optionally nq SearchStats records; complete on return"""
+        optionally nq SearchStats records and the filter's bitmaps (d_bits, stride_words words apart, 0: one for all);
+        complete on return"""
         n = self.capacity - first if n is None else n
         flags = _ffi.FLAT_SKIP_DELETED if skip_deleted else 0
-        check(_ffi.lib().dann_flat_search_batch_device(self._h, C.c_void_p(int(d_queries)), int(nq), int(first), int(n), int(k),
-                                                       flags, C.c_void_p(int(d_ids)), C.c_void_p(int(d_dists)),
-                                                       C.c_void_p(int(d_stats)) if d_stats else None),
-              "dann_flat_search_batch_device")
+        args = (self._h, C.c_void_p(int(d_queries)), int(nq), int(first), int(n), int(k), flags)
+        outs = (C.c_void_p(int(d_ids)), C.c_void_p(int(d_dists)), C.c_void_p(int(d_stats)) if d_stats else None)
+        if not d_bits:
+            check(_ffi.lib().dann_flat_search_batch_device(*args, *outs), "dann_flat_search_batch_device")
+        else:
+            f = _ffi.FlatFilter(int(d_bits), int(stride_words))
+            check(_ffi.lib().dann_flat_filtered_search_batch_device(*args, C.byref(f), *outs),
+                  "dann_flat_filtered_search_batch_device")
+
+    def flat_range_search(self, queries, radius, inner_radius=None, match=None, first=0, n=None, skip_deleted=False,
+                          out_cap=None, stats=False):
+        """Exhaustive range scan over the slots [first, first + n): per query every evaluated row with
+        inner_radius < d <= radius, in ascending slot order.  Returns (ids[nq, out_cap], dists[nq, out_cap], counts[nq]),
+        with stats=True also the SearchStats records; counts are always the true numbers of matches.  out_cap None: n (every
+        result fits); out_cap=0 only counts (ids and dists come back with no columns).  A count above out_cap raises
+        DannError with status EOVERFLOW; `partial` of the exception holds what this method would have returned."""
+        q = np.ascontiguousarray(queries, dtype=self.query_dtype).reshape(-1, self.query_elems)
+        nq = q.shape[0]
+        n = self.capacity - first if n is None else n
+        cap = int(n if out_cap is None else out_cap)
+        ids = np.empty((nq, cap), np.uint32)
+        dists = np.empty((nq, cap), np.float32)
+        counts = np.zeros(nq, np.uint32)
+        st = np.zeros(nq, STATS_DTYPE)
+        flags = _ffi.FLAT_SKIP_DELETED if skip_deleted else 0
+        f, keep = self._flat_filter(match, nq) if match is not None else (None, None)
+        rc = _ffi.lib().dann_flat_range_search_batch(self._h, _p(q), nq, int(first), int(n), float(radius),
+                                                     int(inner_radius is not None), float(inner_radius or 0.0), flags,
+                                                     C.byref(f) if f is not None else None, cap, _p(ids) if cap else None,
+                                                     _p(dists) if cap else None, _p(counts), _p(st) if stats else None)
+        del keep
+        res = (ids, dists, counts, st) if stats else (ids, dists, counts)
+        try:
+            check(rc, "dann_flat_range_search_batch")
+        except DannError as e:
+            e.partial = res
+            raise
+        return res
+
+    def flat_range_search_device(self, d_queries, nq, radius, out_cap, d_ids, d_dists, d_counts, inner_radius=None, first=0,
+                                 n=None, skip_deleted=False, d_stats=0, d_bits=0, stride_words=0):
+        """the same on device addresses (ints): nq x out_cap ids and distances (may be 0 when out_cap is 0), nq counts,
+        optionally nq SearchStats records and the filter's bitmaps; complete on return"""
+        n = self.capacity - first if n is None else n
+        flags = _ffi.FLAT_SKIP_DELETED if skip_deleted else 0
+        f = _ffi.FlatFilter(int(d_bits), int(stride_words)) if d_bits else None
+        vp = lambda a: C.c_void_p(int(a)) if a else None  # noqa: E731
+        check(_ffi.lib().dann_flat_range_search_batch_device(
+            self._h, vp(d_queries), int(nq), int(first), int(n), float(radius), int(inner_radius is not None),
+            float(inner_radius or 0.0), flags, C.byref(f) if f is not None else None, int(out_cap), vp(d_ids), vp(d_dists),
+            vp(d_counts), vp(d_stats)), "dann_flat_range_search_batch_device")
 
     def search_record(self, slots, l_value, rec_stride=None):
         s = np.ascontiguousarray(slots, dtype=np.uint32)

@@ -359,6 +359,52 @@ int32_t dann_flat_search_batch(dann_index* idx, const void* queries, uint32_t nq
 int32_t dann_flat_search_batch_device(dann_index* idx, const void* d_queries, uint32_t nq, uint32_t first_slot, uint32_t n,
                                       uint32_t k, uint32_t flags, uint32_t* d_out_ids, float* d_out_dists,
                                       dann_search_stats* d_out_stats);
+/* Exhaustive scans that tell whether a filtered or a range search is right: the reference's ground-truth tools
+ * (diskann-tools/src/utils/ground_truth.rs) over the slots [first_slot, first_slot + n), with the distances, row types,
+ * query images, flags and range rules of dann_flat_search_batch.
+ * The filter is a bitmap over slot ids as dann_filter defines it -- is_match(i) = bit (i & 31) of bits[i >> 5] for i in
+ * [0, capacity + num_start_points) -- one for all queries (stride_words == 0) or one per query, stride_words words apart
+ * (a non-zero stride below ceil((capacity + num_start_points) / 32) is DANN_EINVAL).  A null filter or null bits: every
+ * slot matches.  Bits at or beyond capacity + num_start_points in the last word are ignored.
+ * A row is evaluated for query q iff it lies in the range, its tag is readable (inline_tags), it is not marked deleted
+ * (DANN_FLAT_SKIP_DELETED) and q's filter holds its slot; out_stats[q].cmps counts those rows, hops is 0.  A row that no
+ * query of a tile of queries accepts is not fetched at all.
+ *
+ * dann_flat_filtered_search_batch: compute_ground_truth_from_data with query_bitmaps (:589-693).  The queue of
+ * FlatIndex::knn_search is fed the evaluated rows only, in ascending slot order; outputs, padding and stats as
+ * dann_flat_search_batch, to which a call with an all-ones filter is equal in every output.
+ *
+ * dann_flat_range_search_batch: compute_range_ground_truth_from_data (:285-353).  The result of a query is every evaluated
+ * row whose distance d passes the predicate of range_search.rs:326-335 -- d <= radius, and !(d <= inner_radius) when
+ * has_inner_radius -- in ascending slot order, with the distance as computed (a NaN distance fails; -0.0 stays -0.0).
+ * out_counts[q] is always the true number of matches; out_ids / out_dists (nq x out_cap) take the first out_cap of them,
+ * 0xFFFFFFFF / +infinity behind.  out_stats (optional): result_count = the true count, written = min(count, out_cap).
+ * If a count exceeds out_cap the call returns DANN_EOVERFLOW and out_stats[q].status is non-zero for those queries; the
+ * counts and every other query's results are valid, and a second call with out_cap = max(out_counts) holds everything.
+ * out_cap == 0 only counts: out_ids / out_dists may be NULL, the call returns DANN_OK.
+ * Errors as dann_flat_search_batch; also DANN_EINVAL for a NaN radius or inner_radius > radius.
+ * The results do not depend on how the scan is cut up, nor on the run. */
+typedef struct {
+    const uint32_t* bits;   /* host memory; device memory in the _device forms */
+    uint64_t stride_words;  /* words between the bitmaps of consecutive queries; 0 = one bitmap for all queries */
+} dann_flat_filter;
+int32_t dann_flat_filtered_search_batch(dann_index* idx, const void* queries, uint32_t nq, uint32_t first_slot, uint32_t n,
+                                        uint32_t k, uint32_t flags, const dann_flat_filter* filter, uint32_t* out_ids,
+                                        float* out_dists, dann_search_stats* out_stats);
+int32_t dann_flat_range_search_batch(dann_index* idx, const void* queries, uint32_t nq, uint32_t first_slot, uint32_t n,
+                                     float radius, int32_t has_inner_radius, float inner_radius, uint32_t flags,
+                                     const dann_flat_filter* filter, uint32_t out_cap, uint32_t* out_ids, float* out_dists,
+                                     uint32_t* out_counts, dann_search_stats* out_stats);
+/* device-pointer forms (queries, bitmaps and outputs on the index's device, the dann_flat_filter itself in host memory;
+ * complete on return) */
+int32_t dann_flat_filtered_search_batch_device(dann_index* idx, const void* d_queries, uint32_t nq, uint32_t first_slot,
+                                               uint32_t n, uint32_t k, uint32_t flags, const dann_flat_filter* d_filter,
+                                               uint32_t* d_out_ids, float* d_out_dists, dann_search_stats* d_out_stats);
+int32_t dann_flat_range_search_batch_device(dann_index* idx, const void* d_queries, uint32_t nq, uint32_t first_slot,
+                                            uint32_t n, float radius, int32_t has_inner_radius, float inner_radius,
+                                            uint32_t flags, const dann_flat_filter* d_filter, uint32_t out_cap,
+                                            uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
+                                            dann_search_stats* d_out_stats);
 /* insert-time search: also returns the VisitedSearchRecord (record.rs:86-93) per query:
  * rec_ids/rec_dists: nq x rec_stride, rec_n: nq */
 int32_t dann_search_record_batch(dann_index* idx, const uint32_t* slots, uint32_t nq, uint32_t l_value,
