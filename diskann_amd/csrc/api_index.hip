@@ -248,6 +248,8 @@ int32_t dann_index_create(const dann_config* cfg, const void* start_rows, uint64
         return DANN_EINVAL;
     }
     for (auto& d : idx->dbg) d.store(__builtin_nan(""), std::memory_order_relaxed);
+    // (beam_search_plain forms a row's address with 32 bits of the stride: a wider field needs a range check here)
+    static_assert(sizeof(idx->cfg.row_stride) == 4, "row strides are below 4 GiB");
     if (idx->cfg.row_stride == 0) idx->cfg.row_stride = (lb + 15u) & ~15u;
     if (idx->cfg.row_stride < lb || (idx->cfg.row_stride & 15u)) {
         set_error("row_stride %u must be >= %u and a multiple of 16", idx->cfg.row_stride, lb);

@@ -353,6 +353,56 @@ __device__ __forceinline__ void group_distance_pre(const F4 (&xs)[DIM / (8 * NAC
 }
 
 
+// finish_vec<4> without a partial block, for group_distance_passes: the same adds, in the same order and with the same
+// left and right operands.  What differs is the instruction they become.  Left to itself the compiler packs these adds
+// in pairs (v_pk_add_f32), a packed add takes no DPP operand, and every shuffled operand then costs a v_mov_b32_dpp of
+// its own: 20 instructions a row.  `lone` hands a sum to the compiler as a value it knows nothing about, so the adds
+// stay single, each takes its DPP operand itself (v_add_f32_dpp), and a row costs 15.  An IEEE add gives the same bits
+// packed or not.
+__device__ __forceinline__ float lone(float x) {
+    asm("" : "+v"(x));
+    return x;
+}
+__device__ __forceinline__ float finish_vec4_dpp(float (&a)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a[i] = lone(a[i] + dpp_f<DPP_XOR2>(a[i]));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a[i] = lone(a[i] + dpp_f<DPP_SHL4>(a[i]));
+    const float q0 = lone(a[0] + dpp_f<DPP_XOR1>(a[0]));
+    const float q1 = lone(a[1] + dpp_f<DPP_XOR1>(a[1]));
+    const float q2 = lone(a[2] + dpp_f<DPP_XOR1>(a[2]));
+    const float q3 = lone(a[3] + dpp_f<DPP_XOR1>(a[3]));
+    return lone(q0 + q2) + lone(q1 + q3);
+}
+
+// group_distance_pre for NP passes of the plain float hop's gather (search_plain_impl.h), NACC = 4, L2 or inner product:
+// all NP * NT row loads are issued before the first FMA, then the NP distances are computed with finish_vec4_dpp.  The
+// arithmetic, its order and the results are group_distance_pre's.
+template <int OP, int DIM, int NP, typename RT>
+__device__ __forceinline__ void group_distance_passes(const F4 (&xs)[DIM / 32], const RT* const (&rows)[NP], int v,
+                                                      float (&out)[NP]) {
+    static_assert(OP != OP_COS, "one accumulator set per row");
+    constexpr int TRIP = 32, NT = DIM / TRIP;
+    Raw4<RT> ys[NP][NT];
+#pragma unroll
+    for (int u = 0; u < NP; ++u) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) ys[u][t].load(rows[u] + t * TRIP + 4 * v);  // unconditional, as group_distance_pre's
+    }
+    // (nothing moves across this line: with the rows' addresses formed inside the body the scheduler otherwise starts on
+    // the first row's arithmetic, and so waits for its loads, before it has issued the next row's)
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < NP; ++u) {
+        FAcc<OP> acc;
+        acc.init();
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc.step(xs[t], ys[u][t].get());
+        out[u] = finish_vec4_dpp(acc.s);
+    }
+}
+
+
 // U rows at once with run-time length: per trip the U row loads are issued together, so a lane
 // keeps U (x unroll) requests in flight instead of one.  Same arithmetic as group_distance_raw.
 template <int NACC, int OP, int U, typename QT, typename RT>

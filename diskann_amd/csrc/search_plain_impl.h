@@ -51,6 +51,7 @@ __device__ __forceinline__ void beam_search_plain(const SearchArgs& a, const uin
     using S = Scheme<DT, OP, false>;
     constexpr int G = S::G, GROUPS = kWave / G, U = kGatherRows, NTQ = DIM / (4 * G);
     static_assert(GROUPS * U * 2 == kWave, "a hop's candidates take at most two gather trips");
+    static_assert(U == 4, "the gather has a body for each of 1 .. 4 passes");
     using RT = typename RowType<DT>::type;
 
     const IndexView& ix = a.ix;
@@ -82,7 +83,7 @@ __device__ __forceinline__ void beam_search_plain(const SearchArgs& a, const uin
     // ---- what the hop reads, in locals ----------------------------------------------------------------------------------
     const uint8_t* const rows_base = ix.rows;
     const uint32_t* const adj_base = ix.adj;
-    const uint64_t row_stride = ix.row_stride;
+    const uint32_t row_stride = (uint32_t)ix.row_stride;  // (below 4 GiB: dann_index_create) -- a row's address is one multiply-add
     const uint32_t adj_stride = ix.adj_stride, R = ix.max_degree, nslots = ix.nslots;
     const uint32_t qcap = a.l_value + ix.nstart;
     const uint32_t ht_mod = a.ht_prime, ht_open = a.ht_open;
@@ -111,26 +112,45 @@ __device__ __forceinline__ void beam_search_plain(const SearchArgs& a, const uin
         val = prow[1u + (lane < R ? lane : R - 1u)];
     };
 
-    // distance of every candidate in cand_id[0..nc) -> cand_d: 32 rows per trip, at most two trips
+    // distance of every candidate in cand_id[0..nc) -> cand_d: at most two trips of up to U passes, a pass being the
+    // GROUPS rows the wave's groups take together.  A trip runs the passes that hold a candidate and no others: a hop
+    // has 17.5 candidates on average for the trip's 32 slots.  One straight body per pass count, chosen by a
+    // wave-uniform switch: each issues all its row loads before the first FMA (passes behind an `if` of their own
+    // would wait for their loads one by one -- vmcnt is not counted across a branch).  Inside the last pass a slot
+    // without a candidate reads row 0 and stores to the sink.
+    auto passes = [&](uint32_t c0, uint32_t nc, auto np_tag) {
+        constexpr int NP = decltype(np_tag)::value;
+        const RT* rows[NP];
+        bool act[NP];
+        float out[NP];
+#pragma unroll
+        for (int u = 0; u < NP; ++u) {
+            const uint32_t c = c0 + u * GROUPS + g;  // (< 64: inside the candidate block whatever nc)
+            const uint32_t idv = cand_id[c];
+            act[u] = c < nc;
+            const uint32_t id = act[u] ? idv : 0u;
+            rows[u] = reinterpret_cast<const RT*>(rows_base + (uint64_t)id * row_stride);
+        }
+        group_distance_passes<OP, DIM, NP>(xq, rows, v, out);
+#pragma unroll
+        for (int u = 0; u < NP; ++u) {
+            const uint32_t c = c0 + u * GROUPS + g;
+            float* const dst = (act[u] & (v == 0)) ? cand_d + c : reinterpret_cast<float*>(sink);
+            *dst = post_op<OP, NORM>(out[u]);
+        }
+    };
     auto gather = [&](uint32_t nc) {
         for (uint32_t c0 = 0; c0 < nc; c0 += GROUPS * U) {
-            const RT* rows[U];
-            bool act[U];
-            float out[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const uint32_t c = c0 + u * GROUPS + g;  // (< 64: inside the candidate block whatever nc)
-                const uint32_t idv = cand_id[c];
-                act[u] = c < nc;
-                const uint32_t id = act[u] ? idv : 0u;
-                rows[u] = reinterpret_cast<const RT*>(rows_base + (uint64_t)id * row_stride);
-            }
-            group_distance_pre<S::NACC, OP, DIM, U>(xq, rows, act, v, out);
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const uint32_t c = c0 + u * GROUPS + g;
-                float* const dst = (act[u] & (v == 0)) ? cand_d + c : reinterpret_cast<float*>(sink);
-                *dst = post_op<OP, NORM>(out[u]);
+            const uint32_t left = nc - c0;
+            const uint32_t np = left < (uint32_t)(GROUPS * U) ? (left + GROUPS - 1u) / GROUPS : (uint32_t)U;
+#ifdef DANN_PHASE_CYCLES
+            ph_acc[10 + np] += 1;  // trips by pass count: slots 11 .. 14
+#endif
+            switch (np) {
+                case 1: passes(c0, nc, std::integral_constant<int, 1>{}); break;
+                case 2: passes(c0, nc, std::integral_constant<int, 2>{}); break;
+                case 3: passes(c0, nc, std::integral_constant<int, 3>{}); break;
+                default: passes(c0, nc, std::integral_constant<int, 4>{}); break;
             }
         }
     };
