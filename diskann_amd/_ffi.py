@@ -26,6 +26,7 @@ MAXSIM_KERNEL, MAXSIM_REFERENCE = 0, 1  # the two orders of dann_maxsim_batch / 
 BUILD_MFMA_BACKEDGE, BUILD_MFMA_POOL, BUILD_ROW_KERNEL_ONLY = 1, 2, 4
 CONSOLIDATE_COMPLETE, CONSOLIDATE_DELETED = 0, 1  # ConsolidateKind (dann_consolidate out_kind)
 CONSOLIDATE_DROP_DELETED = 1  # dann_consolidate flag
+DEGREE_SKIP_DELETED = 1  # dann_degree_stats flag
 FLAT_SKIP_DELETED = 1  # dann_flat_search_batch flag
 INPLACE_VISITED_AND_TOPK, INPLACE_TWO_HOP_AND_ONE_HOP, INPLACE_ONE_HOP = 0, 1, 2  # dann_inplace_delete_params.method
 INPLACE_COUNTERS = 9
@@ -71,6 +72,12 @@ class Diverse(C.Structure):
 class InplaceDeleteParams(C.Structure):
     """dann_inplace_delete_params: graph::InplaceDeleteMethod + num_to_replace"""
     _fields_ = [("method", C.c_uint32), ("k_value", C.c_uint32), ("l_value", C.c_uint32), ("num_to_replace", C.c_uint32)]
+
+
+class DegreeStats(C.Structure):
+    """dann_degree_summary == DegreeStats (index.rs:2191-2239) + the exact totals behind avg_degree"""
+    _fields_ = [("max_degree", C.c_uint32), ("avg_degree", C.c_float), ("min_degree", C.c_uint32), ("reserved", C.c_uint32),
+                ("cnt_less_than_two", C.c_uint64), ("points", C.c_uint64), ("total", C.c_uint64)]
 
 
 NO_ATTRIBUTE = 0xFFFFFFFF  # DANN_NO_ATTRIBUTE: AttributeValueProvider::get returns None
@@ -196,6 +203,9 @@ SYMBOLS = {
     "dann_consolidate": (_i32, [_vp, _P(BuildConfig), _vp, _u32, _u32, _vp, _vp]),
     "dann_inplace_delete": (_i32, [_vp, _P(BuildConfig), _vp, _u32, _P(InplaceDeleteParams), _vp]),
     "dann_drop_deleted_neighbors": (_i32, [_vp, _P(BuildConfig), _vp, _u32, _u32, _vp]),
+    "dann_prune_range": (_i32, [_vp, _P(BuildConfig), _vp, _u32, _u32, _vp]),
+    "dann_count_reachable": (_i32, [_vp, _vp, _u32, _P(_u64), _P(_u32), _vp]),
+    "dann_degree_stats": (_i32, [_vp, _vp, _u32, _u32, _P(DegreeStats)]),
     "dann_debug_gram_tiles": (_i32, [_i32, _i32, _vp, _u32, _u32, _u32, _vp, _vp]),
     "dann_save_graph": (_i32, [_vp, C.c_char_p]),
     "dann_load_graph": (_i32, [_vp, C.c_char_p, _P(_u32), _P(_u64), _P(_u64)]),
@@ -210,6 +220,8 @@ SYMBOLS = {
     "dann_sq8_compress": (_i32, [_i32, _vp, _u32, _u32, _vp, _f32, _vp]),
     "dann_sq_compress": (_i32, [_i32, _i32, _vp, _u32, _u32, _vp, _f32, _vp]),
     "dann_minmax_compress": (_i32, [_i32, _i32, _vp, _u32, _u32, _f32, _vp, _vp]),
+    "dann_medoid": (_i32, [_i32, _i32, _vp, _u64, _u32, _u64, _P(C.c_int64), _vp, _vp]),
+    "dann_medoid_device": (_i32, [_i32, _i32, _vp, _u64, _u32, _u64, _P(C.c_int64), _vp, _vp]),
     "dann_transform_create": (_i32, [_i32, _P(TransformParts), _P(_vp)]),
     "dann_transform_destroy": (_i32, [_vp]),
     "dann_transform_input_dim": (_i32, [_vp]),
@@ -273,6 +285,7 @@ SYMBOLS = {
     "dann_debug_sched_pivots": (_i32, [_vp, _vp, _u32, _P(_u32), _P(_u32), _P(_f32)]),
     "dann_debug_family_name": (C.c_char_p, [_i32]),
     "dann_debug_pq_rolling_sum_stats": (_i32, [_i32, _P(_u64), _i32]),
+    "dann_debug_medoid_times": (_i32, [_i32, _i32, _vp, _u64, _u32, _u64, _P(C.c_int64), _vp, _P(C.c_double)]),
     "dann_debug_mvset_kernel_time": (_i32, [_vp, _i32, _P(C.c_double), _P(_u64)]),
 }
 

@@ -23,6 +23,8 @@
 //                        (<= 4096), so an exact selection of those by (distance, pool position), handed on in pool order,
 //                        leaves the prune the same sorted list;
 //   prune_pools_into_rows (build_kernels.hip) the back-edge prune pipeline: row kernel, or sort + Gram tiles + sweep.
+// dann_prune_range (graph_stats.hip; DiskANNIndex::prune_range, index.rs:2656-2701) is the same pass (run_list_prunes)
+// with no deleted state: lists longer than pruned_degree are queued and always go through robust_prune_list.
 // The worklists are processed in chunks, so the pool buffers and the Gram scratch stay bounded for any index size.
 #include <hip/hip_runtime.h>
 
@@ -67,13 +69,17 @@ __global__ void drop_deleted_kernel(IndexView ix, const uint32_t* bm) {
 struct ConsScanArgs {
     IndexView ix;
     const uint32_t* bm;     // deleted bitmap, null = nothing deleted
-    const uint32_t* ids;    // null = item i is slot i
+    const uint32_t* ids;    // null = item i is slot first + i
+    uint32_t first;
     uint32_t n;
+    uint32_t count_scanned; // dann_prune_range: counts[7] is wanted
+    uint32_t check_tags;    // dann_prune_range on an inline-tags index: a vertex whose own slot is unreadable is left alone
     uint32_t* claim;        // explicit ids: bitmap of the vertices already claimed (the first occurrence works), else null
     uint32_t pruned_degree;
     uint8_t* kinds;         // n: ConsolidateKind
     uint32_t* work[3];      // short (bound <= kShortPool), long (<= kMaxPool), huge worklists (gathered in global memory)
-    uint32_t* counts;       // [0..2] entries of each worklist, [3..5] the largest bound in each
+    uint32_t* counts;       // [0..2] entries of each worklist, [3..5] the largest bound in each, [7] vertices scanned (a
+                            // repeated id once), [8] vertices left alone because their slot is unreadable
 };
 
 // Four vertices per wavefront, 16 lanes each.  A vertex is queued when it may change: it has a deleted neighbour, or its
@@ -82,7 +88,7 @@ __global__ __launch_bounds__(64) void cons_scan_kernel(ConsScanArgs a) {
     const uint32_t lane = threadIdx.x, sub = lane >> 4, sl = lane & 15u;
     const uint32_t item = blockIdx.x * 4u + sub;
     const bool have = item < a.n;
-    const uint32_t v = have ? (a.ids ? a.ids[item] : item) : 0u;
+    const uint32_t v = have ? (a.ids ? a.ids[item] : a.first + item) : 0u;
     const bool del = have && in_bitmap(a.bm, v, a.ix.nslots);
     int first = 1;
     if (have && !del && a.claim && sl == 0) {
@@ -92,6 +98,10 @@ __global__ __launch_bounds__(64) void cons_scan_kernel(ConsScanArgs a) {
     first = __shfl(first, (int)(lane & 48u));
     if (have && sl == 0) a.kinds[item] = del ? (uint8_t)DANN_CONSOLIDATE_DELETED : (uint8_t)DANN_CONSOLIDATE_COMPLETE;
     const bool scan = have && !del && first;
+    if (a.count_scanned) {
+        const uint64_t sm = ballot64(have && first && sl == 0);
+        if (lane == 0 && sm) atomicAdd(&a.counts[7], (uint32_t)__popcll(sm));
+    }
     const uint32_t* arow = a.ix.adj + (uint64_t)v * a.ix.adj_stride;
     const uint32_t len = scan ? min(arow[0], a.ix.max_degree) : 0u;
     uint32_t ndel = 0, bound = 0;
@@ -108,7 +118,13 @@ __global__ __launch_bounds__(64) void cons_scan_kernel(ConsScanArgs a) {
         ndel += (uint32_t)__shfl_xor((int)ndel, o);
         bound += (uint32_t)__shfl_xor((int)bound, o);
     }
-    const bool want = scan && (ndel != 0u || len > a.pruned_degree);
+    bool want = scan && (ndel != 0u || len > a.pruned_degree);
+    if (a.check_tags) {  // (the reference reads the list first: a short list is passed over before any row is fetched)
+        const bool unreadable = want && a.ix.rows[(uint64_t)v * a.ix.row_stride + a.ix.tag_off] < kTagReadable;
+        const uint64_t um = ballot64(unreadable && sl == 0);
+        if (lane == 0 && um) atomicAdd(&a.counts[8], (uint32_t)__popcll(um));
+        want = want && !unreadable;
+    }
     const uint32_t cls = bound <= kShortPool ? 0u : bound <= kMaxPool ? 1u : 2u;
     for (uint32_t c = 0; c < 3; ++c) {
         wave_push(want && cls == c && sl == 0, a.work[c], &a.counts[c], item);
@@ -121,8 +137,11 @@ struct ConsGatherArgs {
     IndexView ix;
     const uint32_t* bm;
     const uint32_t* ids;
+    uint32_t first;
     const uint32_t* work;   // worklist of items; this launch: work[lo .. lo + m)
     uint32_t lo;
+    uint32_t prune_always;  // dann_prune_range: every queued list goes through robust_prune_list, whatever its pool's size,
+                            // and (inline tags) neighbours whose slot is unreadable stay out of the pool
     uint32_t pruned_degree;
     uint32_t pcap;          // pool capacity and stride of the chunk buffers (>= every pool bound of the worklist)
     uint32_t in_global;     // 1: pool and hash set in global memory (pool_ids / hash), else in LDS
@@ -132,7 +151,8 @@ struct ConsGatherArgs {
     float* pool_d;
     uint32_t* counts;
     unsigned long long* stats;  // kStatLines x kStatWords
-    uint32_t* err;          // set when a pool outgrows its bound (a bug, never an input)
+    uint32_t* err;          // bit 0: a pool outgrew its bound (a bug, never an input); bit 1 (prune_always): a list holds
+                            // a neighbour id past the last slot
 };
 
 template <int DT, int OP, bool NORM>
@@ -148,13 +168,14 @@ __global__ __launch_bounds__(kWave) void cons_gather_kernel(ConsGatherArgs a) {
     for (uint32_t i = lane; i <= hmask; i += kWave) hash[i] = kEmpty;
     __syncthreads();
     const uint32_t item = a.work[a.lo + wi];
-    const uint32_t v = a.ids ? a.ids[item] : item;
+    const uint32_t v = a.ids ? a.ids[item] : a.first + item;
     const uint32_t nslots = a.ix.nslots, R = a.ix.max_degree;
+    const bool skip_unreadable = a.prune_always && a.ix.tag_off;
     uint32_t* arow = a.ix.adj + (uint64_t)v * a.ix.adj_stride;
     const uint32_t len = min(arow[0], R);
     // on_neighbors(vertex): the live neighbours into the pool, the deleted ones into dl
     uint32_t cnt = 0, ndel = 0;
-    bool self_in_list = false;
+    bool self_in_list = false, bad_id = false;
     for (uint32_t e0 = 0; e0 < len; e0 += kWave) {
         const uint32_t e = e0 + lane;
         const uint32_t id = e < len ? arow[1 + e] : kEmpty;
@@ -163,12 +184,26 @@ __global__ __launch_bounds__(kWave) void cons_gather_kernel(ConsGatherArgs a) {
         if (del) dl[ndel + mbcnt(dm)] = id;
         ndel += (uint32_t)__popcll(dm);
         self_in_list |= ballot64(e < len && id == v) != 0ull;
-        cnt = append_unique(pool, hash, hmask, cnt, a.pcap, (e < len && !del && id != v) ? id : kEmpty, a.err);
+        bool take = e < len && !del && id != v;
+        if (a.prune_always) {  // (dann_set_neighbors admits an id past the last slot: its row must not be read)
+            const bool bad = take && id >= nslots;
+            bad_id |= ballot64(bad) != 0ull;
+            take = take && !bad;
+        }
+        if (skip_unreadable && take) take = a.ix.rows[(uint64_t)id * a.ix.row_stride + a.ix.tag_off] >= kTagReadable;
+        cnt = append_unique(pool, hash, hmask, cnt, a.pcap, take ? id : kEmpty, a.err);
     }
     __syncthreads();  // dl is read by every lane below
+    if (bad_id) {  // the list is left as it is, and the call answers DANN_EBOUNDS
+        if (lane == 0) {
+            atomicOr(a.err, 2u);
+            a.counts[wi] = 0;
+        }
+        return;
+    }
     unsigned long long* st = a.stats + (size_t)(blockIdx.x & (kStatLines - 1u)) * kStatWords;
     // nothing deleted and no prune required (index.rs:1858-1864: the pool still holds the vertex itself if it is listed)
-    if (ndel == 0 && cnt + (self_in_list ? 1u : 0u) <= a.pruned_degree) {
+    if (!a.prune_always && ndel == 0 && cnt + (self_in_list ? 1u : 0u) <= a.pruned_degree) {
         if (lane == 0) a.counts[wi] = 0;
         return;
     }
@@ -185,8 +220,8 @@ __global__ __launch_bounds__(kWave) void cons_gather_kernel(ConsGatherArgs a) {
         }
     }
     __syncthreads();  // the pool's ids, written by every lane, are read by all of them below
-    if (lane == 0) atomicMax(&st[2], (unsigned long long)cnt);
-    if (cnt < a.pruned_degree) {  // the pool is the new list (set_neighbors)
+    if (lane == 0) atomicMax(&st[2], (unsigned long long)(a.prune_always ? len : cnt));
+    if (a.prune_always ? cnt == 0u : cnt < a.pruned_degree) {  // the pool is the new list (set_neighbors)
         for (uint32_t i = lane; i < cnt; i += kWave) arow[1 + i] = pool[i];
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane == 0) {
@@ -295,6 +330,179 @@ int32_t ensure_deleted_bitmap(dann_index* idx) {
 
 using namespace dann;
 
+namespace dann {
+int32_t run_list_prunes(dann_index* idx, const dann_build_config* cfg, ListPrunePass& pass) {
+    const uint32_t* ids = pass.ids;
+    const uint32_t n = pass.n;
+    int32_t* out_kind = pass.out_kind;
+    const uint32_t* bm = pass.prune_range ? nullptr : idx->d_deleted;
+    hipStream_t st = idx->main.stream;
+    const IndexView ix = idx->view();
+    uint64_t bc0[11] = {};
+    if (pass.want_counters) {
+        if (int32_t rc = dann_build_counters(idx, bc0, 11)) return rc;
+    }
+    // per-call scratch: ids + claim bitmap, kinds, the two worklists, counts, striped stats, error word
+    const size_t claim_words = ids ? (idx->nslots + 31u) / 32u : 0u;
+    DevBuf d_ids, d_claim, d_kinds, d_work, d_meta, d_stats;
+    if (ids) {
+        DANN_HIP(d_ids.alloc((size_t)n * 4));
+        DANN_HIP(hipMemcpyAsync(d_ids.p, ids, (size_t)n * 4, hipMemcpyHostToDevice, st));
+        DANN_HIP(d_claim.alloc(claim_words * 4));
+        DANN_HIP(hipMemsetAsync(d_claim.p, 0, claim_words * 4, st));
+    }
+    DANN_HIP(d_kinds.alloc(n));
+    DANN_HIP(d_work.alloc((size_t)n * 12));
+    DANN_HIP(d_meta.alloc(64));
+    DANN_HIP(hipMemsetAsync(d_meta.p, 0, 64, st));
+    const size_t stats_bytes = (size_t)kStatLines * kStatWords * 8;
+    DANN_HIP(d_stats.alloc(stats_bytes));
+    DANN_HIP(hipMemsetAsync(d_stats.p, 0, stats_bytes, st));
+    uint32_t* meta = d_meta.as<uint32_t>();  // [0..5] scan counts, [6] error word, [7] scanned, [8] unreadable
+    uint32_t* work = d_work.as<uint32_t>();
+
+    ConsScanArgs sa;
+    sa.ix = ix;
+    sa.bm = bm;
+    sa.ids = ids ? d_ids.as<uint32_t>() : nullptr;
+    sa.first = pass.first;
+    sa.n = n;
+    sa.count_scanned = pass.prune_range ? 1u : 0u;
+    sa.check_tags = pass.prune_range && ix.tag_off ? 1u : 0u;
+    sa.claim = ids ? d_claim.as<uint32_t>() : nullptr;
+    sa.pruned_degree = cfg->pruned_degree;
+    sa.kinds = d_kinds.as<uint8_t>();
+    for (int c = 0; c < 3; ++c) sa.work[c] = work + (size_t)c * n;
+    sa.counts = meta;
+    hipLaunchKernelGGL(cons_scan_kernel, dim3((n + 3u) / 4u), dim3(64), 0, st, sa);
+    DANN_HIP(hipGetLastError());
+    uint32_t h_counts[9] = {};
+    DANN_HIP(hipMemcpyAsync(h_counts, meta, 36, hipMemcpyDeviceToHost, st));
+    DANN_HIP(hipStreamSynchronize(st));
+
+    // the matrix-core path keeps a Gram block per item in the index's build scratch: chunks of it stay at the build's
+    // batch scale
+    const uint32_t max_chunk = prune_pools_use_gram(idx) ? 2048u : 8192u;
+    DevBuf c_locs, c_ids, c_d, c_cnt, c_hash, c_keys, c_sel_ids, c_sel_d, c_sel_cnt;
+    size_t c_elems = 0, c_items = 0;
+    for (int cls = 0; cls < 3; ++cls) {
+        const uint32_t nwork = h_counts[cls];
+        if (nwork == 0) continue;
+        const bool huge = cls == 2;
+        const uint32_t pcap = pow2_at_least(h_counts[3 + cls]);
+        const uint32_t chunk =
+            std::min<uint32_t>(nwork, std::max<uint32_t>(huge ? 16u : 256u, std::min<uint32_t>(max_chunk, kChunkElems / pcap)));
+        if ((size_t)chunk * pcap > c_elems || chunk > c_items) {
+            // (earlier classes' buffers serve a later one when large enough; hipFree waits for the work queued on them)
+            c_elems = std::max<size_t>(c_elems, (size_t)chunk * pcap);
+            DANN_HIP(c_ids.alloc(c_elems * 4));
+            DANN_HIP(c_d.alloc(c_elems * 4));
+            if (chunk > c_items) {
+                c_items = chunk;
+                DANN_HIP(c_locs.alloc(c_items * 4));
+                DANN_HIP(c_cnt.alloc(c_items * 4));
+                DANN_HIP(hipMemsetAsync(c_locs.p, 0, c_items * 4, st));
+            }
+        }
+        if (huge) {  // global pools: hash sets, sort keys and the selected heads (stride kMaxPool)
+            DANN_HIP(c_hash.alloc((size_t)chunk * pcap * 8));
+            DANN_HIP(c_keys.alloc((size_t)chunk * pcap * 8));
+            DANN_HIP(c_sel_ids.alloc((size_t)chunk * kMaxPool * 4));
+            DANN_HIP(c_sel_d.alloc((size_t)chunk * kMaxPool * 4));
+            DANN_HIP(c_sel_cnt.alloc((size_t)chunk * 4));
+        }
+        ConsGatherArgs ga;
+        ga.ix = ix;
+        ga.bm = bm;
+        ga.ids = sa.ids;
+        ga.first = pass.first;
+        ga.prune_always = pass.prune_range ? 1u : 0u;
+        ga.work = sa.work[cls];
+        ga.pruned_degree = cfg->pruned_degree;
+        ga.pcap = pcap;
+        ga.in_global = huge ? 1u : 0u;
+        ga.hash = huge ? c_hash.as<uint32_t>() : nullptr;
+        ga.locs = c_locs.as<uint32_t>();
+        ga.pool_ids = c_ids.as<uint32_t>();
+        ga.pool_d = c_d.as<float>();
+        ga.counts = c_cnt.as<uint32_t>();
+        ga.stats = d_stats.as<unsigned long long>();
+        ga.err = meta + 6;
+        const size_t lds = (size_t)(ix.max_degree + (huge ? 0u : 3u * pcap)) * 4u;
+        ConsSelectArgs sel;
+        sel.in_ids = ga.pool_ids;
+        sel.in_d = ga.pool_d;
+        sel.in_cnt = ga.counts;
+        sel.in_stride = pcap;
+        sel.keys = c_keys.as<uint64_t>();
+        sel.keep = cfg->max_occlusion_size ? cfg->max_occlusion_size : 750u;
+        sel.tie_rust = idx->prune_tie_order == DANN_TIE_RUST ? 1u : 0u;
+        sel.out_ids = c_sel_ids.as<uint32_t>();
+        sel.out_d = c_sel_d.as<float>();
+        sel.out_cnt = c_sel_cnt.as<uint32_t>();
+        sel.stats = ga.stats;
+        for (uint32_t lo = 0; lo < nwork; lo += chunk) {
+            const uint32_t m = std::min<uint32_t>(chunk, nwork - lo);
+            ga.lo = lo;
+            int32_t rc = launch_rows(ix, kConsGather, "cons_gather_kernel launch", ga, m, lds, st);
+            if (rc != DANN_OK) return rc;
+            bool used_gram = false;
+            if (huge) {
+                hipLaunchKernelGGL(cons_select_kernel, dim3(m), dim3(256), 0, st, sel);
+                DANN_HIP(hipGetLastError());
+                rc = prune_pools_into_rows(idx, *cfg, ga.locs, sel.out_ids, sel.out_d, sel.out_cnt, kMaxPool, m,
+                                           &used_gram);
+            } else {
+                rc = prune_pools_into_rows(idx, *cfg, ga.locs, ga.pool_ids, ga.pool_d, ga.counts, pcap, m, &used_gram);
+            }
+            if (rc != DANN_OK) return rc;
+        }
+    }
+    if (pass.drop_deleted && idx->d_deleted) {
+        hipLaunchKernelGGL(drop_deleted_kernel, dim3((idx->nslots + 255u) / 256u), dim3(256), 0, st, ix, idx->d_deleted);
+        DANN_HIP(hipGetLastError());
+    }
+    std::vector<uint8_t> h_kinds(out_kind ? n : 0);
+    std::vector<unsigned long long> h_stats((size_t)kStatLines * kStatWords);
+    uint32_t h_err = 0;
+    if (out_kind) DANN_HIP(hipMemcpyAsync(h_kinds.data(), d_kinds.p, n, hipMemcpyDeviceToHost, st));
+    DANN_HIP(hipMemcpyAsync(h_stats.data(), d_stats.p, stats_bytes, hipMemcpyDeviceToHost, st));
+    DANN_HIP(hipMemcpyAsync(&h_err, meta + 6, 4, hipMemcpyDeviceToHost, st));
+    DANN_HIP(hipStreamSynchronize(st));
+    if (h_err & 2u) {
+        set_error("%s: an adjacency list holds a neighbour id out of bounds (%u slots); that list is left as it is", pass.who,
+                  idx->nslots);
+        return DANN_EBOUNDS;
+    }
+    if (h_err) {
+        set_error("%s: a candidate pool outgrew its bound", pass.who);
+        return DANN_EINTERNAL;
+    }
+    if (out_kind)
+        for (uint32_t i = 0; i < n; ++i) out_kind[i] = h_kinds[i];
+    uint64_t sums[kStatWords] = {0, 0, 0, 0, 0, 0};
+    for (uint32_t l = 0; l < kStatLines; ++l)
+        for (uint32_t w = 0; w < kStatWords; ++w) {
+            const unsigned long long x = h_stats[(size_t)l * kStatWords + w];
+            sums[w] = w == 2 ? std::max<uint64_t>(sums[w], x) : sums[w] + x;
+        }
+    uint64_t bc1[11] = {};
+    if (pass.want_counters) {
+        if (int32_t rc = dann_build_counters(idx, bc1, 11)) return rc;
+    }
+    pass.rewritten = sums[0];
+    pass.pruned = sums[1];
+    pass.largest = sums[2];
+    pass.distances = sums[3] + (bc1[4] - bc0[4]) + (bc1[8] - bc0[8]);
+    pass.on_matrix_cores = bc1[0] - bc0[0];  // the sweep of the matrix-core path counts every prune it runs
+    pass.oversized = sums[4];
+    pass.oversized_tied = sums[5];
+    pass.scanned = h_counts[7];
+    pass.unreadable = h_counts[8];
+    return DANN_OK;
+}
+}  // namespace dann
+
 extern "C" {
 
 int32_t dann_delete_points(dann_index* idx, const uint32_t* slots, uint32_t n) try {
@@ -371,157 +579,23 @@ int32_t dann_consolidate(dann_index* idx, const dann_build_config* cfg, const ui
         n = idx->nslots;
     }
     DeviceGuard guard(idx->device);
-    hipStream_t st = idx->main.stream;
-    const IndexView ix = idx->view();
-    uint64_t bc0[11] = {};
+    ListPrunePass pass;
+    pass.who = "dann_consolidate";
+    pass.ids = ids;
+    pass.n = n;
+    pass.drop_deleted = (flags & DANN_CONSOLIDATE_DROP_DELETED) != 0;
+    pass.out_kind = out_kind;
+    pass.want_counters = out_counters != nullptr;
+    if (int32_t rc = run_list_prunes(idx, cfg, pass)) return rc;
     if (out_counters) {
-        if (int32_t rc = dann_build_counters(idx, bc0, 11)) return rc;
-    }
-    // per-call scratch: ids + claim bitmap, kinds, the two worklists, counts, striped stats, error word
-    const size_t claim_words = ids ? (idx->nslots + 31u) / 32u : 0u;
-    DevBuf d_ids, d_claim, d_kinds, d_work, d_meta, d_stats;
-    if (ids) {
-        DANN_HIP(d_ids.alloc((size_t)n * 4));
-        DANN_HIP(hipMemcpyAsync(d_ids.p, ids, (size_t)n * 4, hipMemcpyHostToDevice, st));
-        DANN_HIP(d_claim.alloc(claim_words * 4));
-        DANN_HIP(hipMemsetAsync(d_claim.p, 0, claim_words * 4, st));
-    }
-    DANN_HIP(d_kinds.alloc(n));
-    DANN_HIP(d_work.alloc((size_t)n * 12));
-    DANN_HIP(d_meta.alloc(64));
-    DANN_HIP(hipMemsetAsync(d_meta.p, 0, 64, st));
-    const size_t stats_bytes = (size_t)kStatLines * kStatWords * 8;
-    DANN_HIP(d_stats.alloc(stats_bytes));
-    DANN_HIP(hipMemsetAsync(d_stats.p, 0, stats_bytes, st));
-    uint32_t* meta = d_meta.as<uint32_t>();  // [0..5] scan counts, [6] error word
-    uint32_t* work = d_work.as<uint32_t>();
-
-    ConsScanArgs sa;
-    sa.ix = ix;
-    sa.bm = idx->d_deleted;
-    sa.ids = ids ? d_ids.as<uint32_t>() : nullptr;
-    sa.n = n;
-    sa.claim = ids ? d_claim.as<uint32_t>() : nullptr;
-    sa.pruned_degree = cfg->pruned_degree;
-    sa.kinds = d_kinds.as<uint8_t>();
-    for (int c = 0; c < 3; ++c) sa.work[c] = work + (size_t)c * n;
-    sa.counts = meta;
-    hipLaunchKernelGGL(cons_scan_kernel, dim3((n + 3u) / 4u), dim3(64), 0, st, sa);
-    DANN_HIP(hipGetLastError());
-    uint32_t h_counts[6] = {0, 0, 0, 0, 0, 0};
-    DANN_HIP(hipMemcpyAsync(h_counts, meta, 24, hipMemcpyDeviceToHost, st));
-    DANN_HIP(hipStreamSynchronize(st));
-
-    // the matrix-core path keeps a Gram block per item in the index's build scratch: chunks of it stay at the build's
-    // batch scale
-    const uint32_t max_chunk = prune_pools_use_gram(idx) ? 2048u : 8192u;
-    DevBuf c_locs, c_ids, c_d, c_cnt, c_hash, c_keys, c_sel_ids, c_sel_d, c_sel_cnt;
-    size_t c_elems = 0, c_items = 0;
-    for (int cls = 0; cls < 3; ++cls) {
-        const uint32_t nwork = h_counts[cls];
-        if (nwork == 0) continue;
-        const bool huge = cls == 2;
-        const uint32_t pcap = pow2_at_least(h_counts[3 + cls]);
-        const uint32_t chunk =
-            std::min<uint32_t>(nwork, std::max<uint32_t>(huge ? 16u : 256u, std::min<uint32_t>(max_chunk, kChunkElems / pcap)));
-        if ((size_t)chunk * pcap > c_elems || chunk > c_items) {
-            // (earlier classes' buffers serve a later one when large enough; hipFree waits for the work queued on them)
-            c_elems = std::max<size_t>(c_elems, (size_t)chunk * pcap);
-            DANN_HIP(c_ids.alloc(c_elems * 4));
-            DANN_HIP(c_d.alloc(c_elems * 4));
-            if (chunk > c_items) {
-                c_items = chunk;
-                DANN_HIP(c_locs.alloc(c_items * 4));
-                DANN_HIP(c_cnt.alloc(c_items * 4));
-                DANN_HIP(hipMemsetAsync(c_locs.p, 0, c_items * 4, st));
-            }
-        }
-        if (huge) {  // global pools: hash sets, sort keys and the selected heads (stride kMaxPool)
-            DANN_HIP(c_hash.alloc((size_t)chunk * pcap * 8));
-            DANN_HIP(c_keys.alloc((size_t)chunk * pcap * 8));
-            DANN_HIP(c_sel_ids.alloc((size_t)chunk * kMaxPool * 4));
-            DANN_HIP(c_sel_d.alloc((size_t)chunk * kMaxPool * 4));
-            DANN_HIP(c_sel_cnt.alloc((size_t)chunk * 4));
-        }
-        ConsGatherArgs ga;
-        ga.ix = ix;
-        ga.bm = idx->d_deleted;
-        ga.ids = sa.ids;
-        ga.work = sa.work[cls];
-        ga.pruned_degree = cfg->pruned_degree;
-        ga.pcap = pcap;
-        ga.in_global = huge ? 1u : 0u;
-        ga.hash = huge ? c_hash.as<uint32_t>() : nullptr;
-        ga.locs = c_locs.as<uint32_t>();
-        ga.pool_ids = c_ids.as<uint32_t>();
-        ga.pool_d = c_d.as<float>();
-        ga.counts = c_cnt.as<uint32_t>();
-        ga.stats = d_stats.as<unsigned long long>();
-        ga.err = meta + 6;
-        const size_t lds = (size_t)(ix.max_degree + (huge ? 0u : 3u * pcap)) * 4u;
-        ConsSelectArgs sel;
-        sel.in_ids = ga.pool_ids;
-        sel.in_d = ga.pool_d;
-        sel.in_cnt = ga.counts;
-        sel.in_stride = pcap;
-        sel.keys = c_keys.as<uint64_t>();
-        sel.keep = cfg->max_occlusion_size ? cfg->max_occlusion_size : 750u;
-        sel.tie_rust = idx->prune_tie_order == DANN_TIE_RUST ? 1u : 0u;
-        sel.out_ids = c_sel_ids.as<uint32_t>();
-        sel.out_d = c_sel_d.as<float>();
-        sel.out_cnt = c_sel_cnt.as<uint32_t>();
-        sel.stats = ga.stats;
-        for (uint32_t lo = 0; lo < nwork; lo += chunk) {
-            const uint32_t m = std::min<uint32_t>(chunk, nwork - lo);
-            ga.lo = lo;
-            int32_t rc = launch_rows(ix, kConsGather, "cons_gather_kernel launch", ga, m, lds, st);
-            if (rc != DANN_OK) return rc;
-            bool used_gram = false;
-            if (huge) {
-                hipLaunchKernelGGL(cons_select_kernel, dim3(m), dim3(256), 0, st, sel);
-                DANN_HIP(hipGetLastError());
-                rc = prune_pools_into_rows(idx, *cfg, ga.locs, sel.out_ids, sel.out_d, sel.out_cnt, kMaxPool, m,
-                                           &used_gram);
-            } else {
-                rc = prune_pools_into_rows(idx, *cfg, ga.locs, ga.pool_ids, ga.pool_d, ga.counts, pcap, m, &used_gram);
-            }
-            if (rc != DANN_OK) return rc;
-        }
-    }
-    if ((flags & DANN_CONSOLIDATE_DROP_DELETED) && idx->d_deleted) {
-        hipLaunchKernelGGL(drop_deleted_kernel, dim3((idx->nslots + 255u) / 256u), dim3(256), 0, st, ix, idx->d_deleted);
-        DANN_HIP(hipGetLastError());
-    }
-    std::vector<uint8_t> h_kinds(out_kind ? n : 0);
-    std::vector<unsigned long long> h_stats((size_t)kStatLines * kStatWords);
-    uint32_t h_err = 0;
-    if (out_kind) DANN_HIP(hipMemcpyAsync(h_kinds.data(), d_kinds.p, n, hipMemcpyDeviceToHost, st));
-    DANN_HIP(hipMemcpyAsync(h_stats.data(), d_stats.p, stats_bytes, hipMemcpyDeviceToHost, st));
-    DANN_HIP(hipMemcpyAsync(&h_err, meta + 6, 4, hipMemcpyDeviceToHost, st));
-    DANN_HIP(hipStreamSynchronize(st));
-    if (h_err) {
-        set_error("dann_consolidate: a candidate pool outgrew its bound");
-        return DANN_EINTERNAL;
-    }
-    if (out_kind)
-        for (uint32_t i = 0; i < n; ++i) out_kind[i] = h_kinds[i];
-    if (out_counters) {
-        uint64_t sums[kStatWords] = {0, 0, 0, 0, 0, 0};
-        for (uint32_t l = 0; l < kStatLines; ++l)
-            for (uint32_t w = 0; w < kStatWords; ++w) {
-                const unsigned long long x = h_stats[(size_t)l * kStatWords + w];
-                sums[w] = w == 2 ? std::max<uint64_t>(sums[w], x) : sums[w] + x;
-            }
-        uint64_t bc1[11] = {};
-        if (int32_t rc = dann_build_counters(idx, bc1, 11)) return rc;
         out_counters[0] = n;
-        out_counters[1] = sums[0];
-        out_counters[2] = sums[1];
-        out_counters[3] = sums[2];
-        out_counters[4] = sums[3] + (bc1[4] - bc0[4]) + (bc1[8] - bc0[8]);
-        out_counters[5] = bc1[0] - bc0[0];  // the sweep of the matrix-core path counts every prune it runs
-        out_counters[6] = sums[4];
-        out_counters[7] = sums[5];
+        out_counters[1] = pass.rewritten;
+        out_counters[2] = pass.pruned;
+        out_counters[3] = pass.largest;
+        out_counters[4] = pass.distances;
+        out_counters[5] = pass.on_matrix_cores;
+        out_counters[6] = pass.oversized;
+        out_counters[7] = pass.oversized_tied;
     }
     return DANN_OK;
 } DANN_CATCH_ALL

@@ -188,6 +188,25 @@ int32_t prune_pools_into_rows(dann_index* idx, const dann_build_config& cfg, con
                               const float* d_dists, const uint32_t* d_counts, uint32_t stride, uint32_t m, bool* used_gram);
 // idx->d_deleted, allocated and cleared on first use (consolidate.hip; dann_delete_points, dann_inplace_delete)
 int32_t ensure_deleted_bitmap(dann_index* idx);
+// consolidate.hip: the scan / gather / prune pass of dann_consolidate, also run by dann_prune_range (graph_stats.hip).
+// The caller holds the index exclusively, has checked cfg and the ids, and made the index's device current.
+struct ListPrunePass {
+    const char* who = "";            // the entry point, for messages
+    const uint32_t* ids = nullptr;   // host; null = the slots [first, first + n)
+    uint32_t first = 0, n = 0;
+    bool prune_range = false;        // no deleted state: a list longer than pruned_degree is pruned, every other left alone;
+                                     // on an inline-tags index unreadable slots are skipped (as neighbours) / left alone (as ids)
+    bool drop_deleted = false;       // DANN_CONSOLIDATE_DROP_DELETED
+    int32_t* out_kind = nullptr;     // n ConsolidateKind values, or null
+    bool want_counters = false;      // read dann_build_counters around the pass (distances, on_matrix_cores)
+    // results (distances and on_matrix_cores without want_counters: the gather's share alone, 0)
+    uint64_t scanned = 0, unreadable = 0, rewritten = 0, pruned = 0, largest = 0, distances = 0, on_matrix_cores = 0,
+             oversized = 0, oversized_tied = 0;
+};
+int32_t run_list_prunes(dann_index* idx, const dann_build_config* cfg, ListPrunePass& pass);
+// medoid_kernels.hip: dann_medoid_device's body (the device is current); times_ms: null, or the two passes' HIP-event times
+int32_t medoid_device(int32_t dtype, const void* d_rows, uint64_t nrows, uint32_t dim, uint64_t stride, int64_t* out_row,
+                      float* d_out_mean, uint64_t* out_counters, double* times_ms);
 
 // minmax_kernels.hip: MinMaxQuantizer::compress on device buffers (dann_minmax_compress, dann_minmax_quantize(_device))
 int32_t launch_minmax_compress(int32_t bits, const float* d_x, uint32_t n, uint32_t dim, float grid_scale, uint8_t* d_out,

@@ -17,6 +17,7 @@
 
 #include "dann_device.h"
 #include "dann_internal.h"
+#include "seq_sum.h"
 
 namespace dann {
 namespace {
@@ -383,60 +384,11 @@ __global__ __launch_bounds__(256) void pq_assign_mfma_kernel(const float* data, 
 // ---- a sequential f64 sum, evaluated in parallel wherever that cannot change a bit ---------------------------------
 // The trainer's D^2 draw and its totals are rolling f64 sums over 131 072 f32 values / 8 192 block sums in row order
 // (plusplus.rs:446-462, the micro-kernel's RollingSum): one thread walking them was 2.5 of the trainer's 3.1 seconds.
-// A floating-point sum is order-independent exactly when no addition rounds.  For a range of values v_i with
-// g = the exponent of the lowest set bit over the v_i and the running sum acc at the range's start, and
-// A = sum |v_i|: every partial sum the sequential walk forms is a multiple of 2^min(g, lsb(acc)) and at most
-// |acc| + A in magnitude; if |acc| + A < 2^(min(g, lsb(acc)) + 53) they are all representable, no addition rounds,
-// and the walk's result is acc + (sum of the range in ANY association).  `seq_exact` is that test (A carries a 2^-30
-// margin for its own rounding; a non-finite value fails it).  Ranges that fail are walked one element at a time by one
-// thread, exactly as before: a low bit pushed out when acc crosses a power of two, or a value far below the running
-// sum's last place -- local events on continuous data.
-struct SeqSummary {
-    double S, A;
-    int g;
-};
-constexpr int kSeqNone = 0x7FFFFFFF, kSeqBad = (int)0x80000000;
+// seq_sum.h holds the argument and the test (SeqSummary, seq_take, seq_join, seq_exact); ranges that fail it are walked
+// one element at a time by one thread, exactly as before.
 // [0] wavefront-level ranges taken in parallel, [1] thread-level ranges taken in parallel, [2] ranges walked element by
 // element, [3] elements walked (dann_debug_pq_rolling_sum_stats: the tests assert that both paths ran)
 __device__ unsigned long long g_seq_stats[4];
-__device__ __forceinline__ int lsb_exp_f64(double v) {  // finite, non-zero
-    const uint64_t b = (uint64_t)__builtin_bit_cast(long long, v);
-    const int e = (int)((b >> 52) & 0x7FFu);
-    uint64_t m = b & ((1ull << 52) - 1u);
-    if (e == 0) return -1074 + (int)__builtin_ctzll(m);
-    m |= 1ull << 52;
-    return e - 1075 + (int)__builtin_ctzll(m);
-}
-__device__ __forceinline__ void seq_take(SeqSummary& s, double v) {
-    s.S += v;
-    s.A += __builtin_fabs(v);
-    if (!(__builtin_fabs(v) < __builtin_inf())) s.g = kSeqBad;
-    else if (v != 0.0 && s.g != kSeqBad) {
-        const int g = lsb_exp_f64(v);
-        s.g = g < s.g ? g : s.g;
-    }
-}
-__device__ __forceinline__ SeqSummary seq_join(const SeqSummary& a, const SeqSummary& b) {
-    SeqSummary r;
-    r.S = a.S + b.S;
-    r.A = a.A + b.A;
-    r.g = (a.g == kSeqBad || b.g == kSeqBad) ? kSeqBad : (a.g < b.g ? a.g : b.g);
-    return r;
-}
-__device__ __forceinline__ bool seq_exact(double acc, const SeqSummary& s) {
-    if (s.g == kSeqBad || !(__builtin_fabs(acc) < __builtin_inf())) return false;
-    int g = s.g;
-    if (acc != 0.0) {
-        const int ga = lsb_exp_f64(acc);
-        g = ga < g ? ga : g;
-    }
-    if (g == kSeqNone) return true;  // nothing but zeros on a zero sum
-    const double bound = (__builtin_fabs(acc) + s.A) * (1.0 + 0x1p-30);
-    const int lim = g + 53;
-    if (lim > 1023) return bound < __builtin_inf();
-    if (lim < -1021) return false;
-    return bound < __builtin_ldexp(1.0, lim);
-}
 // One workgroup of 1024 threads walks `count` values in order (LOAD(i) -> double).  Thread t owns the contiguous range
 // [t seg, (t + 1) seg); wavefront w the 64 ranges of its lanes.  Returns (thread 0) the sequential sum; with SELECT also
 // finds the first index whose prefix sum reaches `thr` and passes PRED(i) (the D^2 draw), UINT64_MAX if none.

@@ -557,6 +557,43 @@ class Provider:
                                           _p(counters)), "dann_consolidate")
         return kinds, counters
 
+    # -- DiskANNIndex::prune_range / count_reachable_nodes / get_degree_stats --
+    def prune_range(self, cfg, ids=None, first=0, n=None):
+        """prune_range (the builder's final_prune) on the ids, or on the slots [first, first + n) (n None: up to the
+        last non-start slot) -> the six counters of dann_prune_range (dann.h)"""
+        counters = np.zeros(6, np.uint64)
+        if ids is None:
+            a, n = None, (max(self.capacity - first, 0) if n is None else int(n))
+        else:
+            a = np.ascontiguousarray(ids, dtype=np.uint32).ravel()
+            first, n = 0, a.size
+        check(_ffi.lib().dann_prune_range(self._h, C.byref(cfg), _p(a), int(first), n, _p(counters)), "dann_prune_range")
+        return counters
+
+    def count_reachable(self, starts=None, bitmap=False):
+        """count_reachable_nodes from the start ids (None: the index's start points) -> (count, levels), with
+        bitmap=True -> (count, levels, reached): a boolean per slot"""
+        a = None if starts is None else np.ascontiguousarray(starts, dtype=np.uint32).ravel()
+        nslots = self.capacity + self.num_start_points
+        words = np.zeros((nslots + 31) // 32, np.uint32) if bitmap else None
+        count, levels = C.c_uint64(0), C.c_uint32(0)
+        check(_ffi.lib().dann_count_reachable(self._h, _p(a), 0 if a is None else a.size, C.byref(count), C.byref(levels),
+                                              _p(words)), "dann_count_reachable")
+        if not bitmap:
+            return int(count.value), int(levels.value)
+        reached = np.unpackbits(words.view(np.uint8), bitorder="little")[:nslots].astype(bool)
+        return int(count.value), int(levels.value), reached
+
+    def degree_stats(self, ids=None, skip_deleted=False):
+        """get_degree_stats over the ids (None: the slots [0, capacity)) -> _ffi.DegreeStats"""
+        a = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32).ravel()
+        out = _ffi.DegreeStats()
+        if a is not None and a.size == 0:
+            return out  # (a null pointer would ask for the default range)
+        check(_ffi.lib().dann_degree_stats(self._h, _p(a), 0 if a is None else a.size,
+                                           _ffi.DEGREE_SKIP_DELETED if skip_deleted else 0, C.byref(out)), "dann_degree_stats")
+        return out
+
     # -- DiskANNIndex::multi_inplace_delete / drop_deleted_neighbors ---------
     def inplace_delete(self, cfg, ids, method=_ffi.INPLACE_TWO_HOP_AND_ONE_HOP, k=0, l=0, num_to_replace=3,
                        minibatch=None):
@@ -782,6 +819,41 @@ def sq_compress(x, shift, scale, bits, device=-1):
     check(_ffi.lib().dann_sq_compress(device, int(bits), _p(x), x.shape[0], x.shape[1], _p(shift), float(scale), _p(out)),
           "dann_sq_compress")
     return out
+
+
+MEDOID_DTYPES = {np.dtype(np.float32): F32, np.dtype(np.float16): F16, np.dtype(np.uint8): U8, np.dtype(np.int8): I8}
+
+
+def medoid(rows, device=0, row_stride=0, dtype=None, dim=None):
+    """ComputeMedoid (dann_medoid / dann_medoid_device) -> (row, mean, counters).  `rows`: a 2-D numpy array (host entry) or
+    a 2-D torch tensor on the GPU (device entry; the mean then comes back as a device tensor).  row -1: no row won.
+    A raw store -- a 2-D uint8 array or tensor whose rows are row_stride bytes -- is read as `dtype` rows of `dim` elements."""
+    counters = np.zeros(4, np.uint64)
+    out_row = C.c_int64(-1)
+    if isinstance(rows, np.ndarray):
+        if dtype is None:
+            rows = np.ascontiguousarray(rows)
+            dtype, (n, dim), row_stride = MEDOID_DTYPES[rows.dtype], rows.shape, 0
+        else:
+            rows = np.ascontiguousarray(rows, dtype=np.uint8)
+            n, row_stride = rows.shape
+        mean = np.zeros(dim, np.float32)
+        check(_ffi.lib().dann_medoid(device, dtype, _p(rows), n, dim, row_stride, C.byref(out_row), _p(mean), _p(counters)),
+              "dann_medoid")
+        return int(out_row.value), mean, counters
+    import torch
+    assert rows.is_cuda and rows.dim() == 2 and rows.stride(1) == 1, "a 2-D device tensor with contiguous rows"
+    if dtype is None:
+        names = {torch.float32: F32, torch.float16: F16, torch.uint8: U8, torch.int8: I8}
+        dtype, (n, dim), row_stride = names[rows.dtype], rows.shape, rows.stride(0) * rows.element_size()
+    else:
+        assert rows.dtype == torch.uint8
+        n, row_stride = rows.shape[0], rows.stride(0)
+    mean = torch.zeros(dim, dtype=torch.float32, device=rows.device)
+    torch.cuda.synchronize(rows.device)  # the call runs on the null stream
+    check(_ffi.lib().dann_medoid_device(rows.device.index, dtype, C.c_void_p(rows.data_ptr()), n, dim, row_stride,
+                                        C.byref(out_row), C.c_void_p(mean.data_ptr()), _p(counters)), "dann_medoid_device")
+    return int(out_row.value), mean, counters
 
 
 def minmax_compress(x, bits, grid_scale=1.0, device=-1, return_loss=False):

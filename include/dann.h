@@ -571,6 +571,26 @@ int32_t dann_sq_compress(int32_t device, int32_t bits, const float* x, uint32_t 
  * A NaN in row i: DANN_EINVAL (InputContainsNaN), outputs unspecified.  Host pointers. */
 int32_t dann_minmax_compress(int32_t device, int32_t bits, const float* x, uint32_t n, uint32_t dim, float grid_scale,
                              void* out, float* out_loss);
+/* ComputeMedoid (diskann-utils/src/sampling/medoid.rs:15-156), the start point of StartPointStrategy::Medoid: the row
+ * nearest to the mean of the rows.  dtype: DANN_F32, DANN_F16, DANN_U8 or DANN_I8 (anything else: DANN_EUNSUPPORTED).
+ * Rows lie row_stride_bytes apart (0 = packed, dim * sizeof(T); less than that, or a stride / address that is not a
+ * multiple of sizeof(T): DANN_EINVAL), so an index's own store can be passed (dann_index_device_pointers).
+ *   mean[c] = (f32)(sum_c / (f64)nrows), sum_c the SEQUENTIAL f64 sum of column c in row order from 0.0.  The sum is
+ *   evaluated in parallel over ranges of rows wherever no addition can round -- it is then the same in any order -- and
+ *   row by row from the carry elsewhere: the returned bits are those of the sequential walk.
+ *   d_r = SquaredL2::evaluate(mean, row_r): f32 rows in the f32 x f32 order, f16 rows in the f32 x f16 order, u8 / i8 rows
+ *   widened to f32 in the f32 x f32 order (not the integer kernels).  *out_row = the first row with d_r < min, min
+ *   starting at f32::MAX: equal distances keep the earlier row, a NaN distance never wins, and -1 says that no row won
+ *   (nrows == 0, or no distance below f32::MAX; the mean of no rows is the zero vector, as in the reference).
+ * out_mean (dim floats, may be NULL).  out_counters (may be NULL): 4 words -- [0] ranges of a column summed in parallel,
+ * [1] ranges walked row by row, [2] rows scanned, [3] distances that were NaN.  dim == 0: DANN_EINVAL; dim > 16000:
+ * DANN_EUNSUPPORTED.  device < 0: the current device.  dann_medoid takes host pointers; dann_medoid_device takes rows
+ * and out_mean in device memory (out_row and out_counters stay host pointers) and is host-synchronous on the null
+ * stream. */
+int32_t dann_medoid(int32_t device, int32_t dtype, const void* rows, uint64_t nrows, uint32_t dim,
+                    uint64_t row_stride_bytes, int64_t* out_row, float* out_mean, uint64_t* out_counters);
+int32_t dann_medoid_device(int32_t device, int32_t dtype, const void* rows, uint64_t nrows, uint32_t dim,
+                           uint64_t row_stride_bytes, int64_t* out_row, float* out_mean, uint64_t* out_counters);
 
 /* ---- the quantisers' transforms (diskann-quantization/src/algorithms/transforms), applied on the GPU, device to device.
  * Only CONSTRUCTING a transform draws random numbers; the host keeps doing that and hands over the parts that
@@ -734,6 +754,53 @@ int32_t dann_delete_points(dann_index* idx, const uint32_t* slots, uint32_t n);
 int32_t dann_get_deleted(const dann_index* idx, uint32_t first_slot, uint32_t n, uint8_t* out);
 int32_t dann_consolidate(dann_index* idx, const dann_build_config* cfg, const uint32_t* ids, uint32_t n, uint32_t flags,
                          int32_t* out_kind, uint64_t* out_counters);
+
+/* ---- finishing a build: what the reference's in-memory builder runs after its inserts
+ * (diskann-disk/src/build/builder/inmem_builder.rs): final_prune, the reachability check and the degree statistics.
+ *
+ * dann_prune_range == DiskANNIndex::prune_range (index.rs:2656-2701) on ids[0, n), or with ids == NULL on the slots
+ * [first, first + n).  A list of at most cfg->pruned_degree entries is left alone; a longer one is replaced by
+ * robust_prune_list(id, list) with force_saturate = false (index.rs:2397-2454): the pool is the list in list order
+ * without id itself, d(id, c) the index's pair distance, the tie order that of dann_set_prune_tie_order, the kernels
+ * those of dann_set_build_options -- the pass of dann_consolidate without deleted state, its prune work counted in
+ * dann_build_counters in the same way.  One vertex's prune reads only rows and its own list, so the batched pass equals
+ * the sequential loop in any order; an id given twice is pruned once (the reference's second visit finds a short list).
+ * On an inline-tags index a neighbour whose slot is unreadable stays out of the pool.  The reference aborts its loop
+ * with an error when an id's OWN slot is unreadable; here that id is left alone and counted, and the pass goes on.
+ * out_counters (may be NULL): 6 words -- [0] distinct ids scanned, [1] lists pruned, [2] longest list among them,
+ * [3] distances evaluated, [4] lists pruned on the matrix cores, [5] ids left alone because their own slot is unreadable.
+ * Errors: DANN_EBOUNDS for an id or a range past the last slot, and for a list to prune that holds a neighbour id past the
+ * last slot (dann_set_neighbors admits one): that list is left as it is, the other lists of the call are pruned;
+ * DANN_EINVAL for a bad config, DANN_EUNSUPPORTED for DANN_PQ indexes and for max_occlusion_size > 4096.  A mutation:
+ * DANN_EBUSY while search-server tickets are outstanding.
+ *
+ * dann_count_reachable == count_reachable_nodes (index.rs:2161-2189): the number of distinct nodes a breadth-first walk
+ * over the adjacency rows expands from start_ids[0, n_start) -- NULL: the index's start points.  Pure graph: no tags, no
+ * deleted bitmap, no vectors; a list's length word is clamped to max_degree; duplicate start ids count once.
+ * out_levels (may be NULL): the greatest depth reached, start points at depth 0.  out_bitmap (host, may be NULL):
+ * (capacity + num_start_points + 31) / 32 words, bit i set = slot i was reached.  DANN_EBOUNDS for a start id or a
+ * stored neighbour id past the last slot.  Takes the index shared, like a search.
+ *
+ * dann_degree_stats == get_degree_stats (index.rs:2191-2239) over ids[0, n) -- a repeated id counts each time -- or with
+ * ids == NULL over the slots [0, capacity), the reference's non_start_points_ids.  DANN_DEGREE_SKIP_DELETED leaves out
+ * slots that the deleted bitmap marks.  avg_degree = (float)total / (float)points; no points: all zeros.
+ * The struct is the reference's DegreeStats with the exact totals behind avg_degree; it cannot carry the name of the call
+ * that fills it (in C a typedef and a function share one namespace), hence dann_degree_summary. */
+typedef struct {
+    uint32_t max_degree;
+    float avg_degree;
+    uint32_t min_degree;
+    uint32_t reserved;
+    uint64_t cnt_less_than_two;
+    uint64_t points; /* lists counted */
+    uint64_t total;  /* sum of their lengths */
+} dann_degree_summary;
+enum { DANN_DEGREE_SKIP_DELETED = 1 };
+int32_t dann_prune_range(dann_index* idx, const dann_build_config* cfg, const uint32_t* ids, uint32_t first, uint32_t n,
+                         uint64_t* out_counters);
+int32_t dann_count_reachable(const dann_index* idx, const uint32_t* start_ids, uint32_t n_start, uint64_t* out_count,
+                             uint32_t* out_levels, uint32_t* out_bitmap);
+int32_t dann_degree_stats(const dann_index* idx, const uint32_t* ids, uint32_t n, uint32_t flags, dann_degree_summary* out);
 
 /* ---- diversity-aware search: graph::search::Diverse (diskann/src/graph/search/diverse_search.rs:27-233) over
  * DiverseNeighborQueue (diskann/src/neighbor/diverse_priority_queue.rs:63-238).

@@ -116,6 +116,9 @@ int32_t dann_debug_small_call_stats(dann_index* idx, uint64_t* out2);
  * in them can round, ranges walked element by element, elements walked}.  Same bits either way; the tests assert that
  * their hard inputs reach the walk. */
 int32_t dann_debug_pq_rolling_sum_stats(int32_t device, uint64_t* out4, int32_t reset);
+/* dann_medoid_device with the HIP-event times (ms) of its two passes: out_ms[0] the column sums, out_ms[1] the argmin */
+int32_t dann_debug_medoid_times(int32_t device, int32_t dtype, const void* d_rows, uint64_t nrows, uint32_t dim,
+                                uint64_t row_stride_bytes, int64_t* out_row, uint64_t* out_counters, double* out_ms);
 
 /* HIP-event time (ms) and count of the scoring launches (maxsim_mfma_kernel / maxsim_rows_kernel) of a multi-vector set
  * since its creation or the last call with reset != 0; either pointer may be null.  What scratch/maxsim_rate.py times. */
