@@ -175,6 +175,8 @@ SYMBOLS = {
                                                       _vp]),
     "dann_flat_range_search_batch_device": (_i32, [_vp, _vp, _u32, _u32, _u32, _f32, _i32, _f32, _u32, _P(FlatFilter), _u32,
                                                    _vp, _vp, _vp, _vp]),
+    "dann_pq_linear_search_batch": (_i32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _P(FlatFilter), _vp, _vp, _vp]),
+    "dann_pq_linear_search_batch_device": (_i32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _P(FlatFilter), _vp, _vp, _vp]),
     "dann_search_record_batch": (_i32, [_vp, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp]),
     "dann_mvset_create": (_i32, [_i32, _i32, _u32, _u32, _vp, _vp, _P(_vp)]),
     "dann_mvset_destroy": (_i32, [_vp]),

@@ -6,6 +6,7 @@
 #include "api_common.h"
 #include "flat_gt_launch.h"
 #include "flat_plan.h"
+#include "flat_pq_plan.h"
 #include "wave_lists.h"  // kTagReadable
 
 namespace dann {
@@ -615,7 +616,7 @@ int32_t flat_check(const dann_index* idx, const void* queries, uint32_t nq, uint
         return DANN_EINVAL;
     }
     if (idx->cfg.dtype == DT_PQ) {
-        set_error("dann_flat_search_batch: not defined on DANN_PQ rows (dann_pq_scan scores PQ codes)");
+        set_error("dann_flat_search_batch: not defined on DANN_PQ rows (dann_pq_linear_search_batch scans PQ codes)");
         return DANN_EUNSUPPORTED;
     }
     if (k > kFlatMaxK) {
@@ -741,7 +742,7 @@ int32_t flat_range_check(const dann_index* idx, const void* queries, uint32_t nq
         return DANN_EINVAL;
     }
     if (idx->cfg.dtype == DT_PQ) {
-        set_error("dann_flat_range_search_batch: not defined on DANN_PQ rows (dann_pq_scan scores PQ codes)");
+        set_error("dann_flat_range_search_batch: not defined on DANN_PQ rows (dann_pq_linear_search_batch scans PQ codes)");
         return DANN_EUNSUPPORTED;
     }
     if ((uint64_t)c.first_slot + c.n > idx->nslots) {
@@ -908,6 +909,135 @@ int32_t dann_flat_filtered_search_batch(dann_index* idx, const void* queries, ui
                       : flat_filtered_run(idx, ctx.stream, plan, hs.extra<void>(0), hs.in(0), m, first_slot, n, flags,
                                           f.stride ? hs.in<uint32_t>(1) : hs.extra<uint32_t>(1), f.stride, hs.out<uint32_t>(0),
                                           hs.out<float>(1), hs.stats());
+    });
+} DANN_CATCH_ALL
+
+// ---- exhaustive scan over PQ code rows (flat_pq_kernels.hip): algos::linear_search ------------------------------------
+}  // extern "C"
+namespace {
+// the checks both forms share; DANN_OK with *done set: nothing to launch and nothing to write
+int32_t pq_linear_check(const dann_index* idx, const float* queries, uint32_t nq, uint32_t first_slot, uint32_t n, uint32_t k,
+                        uint32_t flags, const dann_flat_filter* filter, const uint32_t* out_ids, const float* out_dists,
+                        FlatFilterArg* f, bool* done) {
+    *done = false;
+    if (idx->cfg.dtype != DT_PQ) {
+        set_error("dann_pq_linear_search_batch: defined on DANN_PQ rows only (dann_flat_search_batch scans the other row types)");
+        return DANN_EUNSUPPORTED;
+    }
+    if (flags & ~(uint32_t)DANN_FLAT_SKIP_DELETED) {
+        set_error("dann_pq_linear_search_batch: unknown flag bits 0x%x", flags & ~(uint32_t)DANN_FLAT_SKIP_DELETED);
+        return DANN_EINVAL;
+    }
+    if (k == 0) {
+        set_error("dann_pq_linear_search_batch: k cannot be zero");
+        return DANN_EINVAL;
+    }
+    if (k > kFlatMaxK) {
+        set_error("dann_pq_linear_search_batch: k = %u exceeds the supported maximum of %u", k, kFlatMaxK);
+        return DANN_EUNSUPPORTED;
+    }
+    if (int32_t rc = pq_ready(idx)) return rc;
+    if ((uint64_t)first_slot + n > idx->nslots) {
+        set_error("dann_pq_linear_search_batch: slots [%u, %llu) leave the index's %u slots", first_slot,
+                  (unsigned long long)first_slot + n, idx->nslots);
+        return DANN_EBOUNDS;
+    }
+    if (int32_t rc = flat_filter_check("dann_pq_linear_search_batch", idx, filter, f)) return rc;
+    if (nq == 0) {
+        *done = true;
+        return DANN_OK;
+    }
+    if (!queries || !out_ids || !out_dists) {
+        set_error("dann_pq_linear_search_batch: null pointer");
+        return DANN_EINVAL;
+    }
+    return DANN_OK;
+}
+
+// how the scan of `nq` queries is cut up (flat_pq_plan.h)
+FlatPqPlan pq_linear_make_plan(const dann_index* idx, uint32_t nq, uint32_t n, uint32_t k) {
+    const FlatPqPlan plan =
+        flat_pq_plan(idx->cfg.pq_chunks, n, nq, k, idx->num_cus, idx->dbg_u32(DANN_DBG_FLAT_CHUNK_ROWS, 0u));
+    if (idx->verbose())
+        fprintf(stderr, "[dann] PQ linear scan: %u chunks n %u nq %u k %u -> tile %u, %u chunks of %u slots, %u queries per launch\n",
+                plan.chunks, n, nq, k, plan.tile, plan.nchunks, plan.chunk_rows, plan.batch);
+    return plan;
+}
+
+// the scan of nq queries (at most as many as the plan was made for) on device buffers, plan.batch queries per launch;
+// `scratch`: plan.scratch_bytes(); d_bits: the bitmaps of these queries (null: none)
+int32_t pq_linear_run(dann_index* idx, hipStream_t st, const FlatPqPlan& plan, void* scratch, const float* d_queries, uint32_t nq,
+                      uint32_t first_slot, uint32_t n, uint32_t flags, const uint32_t* d_bits, uint64_t stride, uint32_t* d_ids,
+                      float* d_dists, dann_search_stats* d_stats) {
+    const IndexView ix = idx->qview();
+    const uint32_t* deleted = (flags & DANN_FLAT_SKIP_DELETED) ? idx->d_deleted : nullptr;
+    for (uint32_t off = 0; off < nq; off += plan.batch) {
+        const uint32_t m = std::min(plan.batch, nq - off);
+        int32_t rc = launch_flat_pq_search(ix, plan, d_queries + (size_t)off * ix.dim, m, first_slot, n, deleted,
+                                           d_bits ? d_bits + (size_t)off * stride : nullptr, stride, scratch,
+                                           d_ids + (size_t)off * plan.k, d_dists + (size_t)off * plan.k,
+                                           d_stats ? d_stats + off : nullptr, st);
+        if (rc != DANN_OK) return rc;
+    }
+    return DANN_OK;
+}
+}  // namespace
+extern "C" {
+
+int32_t dann_pq_linear_search_batch_device(dann_index* idx, const float* d_queries, uint32_t nq, uint32_t first_slot,
+                                           uint32_t n, uint32_t k, uint32_t flags, const dann_flat_filter* d_filter,
+                                           uint32_t* d_out_ids, float* d_out_dists, dann_search_stats* d_out_stats) try {
+    CHECK_IDX_SHARED(idx);
+    ArenaTrim _trim{ctx};
+    bool done = false;
+    FlatFilterArg f;
+    if (int32_t rc = pq_linear_check(idx, d_queries, nq, first_slot, n, k, flags, d_filter, d_out_ids, d_out_dists, &f, &done))
+        return rc;
+    if (done) return DANN_OK;
+    if (n == 0) {
+        if (int32_t rc = launch_flat_empty(nq, k, d_out_ids, d_out_dists, d_out_stats, ctx.stream)) return rc;
+    } else {
+        const FlatPqPlan plan = pq_linear_make_plan(idx, nq, n, k);
+        if (int32_t rc = grow_stage(ctx, 4, plan.scratch_bytes())) return rc;
+        if (int32_t rc = pq_linear_run(idx, ctx.stream, plan, ctx.stage[4], d_queries, nq, first_slot, n, flags, f.bits, f.stride,
+                                       d_out_ids, d_out_dists, d_out_stats))
+            return rc;
+    }
+    DANN_HIP(hipStreamSynchronize(ctx.stream));
+    return DANN_OK;
+} DANN_CATCH_ALL
+
+int32_t dann_pq_linear_search_batch(dann_index* idx, const float* queries, uint32_t nq, uint32_t first_slot, uint32_t n,
+                                    uint32_t k, uint32_t flags, const dann_flat_filter* filter, uint32_t* out_ids,
+                                    float* out_dists, dann_search_stats* out_stats) try {
+    CHECK_IDX_SHARED(idx);
+    ArenaTrim _trim{ctx};
+    bool done = false;
+    FlatFilterArg f;
+    if (int32_t rc = pq_linear_check(idx, queries, nq, first_slot, n, k, flags, filter, out_ids, out_dists, &f, &done)) return rc;
+    if (done) return DANN_OK;
+    // pieces by flat_host_piece, the plan made for one piece; a shared bitmap goes up once.  extras: the plan's scratch, the
+    // shared bitmap
+    const size_t words = ((size_t)idx->nslots + 31) / 32;
+    const uint32_t piece = flat_host_piece(nq, f.stride, 0);
+    FlatPqPlan plan;
+    if (n != 0) plan = pq_linear_make_plan(idx, piece, n, k);
+    const size_t scratch = n != 0 ? plan.scratch_bytes() : 0;
+    const bool shared = f.bits && !f.stride;
+    HostStage hs;
+    const int32_t lrc =
+        f.stride ? hs.layout(ctx, nq, piece, {{queries, idx->query_bytes()}, {f.bits, (size_t)f.stride * 4}},
+                             {{out_ids, (size_t)k * 4}, {out_dists, (size_t)k * 4}}, HostStage::kCopyStats, {scratch})
+                 : hs.layout(ctx, nq, piece, {{queries, idx->query_bytes()}},
+                             {{out_ids, (size_t)k * 4}, {out_dists, (size_t)k * 4}}, HostStage::kCopyStats,
+                             {scratch, shared ? words * 4 : 0});
+    if (lrc) return lrc;
+    if (shared) DANN_HIP(hipMemcpyAsync(hs.extra<void>(1), f.bits, words * 4, hipMemcpyHostToDevice, ctx.stream));
+    return hs.walk(out_stats, nullptr, [&](uint32_t, uint32_t m) {
+        const uint32_t* d_bits = f.stride ? hs.in<uint32_t>(1) : shared ? hs.extra<uint32_t>(1) : nullptr;
+        return n == 0 ? launch_flat_empty(m, k, hs.out<uint32_t>(0), hs.out<float>(1), hs.stats(), ctx.stream)
+                      : pq_linear_run(idx, ctx.stream, plan, hs.extra<void>(0), hs.in<float>(0), m, first_slot, n, flags, d_bits,
+                                      f.stride, hs.out<uint32_t>(0), hs.out<float>(1), hs.stats());
     });
 } DANN_CATCH_ALL
 

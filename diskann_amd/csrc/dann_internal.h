@@ -265,6 +265,16 @@ int32_t launch_flat_search(const IndexView& ix, const FlatPlan& plan, const void
                            dann_search_stats* d_stats, hipStream_t stream);
 int32_t launch_flat_empty(uint32_t nq, uint32_t k, uint32_t* d_ids, float* d_dists, dann_search_stats* d_stats,
                           hipStream_t stream);
+// pq_kernels.hip: the lookup tables [nq][nchunks][256] of nq f32 queries (populate_chunk_distances_impl), device to device
+int32_t launch_pq_lut(int32_t metric, const float* d_pivots, const uint32_t* d_offsets, uint32_t nchunks, uint32_t dim,
+                      const float* d_queries, uint32_t nq, float* d_lut, hipStream_t stream);
+// flat_pq_kernels.hip: the exhaustive scan over PQ code rows of dann_pq_linear_search_batch(_device), cut up as
+// flat_pq_plan.h says.  One launch serves at most plan.batch queries over slots [first, first + n), n > 0; `scratch` holds
+// plan.scratch_bytes(); d_filter: these queries' bitmaps (null: every slot matches), `stride` words apart (0: one for all).
+struct FlatPqPlan;
+int32_t launch_flat_pq_search(const IndexView& ix, const FlatPqPlan& plan, const float* d_queries, uint32_t nq, uint32_t first,
+                              uint32_t n, const uint32_t* d_deleted, const uint32_t* d_filter, uint64_t stride, void* scratch,
+                              uint32_t* d_ids, float* d_dists, dann_search_stats* d_stats, hipStream_t stream);
 
 }  // namespace dann
 

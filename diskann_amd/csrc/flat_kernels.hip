@@ -121,24 +121,11 @@ __global__ __launch_bounds__(kFlatThreads) void flat_merge_kernel(IndexView ix, 
     uint8_t* const qslot = smem + (size_t)a.merge_cap * 8;
     const uint32_t qi = blockIdx.x, k = a.k, P = a.merge_cap;
     flat_stage_query<DT, OP>(ix, a.queries, qi, qslot);
-    // keys[0, k): the best so far; keys[k, P): the next P - k keys of the query's lists
-    const uint64_t* lists = a.lists + (uint64_t)qi * a.nchunks * k;
-    const uint64_t total = (uint64_t)a.nchunks * k;
-    for (uint32_t i = threadIdx.x; i < k; i += kFlatThreads) keys[i] = kNoKey;
-    for (uint64_t base = 0; base < total; base += P - k) {
-        for (uint32_t i = k + threadIdx.x; i < P; i += kFlatThreads) {
-            const uint64_t j = base + (i - k);
-            keys[i] = j < total ? lists[j] : kNoKey;
-        }
-        __syncthreads();
-        block_bitonic(keys, P, kFlatThreads);
-    }
-    __syncthreads();
+    flat_merge_rounds(keys, a.lists + (uint64_t)qi * a.nchunks * k, (uint64_t)a.nchunks * k, k, P);
     const SqParams sqp{ix.sq_k, ix.sq_shift_norm_sq};
     const QT* qs = reinterpret_cast<const QT*>(qslot + query_stage_off(DT));
     const int g = threadIdx.x / G, v = threadIdx.x % G;
     const uint64_t safe = (uint64_t)a.first;  // n > 0 here: a readable slot
-    uint32_t written = 0;
     for (uint32_t r0 = 0; r0 < k; r0 += GROUPS * kU) {
         const uint8_t* rows[kU];
         bool act[kU];
@@ -164,18 +151,8 @@ __global__ __launch_bounds__(kFlatThreads) void flat_merge_kernel(IndexView ix, 
             }
         }
     }
-    if (a.stats && threadIdx.x == 0) {
-        for (uint32_t r = 0; r < k; ++r) written += keys[r] != kNoKey ? 1u : 0u;
-        uint32_t cmps = 0;
-        for (uint32_t c = 0; c < a.nchunks; ++c) cmps += a.chunk_cmps[(uint64_t)qi * cmps_stride + c];
-        dann_search_stats st;
-        st.cmps = cmps;
-        st.hops = 0;
-        st.result_count = written;  // (no Translate post-processor on this path: min(k, rows inserted))
-        st.status = 0;
-        st.written = written;
-        a.stats[qi] = st;
-    }
+    if (a.stats && threadIdx.x == 0)
+        flat_merge_stats(a.stats + qi, keys, k, a.chunk_cmps + (uint64_t)qi * cmps_stride, a.nchunks);
 }
 
 // n == 0: nothing was scanned

@@ -689,6 +689,25 @@ int32_t launch_pq_pack(const IndexView& ix, uint8_t* d_pack, uint32_t stride, ui
     if (e != hipSuccess) return hip_fail(e, "pq_pack_kernel launch");
     return DANN_OK;
 }
+
+// pq_lut_kernel, device to device: the tables [nq][nchunks][256] of nq f32 queries of `dim` elements
+int32_t launch_pq_lut(int32_t metric, const float* d_pivots, const uint32_t* d_offsets, uint32_t nchunks, uint32_t dim,
+                      const float* d_queries, uint32_t nq, float* d_lut, hipStream_t stream) {
+    if (metric != M_L2 && metric != M_IP) {
+        set_error("PQ lookup tables exist for L2 and inner product only");
+        return DANN_EUNSUPPORTED;
+    }
+    const size_t lds = (size_t)dim * 4;
+    if (lds > 160 * 1024) {
+        set_error("a query of %u dimensions does not fit the LDS", dim);
+        return DANN_EUNSUPPORTED;
+    }
+    if (metric == M_L2)
+        return launch_kernel<pq_lut_kernel<true>>("pq_lut_kernel launch", dim3(nq), dim3(256), lds, stream, d_pivots, d_offsets,
+                                                  nchunks, dim, d_queries, d_lut);
+    return launch_kernel<pq_lut_kernel<false>>("pq_lut_kernel launch", dim3(nq), dim3(256), lds, stream, d_pivots, d_offsets,
+                                               nchunks, dim, d_queries, d_lut);
+}
 }  // namespace dann
 
 using namespace dann;

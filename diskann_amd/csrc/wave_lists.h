@@ -69,6 +69,12 @@ __device__ __forceinline__ uint64_t dist_key(float d, uint32_t payload) {
     return ((uint64_t)u << 32) | payload;
 }
 
+// the distance a key was made of; -0.0 comes back as +0.0, every other non-NaN value as its own bits
+__device__ __forceinline__ float key_dist(uint64_t key) {
+    const uint32_t u = (uint32_t)(key >> 32);
+    return __builtin_bit_cast(float, (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
+}
+
 // ascending bitonic sort of the 64-bit keys[0, P) in LDS, P a power of two, by one workgroup of `nthreads` threads (a
 // kernel that is only ever launched with one size names it: the stride is then a constant, not a load)
 template <class K>

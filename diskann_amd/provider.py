@@ -404,6 +404,36 @@ class Provider:
             check(_ffi.lib().dann_flat_filtered_search_batch_device(*args, C.byref(f), *outs),
                   "dann_flat_filtered_search_batch_device")
 
+    def pq_linear_search(self, queries, k, first=0, n=None, skip_deleted=False, stats=False, match=None):
+        """Exhaustive k-NN over the PQ code rows of the slots [first, first + n) (n None: the rest of the capacity, start
+        points not included) of a PQ index with its table: the reference's algos::linear_search.  Distances are the lookup-table
+        sums of the searches, bit for bit; the result is the first k rows under (distance ascending, slot descending).
+        match: as in flat_search.  Returns (ids[nq, k], dists[nq, k]), with stats=True also the SearchStats records."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        nq = q.shape[0]
+        n = self.capacity - first if n is None else n
+        ids = np.empty((nq, k), np.uint32)
+        dists = np.empty((nq, k), np.float32)
+        st = np.zeros(nq, STATS_DTYPE)
+        flags = _ffi.FLAT_SKIP_DELETED if skip_deleted else 0
+        f, keep = (None, None) if match is None else self._flat_filter(match, nq)
+        check(_ffi.lib().dann_pq_linear_search_batch(self._h, _p(q), nq, int(first), int(n), int(k), flags,
+                                                     C.byref(f) if f is not None else None, _p(ids), _p(dists),
+                                                     _p(st) if stats else None), "dann_pq_linear_search_batch")
+        del keep
+        return (ids, dists, st) if stats else (ids, dists)
+
+    def pq_linear_search_device(self, d_queries, nq, k, d_ids, d_dists, first=0, n=None, skip_deleted=False, d_stats=0, d_bits=0,
+                                stride_words=0):
+        """the same on device addresses (ints) of the index's device, shaped like flat_search_device; complete on return"""
+        n = self.capacity - first if n is None else n
+        flags = _ffi.FLAT_SKIP_DELETED if skip_deleted else 0
+        f = _ffi.FlatFilter(int(d_bits), int(stride_words)) if d_bits else None
+        check(_ffi.lib().dann_pq_linear_search_batch_device(
+            self._h, C.c_void_p(int(d_queries)), int(nq), int(first), int(n), int(k), flags,
+            C.byref(f) if f is not None else None, C.c_void_p(int(d_ids)), C.c_void_p(int(d_dists)),
+            C.c_void_p(int(d_stats)) if d_stats else None), "dann_pq_linear_search_batch_device")
+
     def flat_range_search(self, queries, radius, inner_radius=None, match=None, first=0, n=None, skip_deleted=False,
                           out_cap=None, stats=False):
         """Exhaustive range scan over the slots [first, first + n): per query every evaluated row with

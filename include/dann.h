@@ -405,6 +405,38 @@ int32_t dann_flat_range_search_batch_device(dann_index* idx, const void* d_queri
                                             uint32_t flags, const dann_flat_filter* d_filter, uint32_t out_cap,
                                             uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
                                             dann_search_stats* d_out_stats);
+/* Exhaustive k-NN over PQ code rows: the reference's product-exhaustive-search (diskann-benchmark/src/exhaustive/
+ * product.rs; algos::linear_search, exhaustive/algos.rs:42-99) for nq queries over the slots [first_slot, first_slot + n)
+ * of a DANN_PQ index with its table attached (dann_set_pq_table).  The queries are f32 vectors of dann_query_bytes()
+ * bytes, already centred or rotated by the caller, as for the searches.
+ * Distance: per query the lookup table table[c][b] = populate_chunk_distances_impl (fixed_chunk_pq_table.rs:152-192) for
+ * the index's metric (L2, or the inner product, negated), and d(q, slot) = ((+0.0 + table[0][code[0]]) + table[1][code[1]])
+ * + ... in f32, in chunk order (pq_dist_lookup_single, :82-100): bit for bit what the searches over a DANN_PQ index and
+ * dann_pq_build_lut + dann_pq_scan produce.  The sum is never -0.0.
+ * Selection: linear_search feeds every code row in ascending id order to NeighborPriorityQueue::insert on a queue of k
+ * entries (diskann/src/neighbor/queue.rs:130-171), the rule of dann_flat_search_batch: the result is the first k non-NaN
+ * rows under the strict total order (distance ascending, scan position descending), listed in that order.  Duplicate
+ * code rows tie exactly: the slot scanned later comes first, and wins the k-th place.
+ * Skipped rows: on an inline_tags index a slot whose tag is below Tag::PUBLISHED is skipped and not counted; with
+ * DANN_FLAT_SKIP_DELETED so is a slot marked by dann_delete_points.  filter (optional) has the meaning it has in
+ * dann_flat_filtered_search_batch -- a shared or per-query bitmap over slot ids, NULL or null bits = every slot; a
+ * non-zero stride below ceil((capacity + num_start_points) / 32) is DANN_EINVAL -- and a query evaluates only the slots its
+ * bitmap holds.  A call with an all-ones filter is equal to one without in every output.
+ * out_ids / out_dists: nq x k, the places behind the last result hold 0xFFFFFFFF / +infinity (linear_search pads with
+ * u32::MAX).  out_stats (optional): cmps = rows evaluated and accepted for the query (those with a NaN distance included),
+ * hops = 0, result_count = written = min(k, rows inserted).
+ * Errors: DANN_EUNSUPPORTED for an index that is not DANN_PQ or for k > 1024; DANN_EINVAL for an index without a pivot
+ * table, k == 0, a null pointer with nq > 0, an unknown flag bit or a short filter stride; DANN_EBOUNDS when the range
+ * leaves [0, capacity + num_start_points).  nq == 0 writes nothing; with n == 0 every result is empty.  Every chunk count
+ * an index accepts is served.  The results do not depend on how the scan is cut up, nor on the run. */
+int32_t dann_pq_linear_search_batch(dann_index* idx, const float* queries, uint32_t nq, uint32_t first_slot, uint32_t n,
+                                    uint32_t k, uint32_t flags, const dann_flat_filter* filter, uint32_t* out_ids,
+                                    float* out_dists, dann_search_stats* out_stats);
+/* device-pointer form (queries, bitmaps and outputs on the index's device, the dann_flat_filter itself in host memory;
+ * complete on return) */
+int32_t dann_pq_linear_search_batch_device(dann_index* idx, const float* d_queries, uint32_t nq, uint32_t first_slot,
+                                           uint32_t n, uint32_t k, uint32_t flags, const dann_flat_filter* d_filter,
+                                           uint32_t* d_out_ids, float* d_out_dists, dann_search_stats* d_out_stats);
 /* insert-time search: also returns the VisitedSearchRecord (record.rs:86-93) per query:
  * rec_ids/rec_dists: nq x rec_stride, rec_n: nq */
 int32_t dann_search_record_batch(dann_index* idx, const uint32_t* slots, uint32_t nq, uint32_t l_value,
