@@ -15,7 +15,7 @@ SQ1, SQ4 = 17, 20  # packed scalar-quantised rows: 16 + bits
 SPH1, SPH2, SPH4 = 33, 34, 36  # spherically quantised rows (RaBitQ): 32 + bits
 # dann_query_layout (iface::QueryLayout): the byte image of a spherical index's queries
 QUERY_SAME_AS_DATA, QUERY_FOUR_BIT_TRANSPOSED, QUERY_SCALAR_QUANTIZED, QUERY_FULL_PRECISION = 0, 1, 2, 3
-QUERY_EIGHT_BIT = 8  # MinMaxQuery::EightBit: reserved (DANN_EUNSUPPORTED)
+QUERY_EIGHT_BIT = 8  # MinMaxQuery::EightBit: set with dann_set_query_dtype(MM8), never with dann_set_query_layout
 MM1, MM2, MM4, MM8 = 49, 50, 52, 56  # MinMax-quantised rows: 48 + bits
 COSINE, INNER_PRODUCT, L2, COSINE_NORMALIZED = 0, 1, 2, 3
 OK, EINVAL, ELENGTH, EBOUNDS, ETOOLONG, EHIP, ENOMEM, EOVERFLOW, EUNSUPPORTED, EINTERNAL, EBUSY = (
@@ -218,6 +218,8 @@ SYMBOLS = {
     "dann_set_query_layout": (_i32, [_vp, _i32]),
     "dann_get_query_layout": (_i32, [_vp]),
     "dann_query_bytes": (_i32, [_vp]),
+    "dann_set_query_dtype": (_i32, [_vp, _i32]),
+    "dann_get_query_dtype": (_i32, [_vp, _P(_i32)]),
     "dann_sq8_train": (_i32, [_i32, _vp, _u64, _u32, C.c_double, _vp, _vp, _vp]),
     "dann_sq8_compress": (_i32, [_i32, _vp, _u32, _u32, _vp, _f32, _vp]),
     "dann_sq_compress": (_i32, [_i32, _i32, _vp, _u32, _u32, _vp, _f32, _vp]),

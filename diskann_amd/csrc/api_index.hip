@@ -142,9 +142,16 @@ dann::IndexView dann_index::view() const {
 // The view of the entry points that take queries.  Spherical rows: the query's byte image follows the layout
 // (iface::QueryLayout) -- FOUR_BIT_TRANSPOSED has an inner-product routine of its own and therefore a row type of its
 // own inside the kernels (DT_SPH1T); SCALAR_QUANTIZED shares the symmetric routine and differs in the epilogue, which
-// SqParams::k != 0 selects at run time.
+// SqParams::k != 0 selects at run time.  MinMax rows: QL_EIGHT_BIT (dann_set_query_dtype) says the queries are MM8 images.
 dann::IndexView dann_index::qview(int32_t layout) const {
     IndexView v = view();
+    if (layout == QL_EIGHT_BIT && dt_is_mm(cfg.dtype) && cfg.dtype != DT_MM8) {
+        // MinMax rows searched with MM8 images (dann_set_query_dtype): an inner-product routine and a staged form of
+        // their own, therefore internal row types; the epilogue reads the two headers as ever
+        v.dtype = cfg.dtype - DT_MM1 + DT_MM1Q;
+        v.qbytes = kMmHeader + cfg.dim;
+        return v;
+    }
     if (!dt_is_sph(cfg.dtype)) return v;
     v.qbytes = sph_query_bytes(cfg.dtype, cfg.dim, layout);
     if (layout == QL_TRANSPOSED) v.dtype = DT_SPH1T;
@@ -154,7 +161,12 @@ dann::IndexView dann_index::qview(int32_t layout) const {
 dann::IndexView dann_index::qview() const { return qview(query_layout.load(std::memory_order_relaxed)); }
 uint32_t dann_index::query_bytes() const {
     if (cfg.dtype == DT_PQ) return cfg.dim * 4u;  // PQ rows: f32 queries
-    if (dt_is_sph(cfg.dtype)) return sph_query_bytes(cfg.dtype, cfg.dim, query_layout.load(std::memory_order_relaxed));
+    return query_bytes(query_layout.load(std::memory_order_relaxed));
+}
+uint32_t dann_index::query_bytes(int32_t layout) const {
+    if (cfg.dtype == DT_PQ) return cfg.dim * 4u;
+    if (dt_is_sph(cfg.dtype)) return sph_query_bytes(cfg.dtype, cfg.dim, layout);
+    if (layout == QL_EIGHT_BIT && dt_is_mm(cfg.dtype)) return kMmHeader + cfg.dim;  // an MM8 image
     return layer_bytes;
 }
 
@@ -514,7 +526,7 @@ int32_t dann_set_pq_table(dann_index* idx, const float* pivots, const uint32_t* 
 // ---- query layout of spherical indexes (iface::QueryLayout) ---------------------------------------------------------
 int32_t dann_set_query_layout(dann_index* idx, int32_t layout) try {
     CHECK_IDX(idx);
-    if (layout == QL_EIGHT_BIT) {  // MinMaxQuery::EightBit (an MM8 image against narrower MinMax rows): not served
+    if (layout == QL_EIGHT_BIT) {  // MinMaxQuery::EightBit is set with dann_set_query_dtype(idx, DANN_MM8), never here
         set_error("query layout %d is not supported for dtype %d", layout, idx->cfg.dtype);
         return DANN_EUNSUPPORTED;
     }
@@ -534,6 +546,45 @@ int32_t dann_set_query_layout(dann_index* idx, int32_t layout) try {
         return DANN_EUNSUPPORTED;
     }
     idx->query_layout.store(layout, std::memory_order_relaxed);
+    return DANN_OK;
+} DANN_CATCH_ALL
+
+// ---- query dtype of MinMax indexes (MinMaxQuery::EightBit) -----------------------------------------------------------
+// Kept in query_layout as QL_EIGHT_BIT, which dann_set_query_layout never stores: one word says what a query image is.
+int32_t dann_set_query_dtype(dann_index* idx, int32_t dtype) try {
+    CHECK_IDX(idx);
+    const int32_t own = idx->cfg.dtype;
+    if (dtype != own) {
+        if (!dt_is_mm(dtype) || !dt_is_mm(own)) {
+            set_error("dann_set_query_dtype: dtype %d is no query dtype of an index of dtype %d", dtype, own);
+            return DANN_EINVAL;
+        }
+        if (dtype != DT_MM8) {  // the reference's mixed pairs are (8, 4), (8, 2), (8, 1)
+            set_error("dann_set_query_dtype: queries of dtype %d against rows of dtype %d are not supported", dtype, own);
+            return DANN_EUNSUPPORTED;
+        }
+        // the raw product of kernel::<8, M> is a u32 (minmax/vectors.rs:216-222)
+        if ((uint64_t)idx->cfg.dim * 255u * ((1u << sq_bits(own)) - 1u) > 0xFFFFFFFFull) {
+            set_error("dim %u: the inner product of an 8-bit query and a %d-bit MinMax row does not fit a u32", idx->cfg.dim,
+                      sq_bits(own));
+            return DANN_EINVAL;
+        }
+    }
+    if (idx->server.load(std::memory_order_acquire)) {  // the resident kernel was sized and instantiated for a query form
+        set_error("dann_set_query_dtype: stop the search server first");
+        return DANN_EBUSY;
+    }
+    if (dt_is_mm(own)) idx->query_layout.store(dtype == own ? QL_SAME : QL_EIGHT_BIT, std::memory_order_relaxed);
+    return DANN_OK;
+} DANN_CATCH_ALL
+
+int32_t dann_get_query_dtype(const dann_index* idx, int32_t* out) try {
+    if (!idx || !out) {
+        set_error("null argument");
+        return DANN_EINVAL;
+    }
+    const bool q8 = dt_is_mm(idx->cfg.dtype) && idx->query_layout.load(std::memory_order_relaxed) == QL_EIGHT_BIT;
+    *out = q8 ? DT_MM8 : idx->cfg.dtype;
     return DANN_OK;
 } DANN_CATCH_ALL
 

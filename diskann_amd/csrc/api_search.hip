@@ -98,7 +98,7 @@ int32_t dann_query_create(const dann_index* idx, const void* query, uint64_t len
     if (!query || !out) return DANN_EINVAL;
     *out = nullptr;
     const int32_t layout = idx->query_layout.load(std::memory_order_relaxed);
-    const uint32_t want = dt_is_sph(idx->cfg.dtype) ? sph_query_bytes(idx->cfg.dtype, idx->cfg.dim, layout) : idx->layer_bytes;
+    const uint32_t want = idx->cfg.dtype == DT_PQ ? idx->layer_bytes : idx->query_bytes(layout);
     if (len != want) {  // Full::check_dim (full.rs:86-99)
         set_error("query of %llu bytes does not match the layer's %u bytes", (unsigned long long)len, want);
         return DANN_ELENGTH;

@@ -26,7 +26,7 @@
 namespace dann {
 
 __host__ __device__ constexpr int sq_bits(int dt) {
-    return dt == DT_SQ8 ? 8 : dt_is_sph(dt) ? (dt & 7) : dt_is_mm(dt) ? dt - 48 : dt - 16;
+    return dt == DT_SQ8 ? 8 : dt_is_sph(dt) ? (dt & 7) : dt_is_mm(dt) ? dt - 48 : dt_is_mmq(dt) ? dt - 112 : dt - 16;  // (DT_MM*Q: the rows' bits)
 }
 // query layouts of spherical rows (iface::QueryLayout; dann.h DANN_QUERY_*)
 enum : int { QL_SAME = 0, QL_TRANSPOSED = 1, QL_SCALAR = 2, QL_FULL = 3, QL_EIGHT_BIT = 8 };
@@ -1184,6 +1184,121 @@ __device__ __forceinline__ void group_ip_mm_pre(const uint4& x, const uint8_t* c
     }
 }
 
+// ---- MinMax rows of 4, 2 or 1 bit searched with MM8 query images (MinMaxQuery::EightBit: the heterogeneous
+// kernel::<8, M>, minmax/vectors.rs:206-229, whose raw product is a u32 -- exact, so any lane assignment is
+// bit-identical).  The row side is group_ip_mm's: the same 4-lane group, the same loads, the same tail rule, 128
+// elements per step at every width.  Only the query operand differs: one byte per element, 32 bytes per lane and step,
+// staged once per query (mmq_stage_query) in the order the row's dwords are taken apart in:
+//   4 bit  a row dword holds 8 elements; `& 0x0F0F0F0F` leaves the even ones in its four bytes, `>> 4 &` the odd ones.
+//          Staged per 8 elements: the four even query bytes, then the four odd ones -- two v_dot4_u32_u8 per row dword;
+//   2 bit  a row dword holds 16 elements; `>> 2 s & 0x03030303` leaves elements s, s + 4, s + 8, s + 12.  Staged per 16
+//          elements: dword s = query bytes s, s + 4, s + 8, s + 12 (a 4 x 4 transpose) -- four dots per row dword;
+//   1 bit  a row dword holds 32 elements.  Staged per 32 elements: eight plane dwords, plane j = bit j of the 32 query
+//          bytes; <q, y> = sum_j 2^j popcount(plane_j & y) (v_bcnt_u32_b32), as FOUR_BIT_TRANSPOSED does with four.
+// The staged codes start where the image's do (slot + 32, 16-byte aligned) and a lane's 32 bytes at a multiple of 32:
+// two ds_read_b128 per full step.  Elements at or beyond dim are staged as zero, so whatever the row holds in its
+// padding bits, or in the dword a clamped tail load fetched instead, meets a zero; the row needs no mask.
+template <int MBITS>
+__device__ __forceinline__ void mmq_stage_query(uint8_t* qs, const uint8_t* src, uint32_t dim, uint32_t tid, uint32_t nthreads) {
+    static_assert(MBITS == 4 || MBITS == 2 || MBITS == 1, "rows narrower than the 8-bit query");
+    for (uint32_t i = tid; i < kMmHeader; i += nthreads) qs[i] = src[i];
+    const uint8_t* c = src + kMmHeader;  // exactly dim bytes are read
+    uint32_t* out = reinterpret_cast<uint32_t*>(qs + kMmHeader);
+    const uint32_t nd = MBITS == 1 ? ((dim + 31u) >> 5) * 8u : ((dim + 15u) >> 4) * 4u;  // staged dwords (mm_slot_bytes)
+    for (uint32_t w = tid; w < nd; w += nthreads) {
+        uint32_t val = 0u;
+        if constexpr (MBITS == 1) {
+            const uint32_t e0 = (w >> 3) * 32u, j = w & 7u;
+            for (uint32_t i = 0; i < 32u; ++i)
+                if (e0 + i < dim) val |= (((uint32_t)c[e0 + i] >> j) & 1u) << i;
+        } else {
+#pragma unroll
+            for (uint32_t b = 0; b < 4u; ++b) {
+                const uint32_t e = MBITS == 4 ? (w >> 1) * 8u + 2u * b + (w & 1u) : (w >> 2) * 16u + (w & 3u) + 4u * b;
+                if (e < dim) val |= (uint32_t)c[e] << (8u * b);
+            }
+        }
+        out[w] = val;
+    }
+}
+// acc + the products of one row dword's fields with their staged query dwords `q` (2, 4 or 8 of them)
+template <int MBITS>
+__device__ __forceinline__ uint32_t mmq_dot(const uint32_t* q, uint32_t y, uint32_t acc) {
+    if constexpr (MBITS == 4) {
+        acc = __builtin_amdgcn_udot4(q[0], y & 0x0F0F0F0Fu, acc, false);
+        return __builtin_amdgcn_udot4(q[1], (y >> 4) & 0x0F0F0F0Fu, acc, false);
+    } else if constexpr (MBITS == 2) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_udot4(q[s], (y >> (2 * s)) & 0x03030303u, acc, false);
+        return acc;
+    } else {
+        uint32_t h = (uint32_t)__builtin_popcount(q[7] & y);
+#pragma unroll
+        for (int j = 6; j >= 0; --j) h = (h << 1) + (uint32_t)__builtin_popcount(q[j] & y);
+        return acc + h;
+    }
+}
+// `x` is the staged query (the header, then the staged codes), the rows are images in global memory
+template <int MBITS, int U>
+__device__ __forceinline__ void group_ip_mmq(const uint8_t* __restrict__ x, const uint8_t* const (&rows)[U], int dim, int v,
+                                             float (&out)[U]) {
+    using P = MmShape<MBITS>;
+    constexpr int NW = P::NW, QW = 8 / MBITS, QPB = 8 / MBITS;  // query dwords per row dword; query bytes per row byte
+    static_assert(NW * QW == 8, "a lane's step is 32 query bytes");
+    const int total_bits = dim * MBITS, cb = (total_bits + 7) >> 3;
+    const uint8_t* xc = x + kMmHeader;
+    uint32_t t[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) t[u] = 0u;
+    int o0 = 0;
+    for (; 8 * (o0 + P::STEP) <= total_bits; o0 += P::STEP) {
+        const int o = o0 + P::LB * v;
+        PWords<NW> y[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) y[u] = mm_load<NW, 4>(rows[u] + kMmHeader + o);
+        const PWords<8> xw = mm_load<8, 16>(xc + QPB * o);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+            for (int i = 0; i < NW; ++i) t[u] = mmq_dot<MBITS>(&xw.w[QW * i], y[u].w[i], t[u]);
+        }
+    }
+    if (8 * o0 < total_bits) {
+        const int o = o0 + P::LB * v;
+        PWords<NW> y[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) y[u] = mm_load_tail<NW>(rows[u] + kMmHeader, o, cb);  // (beyond cb: the first code dword)
+        // the query dwords of a row dword that starts below cb lie inside the staged codes; of one beyond it: zeros
+        PWords<8> xw;
+#pragma unroll
+        for (int i = 0; i < NW; ++i) {
+            const int oi = o + 4 * i;
+            const bool in = oi < cb;
+            const PWords<QW> part = mm_load<QW, (QW >= 4 ? 16 : 8)>(xc + (in ? QPB * oi : 0));
+#pragma unroll
+            for (int j = 0; j < QW; ++j) xw.w[QW * i + j] = in ? part.w[j] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+            for (int i = 0; i < NW; ++i) t[u] = mmq_dot<MBITS>(&xw.w[QW * i], y[u].w[i], t[u]);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) out[u] = mm_group_sum<MBITS>(t[u]);
+}
+// stages query `src` (ix.qbytes bytes) of integer rows at `qs` = slot + query_stage_off(DT): the bytes as they are, or, for
+// MinMax rows searched with MM8 images, the form group_ip_mmq reads.  Every kernel that stages such a query calls this.
+template <int DT>
+__device__ __forceinline__ void stage_int_query(uint8_t* qs, const uint8_t* src, uint32_t qbytes, uint32_t dim, uint32_t tid,
+                                                uint32_t nthreads) {
+    if constexpr (dt_is_mmq(DT)) {
+        mmq_stage_query<sq_bits(DT)>(qs, src, dim, tid, nthreads);
+    } else {
+        for (uint32_t i = tid; i < qbytes; i += nthreads) qs[i] = src[i];
+    }
+}
+
 // ---- dtype dispatch ------------------------------------------------------------------
 // Query-side staging type and group width for the *search* path
 // (Full<T>::query_distance, diskann-inmem/src/layers/full.rs:351-504):
@@ -1194,7 +1309,7 @@ __device__ __forceinline__ void group_ip_mm_pre(const uint4& x, const uint8_t* c
 //   f16 x f16: L2/IP/cosine all Strategy2x4 (NACC 2)  (simd.rs:989,1752,2591)
 template <int DT, int OP, bool PAIR>
 struct Scheme {
-    static constexpr bool kInt = (DT == DT_U8 || DT == DT_I8 || DT == DT_PQ || dt_is_sq(DT) || dt_is_sph(DT) || dt_is_mm(DT));
+    static constexpr bool kInt = (DT == DT_U8 || DT == DT_I8 || DT == DT_PQ || dt_is_sq(DT) || dt_is_sph(DT) || dt_mm_rows(DT));
     static constexpr int NACC = (OP == OP_COS) ? 2 : ((DT == DT_F16 && PAIR) ? 2 : 4);
     static constexpr int G = dt_is_packed(DT) ? 4 : kInt ? 8 : 2 * NACC;  // (packed rows: PackedShape::G)
     // search-path gather: 2-byte rows use the wide layout (one lane per accumulator)
@@ -1263,6 +1378,18 @@ struct RowType<DT_MM8> {
     using type = uint8_t;
 };
 template <>
+struct RowType<DT_MM1Q> {
+    using type = uint8_t;
+};
+template <>
+struct RowType<DT_MM2Q> {
+    using type = uint8_t;
+};
+template <>
+struct RowType<DT_MM4Q> {
+    using type = uint8_t;
+};
+template <>
 struct RowType<DT_PQ> {
     using type = uint8_t;
 };
@@ -1270,7 +1397,12 @@ struct RowType<DT_PQ> {
 // `q` is the staged query: f32 for float rows, raw bytes for integer rows.
 template <int DT, int OP, bool PAIR, int DIM, typename QT>
 __device__ __forceinline__ float group_distance(const QT* q, const uint8_t* row, int dim, int v) {
-    if constexpr (dt_is_mm(DT)) {  // (q: the image staged at slot + 12, codes 16-byte aligned)
+    if constexpr (dt_is_mmq(DT)) {  // (q: the MM8 image staged by mmq_stage_query)
+        const uint8_t* const rows[1] = {row};
+        float out[1];
+        group_ip_mmq<sq_bits(DT), 1>(reinterpret_cast<const uint8_t*>(q), rows, dim, v, out);
+        return out[0];
+    } else if constexpr (dt_is_mm(DT)) {  // (q: the image staged at slot + 12, codes 16-byte aligned)
         return group_ip_mm1<sq_bits(DT), MmShape<sq_bits(DT)>::LB>(reinterpret_cast<const uint8_t*>(q), row, dim, v);
     } else if constexpr (dt_is_sph(DT)) {
         return group_ip_sph1<DT>(reinterpret_cast<const uint8_t*>(q), row, dim, v);
@@ -1288,6 +1420,7 @@ __device__ __forceinline__ float group_distance(const QT* q, const uint8_t* row,
 // stored row x stored row with the prune-path association (Scheme<DT, OP, true>)
 template <int DT, int OP>
 __device__ __forceinline__ float group_distance_rows(const uint8_t* x, const uint8_t* y, int dim, int v) {
+    static_assert(!dt_is_mmq(DT), "row x row distances have no query form");
     if constexpr (dt_is_mm(DT)) {  // (both operands are rows in global memory: 4-byte aligned codes)
         return group_ip_mm1<sq_bits(DT), 4>(x, y, dim, v);
     } else if constexpr (dt_is_sph(DT)) {  // (a stored row as the query is always the symmetric form)
@@ -1310,7 +1443,9 @@ __device__ __forceinline__ float group_distance_rows(const uint8_t* x, const uin
 template <int DT, int OP, bool PAIR, int U, bool WIDE = true, typename QT>
 __device__ __forceinline__ void group_distance_many(const QT* q, const uint8_t* const (&rows)[U],
                                                     const bool (&active)[U], int dim, int v, float (&out)[U]) {
-    if constexpr (dt_is_mm(DT)) {
+    if constexpr (dt_is_mmq(DT)) {
+        group_ip_mmq<sq_bits(DT), U>(reinterpret_cast<const uint8_t*>(q), rows, dim, v, out);
+    } else if constexpr (dt_is_mm(DT)) {
         group_ip_mm<sq_bits(DT), U, MmShape<sq_bits(DT)>::LB>(reinterpret_cast<const uint8_t*>(q), rows, dim, v, out);
     } else if constexpr (dt_is_sph(DT)) {
         group_ip_sph<DT, U>(reinterpret_cast<const uint8_t*>(q), rows, dim, v, out);
@@ -1457,7 +1592,7 @@ __device__ __forceinline__ float finish_minmax(float raw, const uint8_t* x, cons
 template <int DT, int OP, bool NORM>
 __device__ __forceinline__ float finish_distance(float raw, const uint8_t* x, const uint8_t* y, uint32_t dim,
                                                  const SqParams& sq) {
-    if constexpr (dt_is_mm(DT)) {
+    if constexpr (dt_mm_rows(DT)) {
         return finish_minmax<OP, NORM>(raw, x, y, dim);
     } else if constexpr (dt_is_sph(DT)) {
         return finish_spherical<DT, OP>(raw, x, y, dim, sq);

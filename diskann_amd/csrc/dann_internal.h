@@ -158,6 +158,9 @@ DANN_DECL_LAUNCH(mm1);
 DANN_DECL_LAUNCH(mm2);
 DANN_DECL_LAUNCH(mm4);
 DANN_DECL_LAUNCH(mm8);
+DANN_DECL_LAUNCH(mm1q);
+DANN_DECL_LAUNCH(mm2q);
+DANN_DECL_LAUNCH(mm4q);
 DANN_DECL_LAUNCH(pq);
 // search_diverse.hip: dann_diverse_search_batch on device-resident queries and outputs (host-synchronous on `stream`)
 int32_t diverse_search_device(dann_index* idx, hipStream_t stream, const void* d_queries, uint32_t nq, uint32_t l_value,
@@ -404,7 +407,9 @@ struct dann_index {
     std::atomic<uint32_t> mutating{0};
     // spherical rows: iface::QueryLayout of the queries the entry points take (dann_set_query_layout)
     std::atomic<int32_t> query_layout{0};
+    // (MinMax rows: QL_EIGHT_BIT says that the queries are MM8 images, dann_set_query_dtype)
     uint32_t query_bytes() const;  // bytes of one query of the query-taking entry points under the current layout
+    uint32_t query_bytes(int32_t layout) const;
     dann::IndexView view() const;  // row x row work: a stored row as the query is always the symmetric form
     dann::IndexView qview() const;               // the query-taking entry points: the current layout
     dann::IndexView qview(int32_t layout) const;

@@ -38,7 +38,7 @@ __device__ __forceinline__ void flat_stage_query(const IndexView& ix, const void
     const uint8_t* qsrc = reinterpret_cast<const uint8_t*>(queries) + (uint64_t)qi * ix.qbytes;
     uint8_t* qs = slot + query_stage_off(DT);
     if constexpr (S::kInt) {
-        for (uint32_t i = threadIdx.x; i < ix.qbytes; i += blockDim.x) qs[i] = qsrc[i];
+        stage_int_query<DT>(qs, qsrc, ix.qbytes, ix.dim, threadIdx.x, blockDim.x);
     } else {
         const RT* src = reinterpret_cast<const RT*>(qsrc);
         for (uint32_t i = threadIdx.x; i < ix.dim; i += blockDim.x) reinterpret_cast<float*>(qs)[i] = load1(src + i);

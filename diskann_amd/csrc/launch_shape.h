@@ -35,7 +35,7 @@ DANN_HD inline uint32_t lds_queue_entries(const SearchArgs& a) {
 DANN_HD inline uint32_t query_lds_bytes(const IndexView& ix) {
     if (ix.dtype == DT_PQ) return ix.pq_chunks * 1024u;
     if (ix.dtype == DT_U8 || ix.dtype == DT_I8 || dt_is_sq(ix.dtype) || dt_is_sph(ix.dtype)) return ix.qbytes;
-    if (dt_is_mm(ix.dtype)) return mm_query_lds_bytes(ix.qbytes);
+    if (dt_mm_rows(ix.dtype)) return mm_slot_bytes(ix.dtype, ix.qbytes);
     return ix.dim * 4u;
 }
 
@@ -97,7 +97,7 @@ inline bool team_shape(const SearchArgs& a) {
     int op;
     bool norm;
     const int dt = a.ix.dtype;
-    if (!plain_mode(a) || dt == DT_PQ || dt_is_packed(dt) || dt_is_mm(dt) || a.ix.dim != 128u || !resolve_metric(dt, a.ix.metric, &op, &norm)) return false;
+    if (!plain_mode(a) || dt == DT_PQ || dt_is_packed(dt) || dt_mm_rows(dt) || a.ix.dim != 128u || !resolve_metric(dt, a.ix.metric, &op, &norm)) return false;
     if (std::max(a.l_value + a.ix.nstart, a.qcap_max) > 256u) return false;
     const bool ints = dt == DT_U8 || dt == DT_I8 || dt == DT_SQ8;
     if (op == OP_L2) return true;

@@ -11,14 +11,14 @@ namespace dann {
 constexpr bool row_op_defined(int dt, int op, bool norm) {
     if (dt == DT_PQ) return !norm && (op == OP_L2 || op == OP_IP);
     if (op == OP_L2) return !norm || dt_is_sq(dt);
-    if (op == OP_IP) return !norm || dt == DT_F32 || dt == DT_F16 || dt_is_mm(dt);
+    if (op == OP_IP) return !norm || dt == DT_F32 || dt == DT_F16 || dt_mm_rows(dt);
     return op == OP_COS && !norm && !dt_is_sq(dt);
 }
 
 // beam search also has a form with the row length fixed at 128 elements: under L2 for every row type but PQ, under the
-// inner product and Cosine for every row type but PQ and the float rows
+// inner product and Cosine for every row type but PQ and the float rows; MinMax rows searched with MM8 queries have none
 constexpr bool search_dim128_defined(int dt, int op) {
-    return dt != DT_PQ && (op == OP_L2 || (dt != DT_F32 && dt != DT_F16));
+    return dt != DT_PQ && !dt_is_mmq(dt) && (op == OP_L2 || (dt != DT_F32 && dt != DT_F16));
 }
 
 // what a visitor hands its functor: read the constants as decltype(r)::dt
@@ -60,15 +60,16 @@ int32_t visit_metric(int metric, F&& f) {
 // The row types an entry point serves:
 //   kRowsStored  the 14 row types an index stores -- entry points that take no query (prune, consolidate, in-place
 //                delete, distances between stored or raw rows)
-//   kRowsQuery   plus DT_SPH1T, the transposed query layout of DT_SPH1 rows -- entry points that take a query (rerank,
-//                expand-beam, paged and diverse search)
+//   kRowsQuery   plus DT_SPH1T, the transposed query layout of DT_SPH1 rows, and DT_MM1Q / MM2Q / MM4Q, MinMax rows
+//                searched with MM8 queries -- entry points that take a query (rerank, expand-beam, paged and diverse
+//                search, the flat scans)
 //   kRowsSearch  plus DT_PQ, which only beam search serves
 //   kRowsFloat   f32 / f16, the MFMA pool prune;  kRowsPair  one-byte codes, two queries per wavefront
 enum RowSet { kRowsStored, kRowsQuery, kRowsSearch, kRowsFloat, kRowsPair };
 constexpr bool row_in_set(RowSet s, int dt) {
     if (s == kRowsFloat) return dt == DT_F32 || dt == DT_F16;
     if (s == kRowsPair) return dt == DT_U8 || dt == DT_I8 || dt == DT_SQ8;
-    if (dt == DT_SPH1T) return s == kRowsQuery || s == kRowsSearch;
+    if (dt == DT_SPH1T || dt_is_mmq(dt)) return s == kRowsQuery || s == kRowsSearch;
     if (dt == DT_PQ) return s == kRowsSearch;
     return dt == DT_F32 || dt == DT_F16 || dt == DT_U8 || dt == DT_I8 || dt_is_sq(dt) || dt_is_sph(dt) || dt_is_mm(dt);
 }
@@ -83,7 +84,7 @@ int32_t visit_row_op(int dtype, int metric, F&& f) {
         break;
         DANN_ROW(DT_F32) DANN_ROW(DT_F16) DANN_ROW(DT_U8) DANN_ROW(DT_I8) DANN_ROW(DT_SQ8) DANN_ROW(DT_SQ4) DANN_ROW(DT_SQ1)
         DANN_ROW(DT_SPH1) DANN_ROW(DT_SPH2) DANN_ROW(DT_SPH4) DANN_ROW(DT_MM1) DANN_ROW(DT_MM2) DANN_ROW(DT_MM4)
-        DANN_ROW(DT_MM8) DANN_ROW(DT_SPH1T) DANN_ROW(DT_PQ)
+        DANN_ROW(DT_MM8) DANN_ROW(DT_SPH1T) DANN_ROW(DT_MM1Q) DANN_ROW(DT_MM2Q) DANN_ROW(DT_MM4Q) DANN_ROW(DT_PQ)
 #undef DANN_ROW
     }
     return kNoRow;

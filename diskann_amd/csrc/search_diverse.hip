@@ -105,7 +105,7 @@ __global__ __launch_bounds__(kWave) void diverse_search_kernel(DiverseArgs a) {
     {
         const uint8_t* qsrc = reinterpret_cast<const uint8_t*>(a.queries) + (uint64_t)qi * ix.qbytes;
         if constexpr (kInt) {
-            for (uint32_t i = lane; i < ix.qbytes; i += kWave) reinterpret_cast<uint8_t*>(qs)[i] = qsrc[i];
+            stage_int_query<DT>(reinterpret_cast<uint8_t*>(qs), qsrc, ix.qbytes, ix.dim, lane, kWave);
         } else {
             const RT* src = reinterpret_cast<const RT*>(qsrc);
             for (uint32_t i = lane; i < ix.dim; i += kWave) reinterpret_cast<float*>(qs)[i] = load1(src + i);

@@ -1081,7 +1081,7 @@ __device__ __forceinline__ void beam_search_one(const SearchArgs& a, const uint3
         const uint8_t* qsrc = a.qslots ? ix.rows + (uint64_t)a.qslots[qi] * ix.row_stride
                                        : reinterpret_cast<const uint8_t*>(a.queries) + (uint64_t)qi * ix.qbytes;
         if constexpr (kInt) {
-            for (uint32_t i = lane; i < ix.qbytes; i += kWave) reinterpret_cast<uint8_t*>(qs)[i] = qsrc[i];
+            stage_int_query<DT>(reinterpret_cast<uint8_t*>(qs), qsrc, ix.qbytes, ix.dim, lane, kWave);
         } else {
             const RT* src = reinterpret_cast<const RT*>(qsrc);
             for (uint32_t i = lane; i < ix.dim; i += kWave) reinterpret_cast<float*>(qs)[i] = load1(src + i);
@@ -2501,7 +2501,7 @@ constexpr int kTeam = DANN_TEAM_WAVES;  // wavefronts per query in the latency r
 
 template <int DT, int OP, bool NORM, int QS, int DIM, int MODE, int LOOP = 0, int TEAM = 1, bool HT16 = false>
 int32_t launch_one(const SearchArgs& a, size_t lds, hipStream_t stream, int* regs_out) {
-    if constexpr (MODE == kModePlain && LOOP == 0 && TEAM == 1 && DIM > 0 && QS <= 4 && DT != DT_PQ && !dt_is_packed(DT) && !dt_is_mm(DT)) {
+    if constexpr (MODE == kModePlain && LOOP == 0 && TEAM == 1 && DIM > 0 && QS <= 4 && DT != DT_PQ && !dt_is_packed(DT) && !dt_mm_rows(DT)) {
         if (a.team && !a.srv.ring && !a.grid && !regs_out)
             return launch_one<DT, OP, NORM, QS, DIM, MODE, 0, kTeam>(a, lds, stream, regs_out);
     }

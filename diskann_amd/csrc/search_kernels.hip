@@ -72,6 +72,9 @@ int32_t launch_search(const SearchArgs& a, hipStream_t stream, int* regs_out) {
         case DT_MM2: return launch_search_mm2(a, qcap, lds, stream, regs_out);
         case DT_MM4: return launch_search_mm4(a, qcap, lds, stream, regs_out);
         case DT_MM8: return launch_search_mm8(a, qcap, lds, stream, regs_out);
+        case DT_MM1Q: return launch_search_mm1q(a, qcap, lds, stream, regs_out);
+        case DT_MM2Q: return launch_search_mm2q(a, qcap, lds, stream, regs_out);
+        case DT_MM4Q: return launch_search_mm4q(a, qcap, lds, stream, regs_out);
         case DT_PQ: return launch_search_pq(a, qcap, lds, stream, regs_out);
     }
     set_error("bad dtype %d", a.ix.dtype);

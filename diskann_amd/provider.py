@@ -52,7 +52,7 @@ class PagedSearch:
     """graph::search::PagedSearch (diskann/src/graph/search/paged.rs) for nq queries."""
 
     def __init__(self, provider, queries, l_value, list_cap=0):
-        q = np.ascontiguousarray(queries, dtype=provider.query_dtype).reshape(-1, provider.query_elems)
+        q = np.ascontiguousarray(queries, dtype=provider.query_np_dtype).reshape(-1, provider.query_elems)
         self.nq = q.shape[0]
         self._h = C.c_void_p()
         self._provider = provider  # keeps the index alive
@@ -90,13 +90,13 @@ class Provider:
         # (spherical); MinMax rows: the 20-byte MinMaxCompensation, then the code bytes
         self.row_elems = (int(_ffi.lib().dann_layer_bytes(dtype, self.dim))
                           if dtype in (SQ8, SQ4, SQ1, SPH1, SPH2, SPH4, MM1, MM2, MM4, MM8) else self.dim)
-        self.query_dtype, self.query_elems = NP_DTYPE[dtype], self.row_elems
+        self.query_np_dtype, self.query_elems = NP_DTYPE[dtype], self.row_elems
         pq_chunks = 0
         if dtype == PQ:  # rows are PQ codes, queries stay full-precision f32
             pq_offsets = np.ascontiguousarray(pq_offsets, dtype=np.uint32)
             pq_chunks = pq_offsets.size - 1
             self.row_elems = pq_chunks
-            self.query_dtype, self.query_elems = np.float32, self.dim
+            self.query_np_dtype, self.query_elems = np.float32, self.dim
         sp = np.ascontiguousarray(start_points, dtype=NP_DTYPE[dtype]).reshape(-1, self.row_elems)
         self.num_start_points = sp.shape[0]
         cfg = Config(dtype, metric, self.dim, self.capacity, self.max_degree, self.num_start_points, row_stride,
@@ -137,7 +137,7 @@ class Provider:
     def set_query_layout(self, layout):
         """the byte image of the queries every query-taking method reads from now on (_ffi.QUERY_*)"""
         check(_ffi.lib().dann_set_query_layout(self._h, int(layout)), "dann_set_query_layout")
-        self.query_elems = self.query_bytes() // np.dtype(self.query_dtype).itemsize
+        self.query_elems = self.query_bytes() // np.dtype(self.query_np_dtype).itemsize
 
     def query_layout(self):
         return int(_ffi.lib().dann_get_query_layout(self._h))
@@ -145,6 +145,18 @@ class Provider:
     def query_bytes(self):
         """bytes of one query under the current layout"""
         return int(_ffi.lib().dann_query_bytes(self._h))
+
+    # -- MinMax rows: MinMaxQuery::EightBit ------------------------------------
+    def set_query_dtype(self, dtype):
+        """the dtype of the query images every query-taking method reads from now on: the index's own, or MM8 on an
+        MM4 / MM2 / MM1 index (images of 20 + dim bytes, what MinMax.compress writes at 8 bits)"""
+        check(_ffi.lib().dann_set_query_dtype(self._h, int(dtype)), "dann_set_query_dtype")
+        self.query_elems = self.query_bytes() // np.dtype(self.query_np_dtype).itemsize
+
+    def query_dtype(self):
+        out = C.c_int32()
+        check(_ffi.lib().dann_get_query_dtype(self._h, C.byref(out)), "dann_get_query_dtype")
+        return out.value
 
     # -- SetElement ---------------------------------------------------------
     def set_element(self, slot, vector):
@@ -253,7 +265,7 @@ class Provider:
             _ffi.lib().dann_query_destroy(h)
 
     def expand_beam_batch(self, queries, ids, offsets):
-        q = np.ascontiguousarray(queries, dtype=self.query_dtype).reshape(-1, self.query_elems)
+        q = np.ascontiguousarray(queries, dtype=self.query_np_dtype).reshape(-1, self.query_elems)
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         off = np.ascontiguousarray(offsets, dtype=np.uint64)
         out = np.empty(ids.size, np.float32)
@@ -264,7 +276,7 @@ class Provider:
     # -- DiskANNIndex::search -------------------------------------------------
     def search(self, params, queries, k=10):
         """nq independent Knn searches; returns (ids[nq,k], dists[nq,k], stats[nq])."""
-        q = np.ascontiguousarray(queries, dtype=self.query_dtype).reshape(-1, self.query_elems)
+        q = np.ascontiguousarray(queries, dtype=self.query_np_dtype).reshape(-1, self.query_elems)
         nq = q.shape[0]
         ids = np.empty((nq, k), np.uint32)
         dists = np.empty((nq, k), np.float32)
@@ -276,7 +288,7 @@ class Provider:
     def range_search(self, queries, starting_l, radius, beam_width=1, inner_radius=None, initial_slack=1.0,
                      range_slack=1.0, max_returned=0, out_cap=None):
         """graph::search::Range for a batch; returns (ids, dists, stats, second_round)."""
-        q = np.ascontiguousarray(queries, dtype=self.query_dtype).reshape(-1, self.query_elems)
+        q = np.ascontiguousarray(queries, dtype=self.query_np_dtype).reshape(-1, self.query_elems)
         nq = q.shape[0]
         cap = int(out_cap or max_returned or 1024)
         ids = np.empty((nq, cap), np.uint32)
@@ -311,7 +323,7 @@ class Provider:
 
     def filtered_search(self, params, queries, k, match, mode=None, adaptive=None, matched_cap=0):
         """InlineFilterSearch (default) or MultihopFilterSearch for a batch; returns (ids, dists, stats)."""
-        q = np.ascontiguousarray(queries, dtype=self.query_dtype).reshape(-1, self.query_elems)
+        q = np.ascontiguousarray(queries, dtype=self.query_np_dtype).reshape(-1, self.query_elems)
         nq = q.shape[0]
         f, keep = self._filter(mode or FILTER_INLINE, match, nq, adaptive, matched_cap)
         ids = np.empty((nq, k), np.uint32)
@@ -326,7 +338,7 @@ class Provider:
     def filtered_range_search(self, queries, starting_l, radius, match, beam_width=1, inner_radius=None,
                               initial_slack=1.0, range_slack=1.0, max_returned=0, out_cap=None, matched_cap=0):
         """graph::search::FilteredRange for a batch; returns (ids, dists, stats, second_round)."""
-        q = np.ascontiguousarray(queries, dtype=self.query_dtype).reshape(-1, self.query_elems)
+        q = np.ascontiguousarray(queries, dtype=self.query_np_dtype).reshape(-1, self.query_elems)
         nq = q.shape[0]
         f, keep = self._filter(FILTER_INLINE, match, nq, None, matched_cap)
         cap = int(out_cap or max_returned or 1024)
@@ -348,7 +360,7 @@ class Provider:
 
     def rerank(self, queries, cand_ids, k):
         """Rerank post-processor: full-precision distances for the candidates of a quantised search."""
-        q = np.ascontiguousarray(queries, dtype=self.query_dtype).reshape(-1, self.query_elems)
+        q = np.ascontiguousarray(queries, dtype=self.query_np_dtype).reshape(-1, self.query_elems)
         c = np.ascontiguousarray(cand_ids, dtype=np.uint32).reshape(q.shape[0], -1)
         ids = np.empty((q.shape[0], k), np.uint32)
         d = np.empty((q.shape[0], k), np.float32)
@@ -370,7 +382,7 @@ class Provider:
         the first k rows under (distance ascending, slot descending).  match: a bool array over the slots [0, capacity +
         start points), shared or one row per query -- only matching slots are evaluated.  Returns (ids[nq, k], dists[nq, k]),
         with stats=True also the SearchStats records; places behind the last result hold 0xFFFFFFFF / +inf."""
-        q = np.ascontiguousarray(queries, dtype=self.query_dtype).reshape(-1, self.query_elems)
+        q = np.ascontiguousarray(queries, dtype=self.query_np_dtype).reshape(-1, self.query_elems)
         nq = q.shape[0]
         n = self.capacity - first if n is None else n
         ids = np.empty((nq, k), np.uint32)
@@ -441,7 +453,7 @@ class Provider:
         with stats=True also the SearchStats records; counts are always the true numbers of matches.  out_cap None: n (every
         result fits); out_cap=0 only counts (ids and dists come back with no columns).  A count above out_cap raises
         DannError with status EOVERFLOW; `partial` of the exception holds what this method would have returned."""
-        q = np.ascontiguousarray(queries, dtype=self.query_dtype).reshape(-1, self.query_elems)
+        q = np.ascontiguousarray(queries, dtype=self.query_np_dtype).reshape(-1, self.query_elems)
         nq = q.shape[0]
         n = self.capacity - first if n is None else n
         cap = int(n if out_cap is None else out_cap)
@@ -548,7 +560,7 @@ class Provider:
 
     def diverse_search(self, params, queries, k, diverse_k, total_k):
         """Diverse::new(Knn, DiverseSearchParams{diverse_k, total_k}) for a batch; returns (ids, dists, stats)"""
-        q = np.ascontiguousarray(queries, dtype=self.query_dtype).reshape(-1, self.query_elems)
+        q = np.ascontiguousarray(queries, dtype=self.query_np_dtype).reshape(-1, self.query_elems)
         nq = q.shape[0]
         ids = np.empty((nq, k), np.uint32)
         dists = np.empty((nq, k), np.float32)
@@ -759,7 +771,7 @@ class Provider:
 
     def search_record_queries(self, queries, l_value, rec_stride=None):
         """VisitedSearchRecord of a Knn search (beam 1) per external query: (ids[nq, stride], dists, n[nq], stats)"""
-        q = np.ascontiguousarray(queries, dtype=self.query_dtype).reshape(-1, self.query_elems)
+        q = np.ascontiguousarray(queries, dtype=self.query_np_dtype).reshape(-1, self.query_elems)
         nq = q.shape[0]
         stride = int(rec_stride or 4 * (l_value + self.num_start_points) + 64)
         rid = np.empty((nq, stride), np.uint32)
@@ -789,8 +801,8 @@ class Provider:
         check(_ffi.lib().dann_server_stop(self._h), "dann_server_stop")
 
     def submit(self, query):
-        """one query (row of query_dtype) -> ticket"""
-        q = np.ascontiguousarray(query, dtype=self.query_dtype).reshape(self.query_elems)
+        """one query (row of query_np_dtype) -> ticket"""
+        q = np.ascontiguousarray(query, dtype=self.query_np_dtype).reshape(self.query_elems)
         t = C.c_uint64(0)
         check(_ffi.lib().dann_search_submit(self._h, _p(q), C.byref(t)), "dann_search_submit")
         return t.value
@@ -816,7 +828,7 @@ class Provider:
         """`threads` native host threads issue single-query calls on this index (dann_debug_concurrent_callers):
         mode 0 = dann_search_batch(nq = 1) per call, mode 1 = submit / wait with `depth` tickets outstanding per
         thread.  Returns (ids, dists, latency_us[nq], seconds)."""
-        q = np.ascontiguousarray(queries, dtype=self.query_dtype).reshape(-1, self.query_elems)
+        q = np.ascontiguousarray(queries, dtype=self.query_np_dtype).reshape(-1, self.query_elems)
         nq = q.shape[0]
         ids = np.empty((nq, k), np.uint32)
         dists = np.empty((nq, k), np.float32)

@@ -162,7 +162,7 @@ def build_sharded_native(provider, cfg, first, n, growth, max_batch, comm, stats
 def search_sharded_native(provider, comm, queries, l_value, beam_width, k):
     """dann_search_sharded: every rank passes the same query block and receives every result."""
     from . import _ffi
-    q = np.ascontiguousarray(queries, dtype=provider.query_dtype).reshape(-1, provider.query_elems)
+    q = np.ascontiguousarray(queries, dtype=provider.query_np_dtype).reshape(-1, provider.query_elems)
     ids = np.empty((q.shape[0], k), np.uint32)
     dists = np.empty((q.shape[0], k), np.float32)
     _ffi.check(_ffi.lib().dann_search_sharded(provider._h, comm._h, q.ctypes.data, q.shape[0], l_value, beam_width, k,

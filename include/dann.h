@@ -99,10 +99,12 @@ typedef enum {
                                            64 four-bit values (bits/distances.rs:2123-2249): ceil(dim / 64) * 32 plane
                                            bytes, then the QueryMeta                                                   */
     DANN_QUERY_SCALAR_QUANTIZED = 2,    /* 2- and 4-bit rows: Dense codes of the rows' width, then the QueryMeta        */
-    DANN_QUERY_FULL_PRECISION = 3,      /* reserved: DANN_EUNSUPPORTED                                                  */
+    DANN_QUERY_FULL_PRECISION = 3,      /* reserved: DANN_EUNSUPPORTED (MinMax rows: see dann_set_query_dtype for the
+                                           query form that is served)                                                  */
     /* 4 .. 7: DANN_EINVAL */
-    DANN_QUERY_EIGHT_BIT = 8            /* MinMaxQuery::EightBit, an MM8 image against narrower MinMax rows: reserved,
-                                           DANN_EUNSUPPORTED on every index                                            */
+    DANN_QUERY_EIGHT_BIT = 8            /* MinMaxQuery::EightBit, an MM8 image against narrower MinMax rows: not set
+                                           through dann_set_query_layout (DANN_EUNSUPPORTED on every index) but with
+                                           dann_set_query_dtype(idx, DANN_MM8); dann_get_query_layout reports it then   */
 } dann_query_layout;
 
 /* == `#[repr(C)] enum Metric`, diskann-vector/src/distance/metric.rs:8-20 */
@@ -567,6 +569,19 @@ int32_t dann_set_query_layout(dann_index* idx, int32_t layout);
 int32_t dann_get_query_layout(const dann_index* idx);
 /* bytes of one query under the current layout (every row type: f32 vectors for DANN_PQ, else the row's payload) */
 int32_t dann_query_bytes(const dann_index* idx);
+/* MinMax indexes: the dtype of the query images that every entry point taking `queries`, `query` or `d_queries` reads.
+ * Default: the index's own.  On a DANN_MM4 / MM2 / MM1 index DANN_MM8 is also allowed (MinMaxQuery::EightBit: the query
+ * is compressed to a Data<8> image and scored through the heterogeneous kernel::<8, M>, minmax/vectors.rs:206-229, x the
+ * query and y the row): dann_query_bytes() is then 20 + dim and the queries are front-canonical MM8 images, the bytes
+ * dann_minmax_compress writes at 8 bits.  Distances stay bit for bit the reference's: the raw product is an exact u32,
+ * so dim * 255 * (2^bits - 1) must fit one (else DANN_EINVAL).  Served by the Knn, range, filtered, filtered-range,
+ * paged, diverse, rerank, expand-beam, dann_query_* and flat entry points, the host-pointer forms included; the search
+ * server as for every row type where the query is a multiple of 16 bytes.  Read on every call; a dann_query keeps the
+ * dtype it was created under.  Whatever uses a stored row as the query (see dann_set_query_layout) stays row x row.
+ * Setting the index's own dtype is accepted on every index; any other pair of MinMax dtypes is DANN_EUNSUPPORTED, any
+ * other dtype DANN_EINVAL; while the search server runs: DANN_EBUSY.  The replicas of a dann_multi are set one by one. */
+int32_t dann_set_query_dtype(dann_index* idx, int32_t dtype);
+int32_t dann_get_query_dtype(const dann_index* idx, int32_t* out);
 /* Optional GPU-private search layout of a DANN_PQ index (at most 64 chunks, no inline tags): for every slot one
  * 64-byte-aligned row holding its adjacency list AND the code rows of its neighbours, so that a hop of the beam search
  * (expand_beam over PQ rows: diskann-providers/src/model/pq/fixed_chunk_pq_table.rs:82-100 per neighbour) is one

@@ -1,6 +1,6 @@
 """MinMax search at 1 M points next to the scalar quantiser and full precision (not part of bench.py): build one
 1 M x 128 graph on f32 rows, then search the same graph on MM8 and MM4 copies of the data (dann_minmax_compress, grid
-scale 1, no transform; queries are row images, DANN_QUERY_SAME_AS_DATA -- the eight-bit query layout is not served),
+scale 1, no transform; queries are row images of the rows' own width; 8-bit queries against narrower rows: scratch/minmax_q8_bench.py),
 on an SQ-8 copy and on the f32 rows themselves (the yardsticks: existing code), in the same run: wall-clock QPS of one
 host-pointer call, the HIP-event kernel time (dann_kernel_time), the algorithmic bytes of a launch (rows + adjacency
 lists read) and recall@10 against f32 brute force, at L in {26, 64}.  Prints one line per configuration and one JSON line.
