@@ -22,7 +22,7 @@
 //   cons_select_kernel   pools of more than 4096 candidates only: SortedNeighbors::new keeps the max_occlusion_size nearest
 //                        (<= 4096), so an exact selection of those by (distance, pool position), handed on in pool order,
 //                        leaves the prune the same sorted list;
-//   prune_pools_into_rows (build_kernels.hip) the back-edge prune pipeline: row kernel, or sort + Gram tiles + sweep.
+//   prune_pools_into_rows (build_batch.hip)  the back-edge prune pipeline: row kernel, or sort + Gram tiles + sweep.
 // dann_prune_range (graph_stats.hip; DiskANNIndex::prune_range, index.rs:2656-2701) is the same pass (run_list_prunes)
 // with no deleted state: lists longer than pruned_degree are queued and always go through robust_prune_list.
 // The worklists are processed in chunks, so the pool buffers and the Gram scratch stay bounded for any index size.

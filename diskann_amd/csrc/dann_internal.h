@@ -180,10 +180,10 @@ int32_t launch_search_server(dann_index* idx, SearchCtx& ctx, SearchArgs a);  //
 // explicit table size set with dann_set_visited_bits, or 0 = let search_with_retry size it
 uint32_t auto_visited_entries(const dann_index* idx, uint32_t l_value, uint32_t beam);
 
-// HIP-event time of the MFMA Gram-tile launches of the build path (build_kernels.hip; dann_kernel_time which = 5)
+// HIP-event time of the MFMA Gram-tile launches of the build path (build_batch.hip; dann_kernel_time which = 5)
 int32_t build_tile_clock(const dann_index* idx, double* total_ms, uint64_t* launches);
 void build_tile_clock_reset(const dann_index* idx);
-// robust_prune_list (force_saturate = false) of caller-built pools straight into the adjacency rows (build_kernels.hip;
+// robust_prune_list (force_saturate = false) of caller-built pools straight into the adjacency rows (build_batch.hip;
 // graph consolidation, consolidate.hip).  Queued on idx->main.stream; prune_pools_use_gram: whether
 // it takes the matrix-core path (the back-edge prunes' policy).
 bool prune_pools_use_gram(const dann_index* idx);
@@ -363,7 +363,7 @@ struct dann_index {
     // Read by the diverse search (search_diverse.hip).
     uint32_t* d_attr = nullptr;
     std::unordered_map<uint64_t, dann::VisitedCalib> calib;  // guarded by stat_mu
-    void* build_scratch = nullptr;            // owned by build_kernels.hip
+    void* build_scratch = nullptr;            // a BuildScratch (build_scratch.h), owned by build_batch.hip
     void (*build_scratch_free)(void*) = nullptr;
     dann::KernelClock clocks[5];  // 4 = beam-search retry launches (ms already in [0]; launches = re-run queries); stat_mu
     dann::KernelClock families[DANN_FAMILY_COUNT];  // beam-search launches per kernel family (dann_debug.h); stat_mu
@@ -472,7 +472,7 @@ bool server_quiesce(dann_index* idx);  // server.hip: the resident kernel leaves
     (void)0
 // the prune kernels' largest candidate pool (their LDS layout); larger pools are refused, or cut to it first
 constexpr uint32_t kMaxPool = 4096;
-// build_kernels.hip: a dann_build_config against the index, for every entry point that prunes (`what` names it in the
+// build_batch.hip: a dann_build_config against the index, for every entry point that prunes (`what` names it in the
 // message).  DANN_EUNSUPPORTED: PQ rows, a metric the row type does not have, max_occlusion_size > kMaxPool;
 // DANN_EINVAL: the rest.  Only the build path searches, so only it needs l_build.
 int32_t check_build_cfg(const dann_index* idx, const dann_build_config* cfg, const char* what, bool need_l_build);

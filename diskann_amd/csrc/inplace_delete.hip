@@ -25,7 +25,7 @@
 //   hipcub radix sort   of the edge keys: each source's targets in call order, each id's targets in its own edge order;
 //   idel_agg_kernel     one wavefront per distinct source: remove the call's ids, the deduplicated extend, then
 //                       nothing / write / pool for robust_prune_list (unreadable ids and the source leave the pool);
-//   prune_pools_into_rows (build_kernels.hip) the back-edge prune pipeline: row kernel, or sort + Gram tiles + sweep.
+//   prune_pools_into_rows (build_batch.hip)  the back-edge prune pipeline: row kernel, or sort + Gram tiles + sweep.
 // Host synchronisations per call: five (the validation read of the deleted bitmap, the edge bound, the edge count, the
 // source count and longest edge run, the final counters), two more with out_counters (dann_build_counters before and
 // after), one more on a rolled-back error.  Every failure before step 4 removes the call's marks again; step 4 rewrites

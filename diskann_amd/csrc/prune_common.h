@@ -1,5 +1,5 @@
 // prune_common.h -- device and host helpers shared by the translation units that run RobustPrune's row kernels
-// (build_kernels.hip: insert / back-edge / pool prunes; consolidate.hip: the pool gather of graph consolidation).
+// (prune_rows.hip, prune_gram.hip: insert / back-edge / pool prunes; consolidate.hip: the pool gather of graph consolidation).
 #pragma once
 
 #include "dann_device.h"

@@ -29,7 +29,7 @@
 using namespace dann;
 
 namespace dann {
-bool build_bootstrap_too_big(dann_index* idx);  // build_kernels.hip
+bool build_bootstrap_too_big(dann_index* idx);  // build_batch.hip
 }
 
 // ---- communicators ----------------------------------------------------------------------------------------------------

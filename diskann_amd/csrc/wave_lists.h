@@ -1,6 +1,6 @@
 // wave_lists.h -- wave-level list helpers of the kernels that build, sort and compact id lists: the slot-bitmap test and
 // the tag values of the deleted state, the lock-free appends of the mutation kernels (consolidate.hip,
-// inplace_delete.hip), and the (distance, payload) sort key with its in-LDS bitonic sort (also build_kernels.hip,
+// inplace_delete.hip), and the (distance, payload) sort key with its in-LDS bitonic sort (also prune_rows.hip, prune_gram.hip,
 // distance_kernels.hip, maxsim_kernels.hip).  The search kernels keep their own ordered_bits / wave_sort_keys
 // (search_kernel_impl.h): no -0.0 fold there, and a sort of global memory.
 #pragma once

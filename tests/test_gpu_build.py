@@ -452,6 +452,52 @@ def test_gram_tiles_of_f16_rows_on_the_f16_matrix_core_stay_inside_the_error_int
             assert np.all(np.abs(nrm.astype(np.float64) - sq) <= np.spacing(sq.astype(np.float32)).astype(np.float64)), (n, dim)
 
 
+GRAM_TILE_SHAPES = ((1, 8, 32), (7, 33, 32), (33, 100, 64), (70, 768, 96), (96, 96, 96), (130, 260, 96), (200, 128, 96),
+                    (256, 64, 96), (160, 1536, 96))
+GRAM_TILE_FORMS = {"f32": (oracle.F32, np.float32), "f16_widened": (oracle.F16 | 0x100, np.float16),
+                   "f16_matrix_core": (oracle.F16, np.float16)}
+
+
+def gram_tile_hashes(form):
+    """SHA-256 of the rows given to dann_debug_gram_tiles and of what it returns (the Gram block's lower triangle, row
+    by row, and the norms), for GRAM_TILE_SHAPES in order, one fixed seed per form."""
+    import ctypes as C
+    import hashlib
+    code, npdt = GRAM_TILE_FORMS[form]
+    rng = np.random.default_rng(57)
+    lib = da._ffi.lib()
+    out = []
+    for n, dim, mg in GRAM_TILE_SHAPES:
+        rows = (rng.standard_normal((n, dim)) * rng.uniform(0.1, 8.0, (n, 1))).astype(npdt)
+        got = np.empty((n, mg), np.float32)
+        nrm = np.empty(n, np.float32)
+        da._ffi.check(lib.dann_debug_gram_tiles(-1, code, rows.ctypes.data_as(C.c_void_p), n, dim, mg,
+                                                got.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p)),
+                      "dann_debug_gram_tiles")
+        lower = got[np.arange(mg)[None, :] <= np.arange(n)[:, None]]  # columns j <= i inside the block
+        out.append({"shape": [n, dim, mg], "rows": hashlib.sha256(rows.tobytes()).hexdigest(),
+                    "gram": hashlib.sha256(lower.tobytes()).hexdigest(), "norms": hashlib.sha256(nrm.tobytes()).hexdigest()})
+    return out
+
+
+@pytest.mark.parametrize("form", sorted(GRAM_TILE_FORMS))
+def test_gram_tiles_keep_the_recorded_bits(form):
+    """The Gram tile kernel's output, bit for bit, against hashes recorded before the build path was split into
+    units (tests/golden/gram_tile_hashes.json names the commit and the device).  The f16 matrix-core form is otherwise
+    only held to an error interval: its sums are in the hardware's order, which no CPU restatement pins -- a change of
+    the tiling, the slab order or the MFMA order moves these bits and nothing else in the suite."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(__file__), "golden", "gram_tile_hashes.json")) as f:
+        want = json.load(f)["forms"][form]
+    got = gram_tile_hashes(form)
+    assert [g["shape"] for g in got] == [w["shape"] for w in want]
+    for g, w in zip(got, want):
+        assert g["rows"] == w["rows"], ("the generated input rows differ from the recorded ones", g["shape"])
+        assert g["gram"] == w["gram"], g["shape"]
+        assert g["norms"] == w["norms"], g["shape"]
+
+
 @pytest.mark.parametrize("dtype,metric,dim", [(oracle.F16, oracle.L2, 96), (oracle.F16, oracle.INNER_PRODUCT, 100),
                                               (oracle.F32, oracle.L2, 260)])
 def test_mfma_pool_prune_f16_and_default_policy_identical_to_oracle(dtype, metric, dim):

@@ -1,5 +1,5 @@
 """The MFMA prunes decide `d_ik / d_jk > alpha` from Gram-matrix distances d' whenever the error interval
-[d' - E, d' + E], E = c1 (|x|^2 + |y|^2) + c2 |d'| (csrc/build_kernels.hip: gram_c1_chained, gram_c2_for_dim,
+[d' - E, d' + E], E = c1 (|x|^2 + |y|^2) + c2 |d'| (csrc/build_common.h: gram_c1_chained, gram_c2_for_dim,
 `first_exceed`), decides it, and re-evaluate the pair with the bit-exact row kernel otherwise.  The graph is only
 identical to the reference's if E really bounds |d' - d_ref|.  This test evaluates d' with the oracle's restatement of
 the kernel's Gram arithmetic (orc_gram_chain: one f32 FMA chain per entry -- checked bit for bit against the MFMA kernel
@@ -22,12 +22,12 @@ def _sets(rng, dim):
 
 
 def _c1_chained(dim):
-    """csrc/build_kernels.hip gram_c1_chained: 1.05 (K + 4) 2^-24 with K = dim rounded up to 32"""
+    """csrc/build_common.h gram_c1_chained: 1.05 (K + 4) 2^-24 with K = dim rounded up to 32"""
     return np.float32(1.05) * np.float32(((dim + 31) // 32 * 32) + 4) * np.float32(2.0 ** -24)
 
 
 def _c2_for_dim(dim):
-    """csrc/build_kernels.hip gram_c2_for_dim: max(3e-6, (dim / 8 + 16) 2^-24)"""
+    """csrc/build_common.h gram_c2_for_dim: max(3e-6, (dim / 8 + 16) 2^-24)"""
     return max(np.float32(3.0e-6), np.float32(dim // 8 + 16) * np.float32(2.0 ** -24))
 
 

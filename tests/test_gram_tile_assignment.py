@@ -1,4 +1,4 @@
-"""CPU model of how gram_tiles_kernel (diskann_amd/csrc/build_kernels.hip) deals the tiles of one candidate list to the
+"""CPU model of how gram_tiles_kernel (diskann_amd/csrc/gram_tiles.hip) deals the tiles of one candidate list to the
 eight waves of its workgroup: tile q of the row-major enumeration goes to wave q % 8 (odd workgroups count their waves in
 reverse).  Checked for every shape the launches can have: each tile of the lower-triangular tiling is computed exactly once,
 no wave owns more than three (the kernel's accumulator budget), the narrow instantiation is chosen exactly when no wave
