@@ -4,6 +4,7 @@ import concurrent.futures as cf
 import os
 import subprocess
 import sys
+import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -13,6 +14,7 @@ SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fgpu-flush-denormals-to-zero=0" if False else "-fno-gpu-flush-denormals-to-zero", "-Wall",
          "-Wno-unused-function"]
+HEARTBEAT_S = 60  # a progress line at least this often while objects compile
 
 
 def _hipcc():
@@ -54,21 +56,35 @@ def build(force=False, verbose=False):
         if force or _stale(obj, [src] + (deps if deps is not None else headers)):
             jobs.append((src, obj))
 
+    done = []
+
     def cc(job):
         src, obj = job
         cmd = [_hipcc(), *FLAGS, "-MD", "-MF", obj[:-2] + ".d", "-c", src, "-o", obj]
+        t0 = time.monotonic()
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed for {src}:\n{r.stdout}\n{r.stderr}")
         if verbose and r.stderr:
             sys.stderr.write(r.stderr)
+        # one line per object: a full build takes many minutes, and a silent one looks hung
+        done.append(obj)
+        print(f"[{len(done)}/{len(jobs)}] {os.path.basename(obj)} {time.monotonic() - t0:.0f} s", file=sys.stderr,
+              flush=True)
         return obj
 
     if jobs:
         # (not os.cpu_count(): on a shared machine it reports the whole box)
         workers = int(os.environ.get("MAX_JOBS") or 16)
+        t0 = time.monotonic()
         with cf.ThreadPoolExecutor(max_workers=max(1, min(workers, len(jobs)))) as ex:
-            list(ex.map(cc, jobs))
+            futures = [ex.submit(cc, job) for job in jobs]
+            # the long units run side by side and finish together, minutes after the last line: say that they run
+            while cf.wait(futures, timeout=HEARTBEAT_S).not_done:
+                print(f"... {len(done)}/{len(jobs)} objects after {time.monotonic() - t0:.0f} s", file=sys.stderr,
+                      flush=True)
+        for f in futures:
+            f.result()
     objs = [os.path.join(objdir, s.replace(".hip", ".o")) for s in SOURCES]
     if jobs or force or _stale(OUT, objs):
         cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUT, *objs]
