@@ -23,6 +23,8 @@ OK, EINVAL, ELENGTH, EBOUNDS, ETOOLONG, EHIP, ENOMEM, EOVERFLOW, EUNSUPPORTED, E
 IBC_NONE, IBC_ALL = 0, 0xFFFFFFFF
 TIE_POSITION, TIE_RUST = 0, 1  # dann_set_prune_tie_order
 MAXSIM_KERNEL, MAXSIM_REFERENCE = 0, 1  # the two orders of dann_maxsim_batch / dann_chamfer_rerank_batch
+# the aggregations of dann_mv_flat_search_batch (MV_AVERAGE_PAIRWISE is reserved: DANN_EUNSUPPORTED)
+MV_CHAMFER, MV_AVG_OF_MINS, MV_MIN_PAIRWISE, MV_AVERAGE_PAIRWISE = 0, 1, 2, 3
 BUILD_MFMA_BACKEDGE, BUILD_MFMA_POOL, BUILD_ROW_KERNEL_ONLY = 1, 2, 4
 CONSOLIDATE_COMPLETE, CONSOLIDATE_DELETED = 0, 1  # ConsolidateKind (dann_consolidate out_kind)
 CONSOLIDATE_DROP_DELETED = 1  # dann_consolidate flag
@@ -187,6 +189,9 @@ SYMBOLS = {
     "dann_maxsim_batch_device": (_i32, [_vp, _i32, _vp, _vp, _u32, _vp, _u32, _vp, _vp]),
     "dann_chamfer_rerank_batch": (_i32, [_vp, _i32, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
     "dann_chamfer_rerank_batch_device": (_i32, [_vp, _i32, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "dann_mv_flat_search_batch": (_i32, [_vp, _i32, _i32, _vp, _vp, _u32, _u32, _u32, _u32, _P(FlatFilter), _vp, _vp, _vp]),
+    "dann_mv_flat_search_batch_device": (_i32, [_vp, _i32, _i32, _vp, _vp, _u32, _u32, _u32, _u32, _P(FlatFilter), _vp, _vp,
+                                                _vp]),
     "dann_prune_batch": (_i32, [_vp, _P(BuildConfig), _vp, _u32, _vp, _vp, _vp, _i32, _vp]),
     "dann_insert_batch": (_i32, [_vp, _P(BuildConfig), _vp, _u32]),
     "dann_insert": (_i32, [_vp, _P(BuildConfig), _u32]),

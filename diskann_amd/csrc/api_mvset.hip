@@ -7,6 +7,7 @@
 #include <memory>
 
 #include "api_common.h"
+#include "maxsim_flat_plan.h"
 
 using namespace dann;
 
@@ -21,6 +22,7 @@ struct dann_mvset {
     uint8_t* d_rows = nullptr;
     dann::MmRowHeader* d_hdr = nullptr;       // MinMax sets only
     uint64_t* d_off = nullptr;
+    std::vector<uint64_t> h_off;              // the same offsets on the host: how many rows a range of documents has
     // HIP-event time of the scoring launches (dann_debug_mvset_kernel_time); clock_mu also keeps one call's pair of
     // events to itself
     mutable std::mutex clock_mu;
@@ -77,17 +79,10 @@ struct MvCall {
     uint64_t qrows_total = 0;
 };
 
-int32_t mv_prepare(const dann_mvset* s, int32_t order, const void* queries, const uint32_t* q_offsets, uint32_t nq,
-                   const uint32_t* cand, uint32_t cand_stride, bool on_device, MvCall& c) {
-    if (order != DANN_MAXSIM_KERNEL && order != DANN_MAXSIM_REFERENCE) {
-        set_error("order %d is not a DANN_MAXSIM_* value", order);
-        return DANN_EINVAL;
-    }
-    if (!q_offsets || !cand) return DANN_EINVAL;
-    if (cand_stride == 0 || cand_stride > kMaxSimCands) {
-        set_error("multi-vector scoring supports 1..%u candidates per query (got %u)", kMaxSimCands, cand_stride);
-        return DANN_EUNSUPPORTED;
-    }
+// the queries of a call: their limits, their offsets (a host copy in c.h_qoff) and their rows at the set's stride on the
+// device (c.q, c.qhdr, c.qoff); c.status is a zeroed word
+int32_t mv_stage_queries(const dann_mvset* s, const void* queries, const uint32_t* q_offsets, uint32_t nq, bool on_device,
+                         MvCall& c) {
     if (nq > kMaxSimQueries) {
         set_error("multi-vector scoring supports %u queries per call (got %u)", kMaxSimQueries, nq);
         return DANN_EUNSUPPORTED;
@@ -127,10 +122,28 @@ int32_t mv_prepare(const dann_mvset* s, int32_t order, const void* queries, cons
     DANN_HIP(hipMemset(c.status.p, 0, 4));
     if (!on_device) {
         DANN_HIP(c.qoff.alloc(((size_t)nq + 1) * 4));
-        DANN_HIP(c.cand.alloc((size_t)nq * cand_stride * 4));
         DANN_HIP(hipMemcpy(c.qoff.p, q_offsets, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice));
+    }
+    return DANN_OK;
+}
+
+int32_t mv_prepare(const dann_mvset* s, int32_t order, const void* queries, const uint32_t* q_offsets, uint32_t nq,
+                   const uint32_t* cand, uint32_t cand_stride, bool on_device, MvCall& c) {
+    if (order != DANN_MAXSIM_KERNEL && order != DANN_MAXSIM_REFERENCE) {
+        set_error("order %d is not a DANN_MAXSIM_* value", order);
+        return DANN_EINVAL;
+    }
+    if (!q_offsets || !cand) return DANN_EINVAL;
+    if (cand_stride == 0 || cand_stride > kMaxSimCands) {
+        set_error("multi-vector scoring supports 1..%u candidates per query (got %u)", kMaxSimCands, cand_stride);
+        return DANN_EUNSUPPORTED;
+    }
+    if (int32_t rc = mv_stage_queries(s, queries, q_offsets, nq, on_device, c)) return rc;
+    if (!on_device) {
+        DANN_HIP(c.cand.alloc((size_t)nq * cand_stride * 4));
         DANN_HIP(hipMemcpy(c.cand.p, cand, (size_t)nq * cand_stride * 4, hipMemcpyHostToDevice));
     }
+    const uint32_t qstride = mv_stride(c.qdtype, s->dim);  // (as mv_stage_queries laid the rows out)
     c.a.drows = s->d_rows;
     c.a.doff = s->d_off;
     c.a.ndocs = s->ndocs;
@@ -222,6 +235,126 @@ int32_t mv_rerank(const dann_mvset* s, int32_t order, const void* queries, const
     }
     return DANN_OK;
 }
+
+// dann_mv_flat_search_batch(_device): the checks in the header's order, the queries staged as a scoring call stages them,
+// then plan.batch queries per launch of the scan and its merge (maxsim_flat_kernels.hip)
+int32_t mv_flat_search(const dann_mvset* s, int32_t order, int32_t aggregation, const void* queries, const uint32_t* q_offsets,
+                       uint32_t nq, uint32_t first, uint32_t n, uint32_t k, const dann_flat_filter* filter, uint32_t* out_ids,
+                       float* out_dists, dann_search_stats* out_stats, bool on_device) {
+    const char* who = "dann_mv_flat_search_batch";
+    if (!s) return DANN_EINVAL;
+    if (dt_is_mm(s->dtype)) {
+        set_error("%s: not built for MinMax sets (dtype %d); DANN_F32 and DANN_F16 sets are served", who, s->dtype);
+        return DANN_EUNSUPPORTED;
+    }
+    if (order != DANN_MAXSIM_KERNEL && order != DANN_MAXSIM_REFERENCE) {
+        set_error("%s: order %d is not a DANN_MAXSIM_* value", who, order);
+        return DANN_EINVAL;
+    }
+    if (aggregation == DANN_MV_AVERAGE_PAIRWISE) {
+        set_error("%s: DANN_MV_AVERAGE_PAIRWISE is reserved", who);
+        return DANN_EUNSUPPORTED;
+    }
+    if (aggregation != DANN_MV_CHAMFER && aggregation != DANN_MV_AVG_OF_MINS && aggregation != DANN_MV_MIN_PAIRWISE) {
+        set_error("%s: aggregation %d is not a DANN_MV_* value", who, aggregation);
+        return DANN_EINVAL;
+    }
+    if (k == 0) {
+        set_error("%s: k cannot be zero", who);
+        return DANN_EINVAL;
+    }
+    if (k > kFlatMaxK) {
+        set_error("%s: k = %u exceeds the supported maximum of %u", who, k, kFlatMaxK);
+        return DANN_EUNSUPPORTED;
+    }
+    if ((uint64_t)first + n > s->ndocs) {
+        set_error("%s: documents [%u, %llu) leave the set's %u documents", who, first, (unsigned long long)first + n, s->ndocs);
+        return DANN_EBOUNDS;
+    }
+    const uint32_t* fbits = filter ? filter->bits : nullptr;
+    const uint64_t fstride = fbits ? filter->stride_words : 0;
+    const size_t words = ((size_t)s->ndocs + 31) / 32;
+    if (fstride && fstride < words) {
+        set_error("%s: filter stride %llu words is shorter than one bitmap (%llu words)", who, (unsigned long long)fstride,
+                  (unsigned long long)words);
+        return DANN_EINVAL;
+    }
+    if (nq == 0) return DANN_OK;
+    if (!q_offsets || !out_ids || !out_dists) {
+        set_error("%s: null pointer", who);
+        return DANN_EINVAL;
+    }
+    DeviceGuard dev(s->device);
+    if (!dev.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
+    MvCall c;
+    if (int32_t rc = mv_stage_queries(s, queries, q_offsets, nq, on_device, c)) return rc;
+    if (c.qdtype != s->dtype) {  // (the scan reads query rows at the set's stride; an f32 / f16 set takes no other dtype)
+        set_error("%s: queries of dtype %d on a set of dtype %d", who, c.qdtype, s->dtype);
+        return DANN_EINVAL;
+    }
+    const uint32_t* d_qoff = on_device ? q_offsets : c.qoff.as<uint32_t>();
+    // outputs and bitmaps on the device
+    DevBuf bi, bd, bs, bf;
+    const size_t ob = (size_t)nq * k * 4;
+    uint32_t* d_ids = out_ids;
+    float* d_d = out_dists;
+    dann_search_stats* d_stats = out_stats;
+    const uint32_t* d_fbits = fbits;
+    if (!on_device) {
+        DANN_HIP(bi.alloc(ob));
+        DANN_HIP(bd.alloc(ob));
+        d_ids = bi.as<uint32_t>(), d_d = bd.as<float>();
+        if (out_stats) {
+            DANN_HIP(bs.alloc((size_t)nq * sizeof(dann_search_stats)));
+            d_stats = bs.as<dann_search_stats>();
+        }
+        if (fbits) {
+            const size_t fb = (fstride ? (size_t)nq * fstride : words) * 4;
+            DANN_HIP(bf.alloc(fb));
+            DANN_HIP(hipMemcpy(bf.p, fbits, fb, hipMemcpyHostToDevice));
+            d_fbits = bf.as<uint32_t>();
+        }
+    }
+    if (n == 0) {
+        if (int32_t rc = launch_flat_empty(nq, k, d_ids, d_d, d_stats, nullptr)) return rc;
+    } else {
+        const uint64_t ends[2] = {s->h_off[first], s->h_off[(size_t)first + n]};  // the scanned rows
+        int cus = 0;
+        DANN_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device));
+        const MvFlatPlan plan = mv_flat_plan(ends[1] - ends[0], n, nq, k, (uint32_t)cus, 0);
+        DevBuf scratch, nz;
+        DANN_HIP(scratch.alloc(plan.scratch_bytes()));
+        const bool signs = aggregation == DANN_MV_MIN_PAIRWISE;  // a key folds -0.0 into +0.0: the signs travel beside it
+        if (signs) DANN_HIP(nz.alloc((size_t)plan.batch * words * 4));
+        const MvFlatSet set{s->d_rows, s->d_off, s->dtype, s->dim, s->stride};
+        std::lock_guard<std::mutex> lk(s->clock_mu);
+        DANN_HIP(hipEventRecord(s->ev0, nullptr));
+        for (uint32_t off = 0; off < nq; off += plan.batch) {
+            const uint32_t m = std::min(plan.batch, nq - off);
+            if (signs) DANN_HIP(hipMemsetAsync(nz.p, 0, (size_t)m * words * 4, nullptr));
+            if (int32_t rc = launch_mv_flat_search(set, plan, order, aggregation, c.q.as<uint8_t>(), d_qoff + off, m, first, n,
+                                                   d_fbits ? d_fbits + (size_t)off * fstride : nullptr, fstride,
+                                                   signs ? nz.as<uint32_t>() : nullptr, (uint32_t)words, scratch.p,
+                                                   d_ids + (size_t)off * k, d_d + (size_t)off * k,
+                                                   d_stats ? d_stats + off : nullptr, nullptr))
+                return rc;
+        }
+        DANN_HIP(hipEventRecord(s->ev1, nullptr));
+        DANN_HIP(hipStreamSynchronize(nullptr));  // (`scratch` is freed on return)
+        float ms = 0.f;
+        DANN_HIP(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+        s->clock.total_ms += ms;
+        s->clock.launches += 1;
+    }
+    if (!on_device) {
+        DANN_HIP(hipMemcpy(out_ids, bi.p, ob, hipMemcpyDeviceToHost));
+        DANN_HIP(hipMemcpy(out_dists, bd.p, ob, hipMemcpyDeviceToHost));
+        if (out_stats) DANN_HIP(hipMemcpy(out_stats, bs.p, (size_t)nq * sizeof(dann_search_stats), hipMemcpyDeviceToHost));
+    } else {
+        DANN_HIP(hipStreamSynchronize(nullptr));
+    }
+    return DANN_OK;
+}
 }  // namespace
 
 int32_t dann_mvset_create(int32_t device, int32_t dtype, uint32_t dim, uint32_t ndocs, const uint64_t* row_offsets,
@@ -273,6 +406,7 @@ int32_t dann_mvset_create(int32_t device, int32_t dtype, uint32_t dim, uint32_t 
         if (int32_t rc = mv_copy_rows(s->d_rows, s->stride, rows, row_bytes, nrows, false)) return rc;
     }
     DANN_HIP(hipMemcpy(s->d_off, row_offsets, ((size_t)ndocs + 1) * 8, hipMemcpyHostToDevice));
+    s->h_off.assign(row_offsets, row_offsets + (size_t)ndocs + 1);
     *out = s.release();
     return DANN_OK;
 } DANN_CATCH_ALL
@@ -350,6 +484,22 @@ int32_t dann_chamfer_rerank_batch_device(const dann_mvset* set, int32_t order, c
                                          uint32_t* d_out_counts) try {
     return mv_rerank(set, order, d_queries, d_q_offsets, nq, d_cand_ids, cand_stride, k, d_out_ids, d_out_dists,
                      d_out_counts, true);
+} DANN_CATCH_ALL
+
+int32_t dann_mv_flat_search_batch(const dann_mvset* set, int32_t order, int32_t aggregation, const void* queries,
+                                  const uint32_t* q_offsets, uint32_t nq, uint32_t first_doc, uint32_t n, uint32_t k,
+                                  const dann_flat_filter* filter, uint32_t* out_ids, float* out_dists,
+                                  dann_search_stats* out_stats) try {
+    return mv_flat_search(set, order, aggregation, queries, q_offsets, nq, first_doc, n, k, filter, out_ids, out_dists, out_stats,
+                          false);
+} DANN_CATCH_ALL
+
+int32_t dann_mv_flat_search_batch_device(const dann_mvset* set, int32_t order, int32_t aggregation, const void* d_queries,
+                                         const uint32_t* d_q_offsets, uint32_t nq, uint32_t first_doc, uint32_t n,
+                                         uint32_t k, const dann_flat_filter* d_filter, uint32_t* d_out_ids,
+                                         float* d_out_dists, dann_search_stats* d_out_stats) try {
+    return mv_flat_search(set, order, aggregation, d_queries, d_q_offsets, nq, first_doc, n, k, d_filter, d_out_ids, d_out_dists,
+                          d_out_stats, true);
 } DANN_CATCH_ALL
 
 }  // extern "C"

@@ -246,6 +246,22 @@ int32_t launch_mm_repack(int32_t dtype, const uint8_t* d_images, uint32_t image_
 int32_t launch_maxsim_mm(int32_t qdtype, int32_t dtype, int32_t order, const MaxSimArgs& a, uint32_t nq, hipStream_t stream);
 int32_t launch_chamfer_sort(const uint32_t* d_cand, const float* d_chamfer, uint32_t nq, uint32_t stride, uint32_t ndocs,
                             uint32_t k, uint32_t* d_out_ids, float* d_out_d, uint32_t* d_out_counts, hipStream_t stream);
+// maxsim_flat_kernels.hip: the exhaustive scan of dann_mv_flat_search_batch(_device) over an f32 / f16 set, cut up as
+// maxsim_flat_plan.h says.  One launch serves at most plan.batch queries (d_qoff: their nq + 1 offsets into d_qrows) over
+// documents [first, first + n), n > 0; `scratch` holds plan.scratch_bytes(); d_filter: these queries' bitmaps over
+// document ids (null: every document), `fstride` words apart (0: one for all); d_negzero: nq x nz_words zeroed words
+// under DANN_MV_MIN_PAIRWISE, else null.
+struct MvFlatSet {
+    const uint8_t* drows;
+    const uint64_t* doff;
+    int32_t dtype;
+    uint32_t dim, stride;
+};
+struct MvFlatPlan;
+int32_t launch_mv_flat_search(const MvFlatSet& set, const MvFlatPlan& plan, int32_t order, int32_t aggregation, const uint8_t* d_qrows,
+                              const uint32_t* d_qoff, uint32_t nq, uint32_t first, uint32_t n, const uint32_t* d_filter,
+                              uint64_t fstride, uint32_t* d_negzero, uint32_t nz_words, void* scratch, uint32_t* d_ids,
+                              float* d_dists, dann_search_stats* d_stats, hipStream_t stream);
 
 int32_t launch_expand_beam(const IndexView& ix, const void* d_queries, uint32_t nq, const uint32_t* d_ids,
                            const uint64_t* d_offsets, uint64_t max_len, float* d_out, hipStream_t stream);

@@ -1,4 +1,5 @@
-"""Multi-vector (late-interaction) scoring: dann_mvset + dann_maxsim_batch / dann_chamfer_rerank_batch.
+"""Multi-vector (late-interaction) scoring: dann_mvset + dann_maxsim_batch / dann_chamfer_rerank_batch, and the exhaustive
+search over a whole set, dann_mv_flat_search_batch.
 
 A document and a query are small matrices of token rows.  MaxSim: per query row, the best inner product over the document's
 rows, as a similarity score (negated); Chamfer: their sum over the query's rows.  `order` picks whose bits come back
@@ -14,7 +15,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._ffi import F16, F32, MAXSIM_KERNEL, MAXSIM_REFERENCE, MM1, MM2, MM4, MM8, check, lib
+from ._ffi import (F16, F32, MAXSIM_KERNEL, MAXSIM_REFERENCE, MM1, MM2, MM4, MM8, MV_AVG_OF_MINS, MV_CHAMFER, MV_MIN_PAIRWISE,
+                   FlatFilter, check, lib)
 
 _NP = {F32: np.float32, F16: np.float16}
 _MM = (MM1, MM2, MM4, MM8)
@@ -134,5 +136,40 @@ class MultiVectorSet:
                                               _vp(dists), _vp(counts)), "dann_chamfer_rerank_batch")
         return ids, dists, counts
 
+    def _flat_filter(self, match, nq):
+        """dann_flat_filter of a bool array over the documents (shared) or nq x ndocs (per query); keep `bits` alive"""
+        m = np.asarray(match, dtype=bool)
+        m = m.reshape(1, -1) if m.ndim == 1 else m
+        if m.shape[1] != self.ndocs or m.shape[0] not in (1, nq):
+            raise ValueError("match is (ndocs,) or (queries, ndocs)")
+        words = (self.ndocs + 31) // 32
+        padded = np.zeros((m.shape[0], words * 32), bool)
+        padded[:, :self.ndocs] = m
+        bits = np.ascontiguousarray(np.packbits(padded, axis=1, bitorder="little")).view(np.uint32).reshape(m.shape[0], words)
+        f = FlatFilter()
+        f.bits = bits.ctypes.data
+        f.stride_words = 0 if m.shape[0] == 1 else words
+        return f, bits
 
-__all__ = ["MultiVectorSet", "MAXSIM_KERNEL", "MAXSIM_REFERENCE", "SKIP", "csr"]
+    def flat_search(self, queries, k, order=MAXSIM_KERNEL, aggregation=MV_CHAMFER, first=0, n=None, match=None, stats=False):
+        """Exhaustive k-NN over the documents [first, first + n) (n None: the rest of the set): per query the first k
+        documents under (aggregated score ascending, document id descending).  aggregation: MV_CHAMFER, MV_AVG_OF_MINS or
+        MV_MIN_PAIRWISE over the MaxSim scores of `order`.  match: a bool array over the documents, shared or one row per
+        query -- only matching documents are scored.  Returns (ids[nq, k], dists[nq, k]), with stats=True also the
+        SearchStats records; places behind the last result hold SKIP / +inf."""
+        from .provider import STATS_DTYPE
+        qoff, qrows = csr(queries, *self._row_shape(self.query_dtype), np.uint32)
+        nq = len(queries)
+        n = self.ndocs - first if n is None else n
+        ids = np.empty((nq, k), np.uint32)
+        dists = np.empty((nq, k), np.float32)
+        st = np.zeros(nq, STATS_DTYPE)
+        f, keep = (None, None) if match is None else self._flat_filter(match, nq)
+        check(lib().dann_mv_flat_search_batch(self._h, order, aggregation, _vp(qrows), _vp(qoff), nq, int(first), int(n), int(k),
+                                              C.byref(f) if f is not None else None, _vp(ids), _vp(dists),
+                                              _vp(st) if stats else None), "dann_mv_flat_search_batch")
+        del keep
+        return (ids, dists, st) if stats else (ids, dists)
+
+
+__all__ = ["MultiVectorSet", "MAXSIM_KERNEL", "MAXSIM_REFERENCE", "MV_CHAMFER", "MV_AVG_OF_MINS", "MV_MIN_PAIRWISE", "SKIP", "csr"]

@@ -1025,6 +1025,52 @@ int32_t dann_chamfer_rerank_batch_device(const dann_mvset* set, int32_t order, c
                                          const uint32_t* d_q_offsets, uint32_t nq, const uint32_t* d_cand_ids,
                                          uint32_t cand_stride, uint32_t k, uint32_t* d_out_ids, float* d_out_dists,
                                          uint32_t* d_out_counts);
+/* Exhaustive multi-vector k-NN: the reference's compute_multivec_ground_truth_from_data (diskann-tools/src/utils/
+ * ground_truth.rs:696-787, the compute_multivec_groundtruth tool) for nq queries over the documents
+ * [first_doc, first_doc + n) of a set.
+ * Sets and metric: DANN_F32 and DANN_F16 sets, queries in the set's dtype and CSR as for dann_maxsim_batch; a MinMax set
+ * (DANN_MM*) answers DANN_EUNSUPPORTED.  The metric is the inner product, the only one the multi-vector scores have.
+ * Per-row scores: scores[i] of (query, document) are exactly what dann_maxsim_batch returns for `order` --
+ * DANN_MAXSIM_KERNEL: one fma chain per pair from +0.0, -max_j from f32::MIN, the negation last; DANN_MAXSIM_REFERENCE:
+ * min_j InnerProduct::evaluate(q_i, d_j) from f32::MAX; a document without rows scores f32::MAX in every row.
+ * DANN_MAXSIM_REFERENCE with DANN_MV_AVG_OF_MINS is the tool's AvgofMins under Metric::InnerProduct, bit for bit.
+ * Aggregation, every f32 operation on its own:
+ *   DANN_MV_CHAMFER       Chamfer::evaluate: ((0.0 + scores[0]) + scores[1]) + ... in query-row order; 0.0 for a document
+ *                         without rows (as dann_maxsim_batch) and for a query without rows
+ *   DANN_MV_AVG_OF_MINS   the same sequential sum, then / (f32)q_rows (:764-776); a document without rows sums its
+ *                         f32::MAX cells as the arithmetic gives; a query without rows: 0.0 / 0.0 = NaN, dropped by the queue
+ *   DANN_MV_MIN_PAIRWISE  min_i scores[i] from f32::MAX (:753-763); f32::MAX for a query without rows
+ *   DANN_MV_AVERAGE_PAIRWISE  reserved: DANN_EUNSUPPORTED (a q_rows x d_rows long sequential f32 chain per pair: its bits
+ *                         cannot come out of a tiled product).  Any other value: DANN_EINVAL.
+ * Selection: the rule of dann_flat_search_batch.  The documents go in ascending id order through
+ * NeighborPriorityQueue::insert on a queue of k entries: the result is the first k non-NaN documents under (distance
+ * ascending with -0.0 == +0.0, document id descending), listed in that order; of equal scores the later document comes
+ * first and wins the k-th place.  out_ids / out_dists: nq x k, padded with 0xFFFFFFFF / +infinity.  out_stats
+ * (optional): cmps = documents evaluated for the query, hops = 0, result_count = written = min(k, documents inserted).
+ * Filter: a dann_flat_filter as in dann_flat_filtered_search_batch, over DOCUMENT ids [0, ndocs): shared
+ * (stride_words == 0) or per query; a non-zero stride below ceil(ndocs / 32) is DANN_EINVAL; NULL or null bits = every
+ * document.  A document whose bit is clear is neither scored nor counted.  A call with an all-ones filter equals one
+ * without in every output.
+ * Limits and errors, in this order: DANN_EINVAL for a null set; DANN_EUNSUPPORTED for a MinMax set; DANN_EINVAL for an
+ * unknown order or aggregation, DANN_EUNSUPPORTED for DANN_MV_AVERAGE_PAIRWISE; DANN_EINVAL for k == 0,
+ * DANN_EUNSUPPORTED for k > 1024; DANN_EBOUNDS when the range leaves [0, ndocs]; DANN_EINVAL for a short filter stride;
+ * nq == 0 then writes nothing; DANN_EINVAL for null q_offsets / out_ids / out_dists (or null queries with rows to
+ * read); nq and rows per query as for dann_maxsim_batch (DANN_EUNSUPPORTED); DANN_ELENGTH for q_offsets that decrease or
+ * do not start at 0.  With n == 0 every result is empty.  The call is host-synchronous.  The results depend neither on
+ * how the scan is cut up nor on the run.
+ * Outside the contract, as for the scores: NaN / infinite inputs, products that underflow to -0.0, and a
+ * DANN_MV_MIN_PAIRWISE minimum over zeros of both signs. */
+enum { DANN_MV_CHAMFER = 0, DANN_MV_AVG_OF_MINS = 1, DANN_MV_MIN_PAIRWISE = 2, DANN_MV_AVERAGE_PAIRWISE = 3 };
+int32_t dann_mv_flat_search_batch(const dann_mvset* set, int32_t order, int32_t aggregation, const void* queries,
+                                  const uint32_t* q_offsets, uint32_t nq, uint32_t first_doc, uint32_t n, uint32_t k,
+                                  const dann_flat_filter* filter, uint32_t* out_ids, float* out_dists,
+                                  dann_search_stats* out_stats);
+/* device-pointer form (queries, offsets, bitmaps and outputs on the set's device, the dann_flat_filter itself in host
+ * memory; complete on return) */
+int32_t dann_mv_flat_search_batch_device(const dann_mvset* set, int32_t order, int32_t aggregation, const void* d_queries,
+                                         const uint32_t* d_q_offsets, uint32_t nq, uint32_t first_doc, uint32_t n,
+                                         uint32_t k, const dann_flat_filter* d_filter, uint32_t* d_out_ids,
+                                         float* d_out_dists, dann_search_stats* d_out_stats);
 
 /* ABI revision of this header; bumped on any incompatible change of a signature or struct layout */
 #define DANN_ABI_VERSION 5
