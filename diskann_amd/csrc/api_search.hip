@@ -520,6 +520,112 @@ int32_t dann_filtered_range_search_batch(dann_index* idx, const void* queries, u
     return filtered_search(idx, ctx, c);
 } DANN_CATCH_ALL
 
+// ---- beta-filtered search (layers/betafilter.rs) -------------------------------------------------------------------
+}  // extern "C"
+namespace {
+// the checks both forms share (parameter errors as dann_filtered_search_batch; BetaFilter::new itself validates nothing,
+// a NaN factor would make every matching distance a NaN the queue ignores)
+int32_t beta_check(const dann_index* idx, uint32_t l_value, uint32_t beam_width, const uint32_t* bits, uint64_t stride_words,
+                   float beta) {
+    if (!bits) {
+        set_error("dann_beta_search_batch: bits must be non-null");
+        return DANN_EINVAL;
+    }
+    if (beta != beta) {
+        set_error("dann_beta_search_batch: beta is NaN");
+        return DANN_EINVAL;
+    }
+    if (l_value == 0 || beam_width == 0) {
+        set_error("l_value and beam_width must be non-zero");
+        return DANN_EINVAL;
+    }
+    if (int32_t prc = pq_ready(idx)) return prc;
+    const uint64_t words = ((uint64_t)idx->nslots + 31) / 32;
+    if (stride_words && stride_words < words) {
+        set_error("filter stride %llu words is shorter than one bitmap (%llu words)", (unsigned long long)stride_words,
+                  (unsigned long long)words);
+        return DANN_EINVAL;
+    }
+    return DANN_OK;
+}
+SearchArgs beta_args(dann_index* idx, uint32_t l_value, uint32_t beam_width, uint32_t k, uint64_t stride_words, float beta) {
+    SearchArgs a;
+    a.ix = idx->qview();
+    a.l_value = l_value;
+    a.beam_width = beam_width;
+    a.k = k;
+    a.ht_entries = auto_visited_entries(idx, l_value, beam_width);
+    a.beta_on = 1;
+    a.beta = beta;
+    a.filter_stride = stride_words;
+    return a;
+}
+}  // namespace
+extern "C" {
+
+int32_t dann_beta_search_batch(dann_index* idx, const void* queries, uint32_t nq, uint32_t l_value, uint32_t beam_width,
+                               uint32_t k, const uint32_t* bits, uint64_t stride_words, float beta, uint32_t* out_ids,
+                               float* out_dists, dann_search_stats* out_stats) try {
+    CHECK_IDX_SHARED(idx);
+    ArenaTrim _trim{ctx};
+    if (nq == 0) return DANN_OK;
+    if (!queries || !out_ids || !out_dists) return DANN_EINVAL;  // (k as dann_search_batch takes it)
+    if (int32_t rc = beta_check(idx, l_value, beam_width, bits, stride_words, beta)) return rc;
+    // queries go through in pieces that keep per-query bitmaps of a large index within the arena's resident size; the
+    // bitmaps are a per-query input of the piece (stride_words words each), a shared one a whole-call upload
+    const size_t words = ((size_t)idx->nslots + 31) / 32;
+    const size_t per_query = (size_t)idx->query_bytes() + (size_t)k * 8 + sizeof(dann_search_stats) + (size_t)stride_words * 4;
+    const uint32_t piece = (uint32_t)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(nq, 65536), kArenaKeepBytes / 2 / per_query));
+    HostStage hs;
+    const int32_t lrc = stride_words ? hs.layout(ctx, nq, piece, {{queries, idx->query_bytes()}, {bits, (size_t)stride_words * 4}},
+                                                 {{out_ids, (size_t)k * 4}, {out_dists, (size_t)k * 4}}, HostStage::kCheckStats)
+                                     : hs.layout(ctx, nq, piece, {{queries, idx->query_bytes()}},
+                                                 {{out_ids, (size_t)k * 4}, {out_dists, (size_t)k * 4}}, HostStage::kCheckStats,
+                                                 {words * 4});
+    if (lrc != DANN_OK) return lrc;
+    if (!stride_words) DANN_HIP(hipMemcpyAsync(hs.extra<void>(0), bits, words * 4, hipMemcpyHostToDevice, ctx.stream));
+    SearchArgs a = beta_args(idx, l_value, beam_width, k, stride_words, beta);
+    a.queries = hs.in(0);
+    a.filter = stride_words ? hs.in<uint32_t>(1) : hs.extra<uint32_t>(0);
+    a.out_ids = hs.out<uint32_t>(0);
+    a.out_dists = hs.out<float>(1);
+    a.stats = hs.stats();
+    uint32_t bad = nq;
+    if (int32_t rc = hs.walk(out_stats, &bad, [&](uint32_t, uint32_t m) {
+            a.nq = m;
+            return search_with_retry(idx, ctx, a);
+        }))
+        return rc;
+    if (bad < nq) {
+        set_error("query %u: a start point is not readable, or per-query scratch exhausted (visited table and spill pool); "
+                  "raise the table size with dann_set_visited_bits", bad);
+        return DANN_EOVERFLOW;
+    }
+    return DANN_OK;
+} DANN_CATCH_ALL
+
+int32_t dann_beta_search_batch_device(dann_index* idx, const void* d_queries, uint32_t nq, uint32_t l_value,
+                                      uint32_t beam_width, uint32_t k, const uint32_t* d_bits, uint64_t stride_words,
+                                      float beta, uint32_t* d_out_ids, float* d_out_dists,
+                                      dann_search_stats* d_out_stats) try {
+    CHECK_IDX_SHARED(idx);
+    if (nq == 0) return DANN_OK;
+    if (!d_queries || !d_out_ids || !d_out_dists) return DANN_EINVAL;
+    if (int32_t rc = beta_check(idx, l_value, beam_width, d_bits, stride_words, beta)) return rc;
+    if (!d_out_stats) {  // the overflow retry needs per-query status: context-owned stats when the caller passes none
+        if (int32_t rc = grow_stage(ctx, 2, (size_t)nq * sizeof(dann_search_stats))) return rc;
+        d_out_stats = reinterpret_cast<dann_search_stats*>(ctx.stage[2]);
+    }
+    SearchArgs a = beta_args(idx, l_value, beam_width, k, stride_words, beta);
+    a.queries = d_queries;
+    a.nq = nq;
+    a.filter = d_bits;
+    a.out_ids = d_out_ids;
+    a.out_dists = d_out_dists;
+    a.stats = d_out_stats;
+    return search_with_retry(idx, ctx, a);
+} DANN_CATCH_ALL
+
 int32_t dann_diverse_search_batch(dann_index* idx, const void* queries, uint32_t nq, uint32_t l_value,
                                   uint32_t beam_width, uint32_t k, const dann_diverse* params, uint32_t* out_ids,
                                   float* out_dists, dann_search_stats* out_stats) try {

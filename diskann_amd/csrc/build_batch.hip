@@ -807,6 +807,9 @@ int32_t dann_prune_batch(dann_index* idx, const dann_build_config* cfg, const ui
     DANN_HIP(hipMemcpyAsync(dd.p, pool_dists, total * 4, hipMemcpyHostToDevice, st));
     DANN_HIP(hipMemcpyAsync(doff.p, offsets, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
     DANN_HIP(hipMemsetAsync(derr.p, 0, 4, st));
+    // (the kernel writes a row up to its length: the places behind it come back as zeros, not as what the fresh
+    // allocation happened to hold)
+    DANN_HIP(hipMemsetAsync(dout.p, 0, (size_t)n * ostride * 4, st));
     PoolArgs pa;
     pa.ix = idx->view();
     pa.cfg = to_prune_cfg(idx, *cfg);

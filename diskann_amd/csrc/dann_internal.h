@@ -166,6 +166,12 @@ DANN_DECL_LAUNCH(pq);
 int32_t diverse_search_device(dann_index* idx, hipStream_t stream, const void* d_queries, uint32_t nq, uint32_t l_value,
                               uint32_t beam_width, uint32_t k, uint32_t diverse_k, uint32_t total_k, uint32_t* d_ids,
                               float* d_dists, dann_search_stats* d_stats);
+// search_beta_<rows>.hip: beam_search_beta_kernel (SearchArgs::beta_on), the row types of beam search in five units
+DANN_DECL_LAUNCH(beta_float);
+DANN_DECL_LAUNCH(beta_int);
+DANN_DECL_LAUNCH(beta_sph);
+DANN_DECL_LAUNCH(beta_mm);
+DANN_DECL_LAUNCH(beta_mmq);
 #undef DANN_DECL_LAUNCH
 int32_t launch_search_pqlut(const SearchArgs& a, size_t lds, hipStream_t stream);  // search_pqlut.hip (SearchArgs::pqlut)
 int32_t launch_search_pqlut_g1(const SearchArgs& a, size_t lds, hipStream_t stream);

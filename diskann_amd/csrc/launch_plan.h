@@ -171,13 +171,14 @@ inline int search_family(const SearchArgs& a) {
 
 inline uint64_t calib_key(const SearchArgs& a) {
     return ((uint64_t)a.l_value << 32) | ((uint64_t)a.beam_width << 8) | (a.rec_ids ? 1u : 0u) | (a.range_ids ? 2u : 0u) |
-           (a.filter_mode << 2);
+           (a.filter_mode << 2) | (a.beta_on ? 16u : 0u);
 }
 
 // dann_set_max_concurrency: `max_concurrency` persistent waves share the batch through a counter in the zeroed pad words
-// behind the spill pool -- never teams, pairs or the PQ table kernel: those launch one block per query (pair)
+// behind the spill pool -- never teams, pairs or the PQ table kernel: those launch one block per query (pair).  The
+// kernels with a persistent loop: the plain-mode ones and the beta search's.
 inline bool launch_capped(const SearchArgs& a, const LaunchKnobs& k) {
-    return k.max_concurrency && a.nq > k.max_concurrency && plain_mode(a);
+    return k.max_concurrency && a.nq > k.max_concurrency && (plain_mode(a) || beta_mode(a));
 }
 inline void cap_grid(SearchArgs& x, const LaunchKnobs& k) {
     const bool capped = launch_capped(x, k);

@@ -87,9 +87,12 @@ DANN_HD inline SearchLds search_lds_layout(uint32_t ht_entries, uint32_t cmax, u
 
 // what kModePlain assumes (checked by the host for every launch)
 inline bool plain_mode(const SearchArgs& a) {
-    return !a.filter_mode && a.beam_width == 1 && a.ix.tag_off == 0 && a.ix.max_degree <= (uint32_t)kWave &&
+    return !a.filter_mode && !a.beta_on && a.beam_width == 1 && a.ix.tag_off == 0 && a.ix.max_degree <= (uint32_t)kWave &&
            a.ix.nstart <= (uint32_t)kWave;
 }
+// a beta search (SearchArgs::beta_on) has one kernel, beam_search_beta_kernel: one wave per query or persistent waves.
+// Not plain_mode, so no team, pair, PQ-table-in-registers or 16-bit-table launch is ever planned for it.
+inline bool beta_mode(const SearchArgs& a) { return a.beta_on != 0; }
 
 // does a team instantiation exist for this launch?  (launch_one: plain mode, a fixed-length kernel -- 128-element rows
 // of the metric's specialised form --, at most 256 queue entries, not PQ rows; row_dispatch.h search_dim128_defined)

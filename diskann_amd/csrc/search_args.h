@@ -143,6 +143,10 @@ struct SearchArgs {
                                      //    visited table; plain Knn, <= 64 chunks, L + start points <= 256)
     uint32_t pair = 0;               // 1: two queries per wavefront (search_pair_impl.h; 128-byte integer rows, L + start
                                      //    points <= 96, degree <= 64); ht_entries = table words of ONE query then
+    // BetaFilter (layers/betafilter.rs; dann_beta_search_batch): the Knn search over distances multiplied by `beta` for the
+    // ids whose bit is set in `filter` (filter_stride as above; filter_mode stays 0).  beam_search_beta_kernel only.
+    uint32_t beta_on = 0;
+    float beta = 1.f;
 };
 
 // per (L, beam, mode) sizing state of the LDS visited table: cap_ids = 90th percentile of the

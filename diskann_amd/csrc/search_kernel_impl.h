@@ -1010,12 +1010,25 @@ __device__ __forceinline__ void team_helper(const SearchArgs& a, uint8_t* smem) 
     __syncthreads();  // the release
 }
 
-enum : int { kModePlain = 0, kModeGeneral = 1, kModeFiltered = 2 };
+//   kModeBeta     kModeGeneral with BetaFilter's scaling (layers/betafilter.rs) where a distance is produced: every
+//                 candidate's bitmap word is requested together with its row, and the lane that holds the row's
+//                 finished distance applies beta_apply before the value reaches the candidate buffer -- start points
+//                 and hops alike (both go through `gather`).  Generic-length instantiations only, made by
+//                 search_beta_impl.h (beam_search_beta_kernel); no other unit instantiates it.
+enum : int { kModePlain = 0, kModeGeneral = 1, kModeFiltered = 2, kModeBeta = 3 };
+// Filter::apply (betafilter.rs): d * beta for an id whose bit is set in `w`, its word of the bitmap, else d.  One f32
+// multiply with a rounding of its own (__fmul_rn is never contracted into a neighbouring operation), then one select.
+__device__ __forceinline__ float beta_apply(float d, uint32_t w, uint32_t id, float beta) {
+    const float scaled = __fmul_rn(d, beta);
+    return ((w >> (id & 31u)) & 1u) ? scaled : d;
+}
 // TEAM > 1: this is the queue wave of a team (see team_control_wave)
 template <int DT, int OP, bool NORM, int QS, int DIM, int MODE, int TEAM = 1, bool HT16 = false>
 __device__ __forceinline__ void beam_search_one(const SearchArgs& a, const uint32_t slot, uint8_t* smem) {
     constexpr bool FILT = MODE == kModeFiltered;
     constexpr bool PLAIN = MODE == kModePlain;
+    constexpr bool BETA = MODE == kModeBeta;
+    static_assert(!BETA || (DIM == 0 && TEAM == 1 && !HT16), "the beta search has generic-length one-wave kernels only");
     static_assert(TEAM == 1 || (PLAIN && DIM > 0), "teams serve the plain fixed-length searches");
     static_assert(TEAM == 1 || !HT16, "teams keep the 32-bit visited table (their rollback works on its slots)");
     // synchronisation of this wave with itself (LDS written by some lanes, read by others): the workgroup barrier of a
@@ -1305,8 +1318,12 @@ __device__ __forceinline__ void beam_search_one(const SearchArgs& a, const uint3
             // added in chunk order in f32; code rows read 16 bytes at a time
             const float* lut = reinterpret_cast<const float*>(qs);
             for (uint32_t c = lane; c < nc; c += kWave) {
-                const uint8_t* code = ix.rows + (uint64_t)cand_id[c] * ix.row_stride;
+                const uint32_t id = cand_id[c];
+                const uint8_t* code = ix.rows + (uint64_t)id * ix.row_stride;
                 const uint8_t tg = tag_off ? code[tag_off] : (uint8_t)255;
+                uint32_t bword = 0;  // (BETA) the candidate's bitmap word, in flight with its code row
+                if constexpr (BETA) bword = fbits[id >> 5];
+                (void)bword;
                 float accum = 0.0f;
                 for (uint32_t b0 = 0; b0 < ix.pq_chunks; b0 += 16) {
                     const uint4 w = *reinterpret_cast<const uint4*>(code + b0);
@@ -1317,6 +1334,7 @@ __device__ __forceinline__ void beam_search_one(const SearchArgs& a, const uint3
                         if (ch < ix.pq_chunks) accum += lut[ch * 256u + ((ws[i >> 2] >> (8 * (i & 3))) & 255u)];
                     }
                 }
+                if constexpr (BETA) accum = beta_apply(accum, bword, id, a.beta);
                 cand_d[c] = accum;
                 if (tg < kTagPublished) cand_id[c] = kEmpty;
             }
@@ -1326,12 +1344,21 @@ __device__ __forceinline__ void beam_search_one(const SearchArgs& a, const uint3
                 const uint8_t* rows[U];
                 bool act[U];
                 float out[U];
+                // (BETA) the candidates' ids and bitmap words: the word is requested here, with the row gather -- an
+                // unconditional load, a lane without a candidate reads word 0 -- and used once, by the lane that
+                // finishes the row's distance
+                uint32_t bid[U], bword[U];
+                (void)bid, (void)bword;
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     uint32_t c = c0 + u * GROUPS + g;
                     act[u] = c < nc;
                     uint32_t id = act[u] ? cand_id[c] : 0u;
                     rows[u] = ix.rows + (uint64_t)id * ix.row_stride;
+                    if constexpr (BETA) {
+                        bid[u] = id;
+                        bword[u] = fbits[id >> 5];
+                    }
                 }
                 uint8_t tg[U];
                 if (tag_off) {
@@ -1343,8 +1370,9 @@ __device__ __forceinline__ void beam_search_one(const SearchArgs& a, const uint3
                 for (int u = 0; u < U; ++u) {
                     uint32_t c = c0 + u * GROUPS + g;
                     if (act[u] && v == 0) {
-                        cand_d[c] = finish_distance<DT, OP, NORM>(out[u], reinterpret_cast<const uint8_t*>(qs), rows[u],
-                                                                  ix.dim, sqp);
+                        float d = finish_distance<DT, OP, NORM>(out[u], reinterpret_cast<const uint8_t*>(qs), rows[u], ix.dim, sqp);
+                        if constexpr (BETA) d = beta_apply(d, bword[u], bid[u], a.beta);
+                        cand_d[c] = d;
                         if (tag_off && tg[u] < kTagPublished) cand_id[c] = kEmpty;
                     }
                 }

@@ -33,6 +33,16 @@ __global__ void cmps_hist_kernel(const dann_search_stats* stats, uint32_t n, uin
         if (h[i]) atomicAdd(&hist[i], h[i]);
 }
 
+// the beta search's kernels, by the unit that holds the row type's instantiations (search_beta_impl.h)
+static int32_t launch_search_beta(const SearchArgs& a, uint32_t qcap, size_t lds, hipStream_t stream, int* regs_out) {
+    const int dt = a.ix.dtype;
+    if (dt == DT_F32 || dt == DT_F16 || dt == DT_PQ) return launch_search_beta_float(a, qcap, lds, stream, regs_out);
+    if (dt_is_mmq(dt)) return launch_search_beta_mmq(a, qcap, lds, stream, regs_out);
+    if (dt_is_mm(dt)) return launch_search_beta_mm(a, qcap, lds, stream, regs_out);
+    if (dt_is_sph(dt) || dt == DT_SPH1T) return launch_search_beta_sph(a, qcap, lds, stream, regs_out);
+    return launch_search_beta_int(a, qcap, lds, stream, regs_out);  // (u8 / i8 / SQ; anything else is its "bad dtype")
+}
+
 int32_t launch_search(const SearchArgs& a, hipStream_t stream, int* regs_out) {
     if (a.nq == 0) return DANN_OK;
     if (a.l_value == 0 || a.beam_width == 0) {
@@ -54,6 +64,7 @@ int32_t launch_search(const SearchArgs& a, hipStream_t stream, int* regs_out) {
         set_error("per-query LDS footprint %zu B exceeds 160 KiB (visited table %u entries)", lds, a.ht_entries);
         return DANN_EOVERFLOW;
     }
+    if (a.beta_on) return launch_search_beta(a, qcap, lds, stream, regs_out);
     if (a.pqlut && !regs_out) return launch_search_pqlut(a, lds, stream);
     if (a.pair && !regs_out) return launch_search_pair(a, lds, stream);
     switch (a.ix.dtype) {

@@ -335,6 +335,21 @@ class Provider:
         del keep
         return ids, dists, stats
 
+    def beta_search(self, params, queries, k, match, beta, stats=True):
+        """BetaFilter (layers/betafilter.rs) for a batch: the Knn search over distances multiplied by `beta` where
+        `match` (as filtered_search takes it) is set; returns (ids, dists, stats), dists scaled; stats=False: None."""
+        q = np.ascontiguousarray(queries, dtype=self.query_np_dtype).reshape(-1, self.query_elems)
+        nq = q.shape[0]
+        f, keep = self._filter(0, match, nq)
+        ids = np.empty((nq, k), np.uint32)
+        dists = np.empty((nq, k), np.float32)
+        st = np.zeros(nq, STATS_DTYPE) if stats else None
+        check(_ffi.lib().dann_beta_search_batch(self._h, _p(q), nq, params.l_value, params.beam_width, k, f.bits,
+                                                f.stride_words, beta, _p(ids), _p(dists), _p(st) if stats else None),
+              "dann_beta_search_batch")
+        del keep
+        return ids, dists, st
+
     def filtered_range_search(self, queries, starting_l, radius, match, beam_width=1, inner_radius=None,
                               initial_slack=1.0, range_slack=1.0, max_returned=0, out_cap=None, matched_cap=0):
         """graph::search::FilteredRange for a batch; returns (ids, dists, stats, second_round)."""

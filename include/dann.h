@@ -310,6 +310,27 @@ int32_t dann_filtered_range_search_batch(dann_index* idx, const void* queries, u
                                          uint32_t max_returned, uint32_t out_cap, const dann_filter* filter,
                                          uint32_t* out_ids, float* out_dists, dann_search_stats* out_stats,
                                          uint32_t* out_second_round);
+/* ---- beta-filtered search: index.search(Knn{l_value, beam_width}, BetaFilter<Strategy>, ..) for nq queries
+ * (diskann-providers/src/model/graph/provider/layers/betafilter.rs).  The search is dann_search_batch's -- the same
+ * visited rule, queue order and tie rule, cmps / hops accounting (start points counted) and post-processing (start
+ * points dropped, inline tags honoured) -- over distances passed through Filter::apply: the index's own distance of an
+ * id, then one f32 multiply by `beta` if is_match(id).  Start points and expanded neighbours alike; negative
+ * (inner-product) distances are scaled all the same, so beta < 1 then pushes matches away.  out_dists holds the scaled
+ * values.  beta == 1 or a bitmap without a set bit give dann_search_batch's outputs bit for bit.
+ * The predicate is a bitmap as dann_filter's: is_match(i) = bit (i & 31) of bits[i >> 5] for i in [0, capacity +
+ * num_start_points); stride_words = words between the bitmaps of consecutive queries, 0 = one bitmap for all queries.
+ * Any non-NaN beta is taken (BetaFilter::new validates nothing); NaN, null bits, a stride shorter than one bitmap and
+ * l_value == 0 or beam_width == 0 are DANN_EINVAL; k is taken as dann_search_batch takes it.  Every row type and query
+ * layout dann_search_batch serves, DANN_PQ included.  One wave per query, or the persistent waves of
+ * dann_set_max_concurrency; dann_debug_search_families reports which.
+ * _device: queries, bits and outputs are device pointers on the index's device; d_out_stats may be null. */
+int32_t dann_beta_search_batch(dann_index* idx, const void* queries, uint32_t nq, uint32_t l_value, uint32_t beam_width,
+                               uint32_t k, const uint32_t* bits, uint64_t stride_words, float beta, uint32_t* out_ids,
+                               float* out_dists, dann_search_stats* out_stats);
+int32_t dann_beta_search_batch_device(dann_index* idx, const void* d_queries, uint32_t nq, uint32_t l_value,
+                                      uint32_t beam_width, uint32_t k, const uint32_t* d_bits, uint64_t stride_words,
+                                      float beta, uint32_t* d_out_ids, float* d_out_dists,
+                                      dann_search_stats* d_out_stats);
 
 /* ---- paged search: DiskANNIndex::paged_search + PagedSearch::next_page (diskann/src/graph/index.rs:2075-2155,
  * diskann/src/graph/search/paged.rs:53-149) for nq queries at once.  The session owns the reference's per-search
