@@ -191,6 +191,10 @@ SYMBOLS = {
     "dann_maxsim_batch_device": (_i32, [_vp, _i32, _vp, _vp, _u32, _vp, _u32, _vp, _vp]),
     "dann_chamfer_rerank_batch": (_i32, [_vp, _i32, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
     "dann_chamfer_rerank_batch_device": (_i32, [_vp, _i32, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "dann_projected_eigen_batch": (_i32, [_vp, _i32, _vp, _vp, _u32, _vp, _u32, _vp, _vp]),
+    "dann_projected_eigen_batch_device": (_i32, [_vp, _i32, _vp, _vp, _u32, _vp, _u32, _vp, _vp]),
+    "dann_projected_eigen_rerank_batch": (_i32, [_vp, _i32, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "dann_projected_eigen_rerank_batch_device": (_i32, [_vp, _i32, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
     "dann_mv_flat_search_batch": (_i32, [_vp, _i32, _i32, _vp, _vp, _u32, _u32, _u32, _u32, _P(FlatFilter), _vp, _vp, _vp]),
     "dann_mv_flat_search_batch_device": (_i32, [_vp, _i32, _i32, _vp, _vp, _u32, _u32, _u32, _u32, _P(FlatFilter), _vp, _vp,
                                                 _vp]),

@@ -19,7 +19,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # after that was seen keeps them out (what it costs the reference-order kernel).  The units written before
 # keep their flags: their bits are pinned by their own tests.
 _NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-UNIT_FLAGS = {"maxsim_flat_kernels.hip": _NO_PACKED_F32}
+UNIT_FLAGS = {"maxsim_flat_kernels.hip": _NO_PACKED_F32, "projected_eigen_kernels.hip": _NO_PACKED_F32}
 # (the beta search's units, search_beta_<rows>.hip: its one multiply is a rounding of its own)
 UNIT_FLAGS.update({s: _NO_PACKED_F32 for s in SOURCES if s.startswith("search_beta_")})
 HEARTBEAT_S = 60  # a progress line at least this often while objects compile

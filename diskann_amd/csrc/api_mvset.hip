@@ -1,5 +1,5 @@
-// api_mvset.hip -- multi-vector sets (maxsim_kernels.hip): dann_mvset_*, dann_maxsim_* and dann_chamfer_* of
-// include/dann.h.  A set never touches a dann_index.
+// api_mvset.hip -- multi-vector sets (maxsim_kernels.hip, projected_eigen_kernels.hip): dann_mvset_*, dann_maxsim_*,
+// dann_chamfer_* and dann_projected_eigen_* of include/dann.h.  A set never touches a dann_index.
 // Rows are kept at a stride of whole 16-byte units with the tail zeroed -- the layout the kernels stage from -- and the
 // queries of a call are brought to the same stride on their way to the device.  MinMax sets (maxsim_mm_kernels.hip): the
 // rows are canonical images on the way in; the device keeps their packed codes at such a stride and a header record per row.
@@ -160,14 +160,28 @@ int32_t mv_prepare(const dann_mvset* s, int32_t order, const void* queries, cons
     return DANN_OK;
 }
 
+// the distance a scoring call sums up: MaxSim scores into their Chamfer sum, or ProjectedEigen (projected_eigen_kernels.hip)
+enum MvDistance { MV_MAXSIM, MV_PROJECTED_EIGEN };
+
+// is the distance defined on the set?
+int32_t mv_check_set(const dann_mvset* s, MvDistance dist) {
+    if (dist == MV_PROJECTED_EIGEN && dt_is_mm(s->dtype)) {  // (the reference defines it on Standard<T> matrices only)
+        set_error("ProjectedEigen is not defined on MinMax sets (dtype %d); DANN_F32 and DANN_F16 sets are served", s->dtype);
+        return DANN_EUNSUPPORTED;
+    }
+    return DANN_OK;
+}
+
 // launch, wait, and turn the device's bounds check into the status
-int32_t mv_score(const dann_mvset* s, int32_t order, MvCall& c, uint32_t nq, float* d_chamfer, float* d_scores) {
+int32_t mv_score(const dann_mvset* s, MvDistance dist, int32_t order, MvCall& c, uint32_t nq, float* d_chamfer,
+                 float* d_scores) {
     c.a.out_chamfer = d_chamfer;
     c.a.out_scores = d_scores;
     std::lock_guard<std::mutex> lk(s->clock_mu);
     DANN_HIP(hipEventRecord(s->ev0, nullptr));
-    if (int32_t rc = dt_is_mm(s->dtype) ? launch_maxsim_mm(c.qdtype, s->dtype, order, c.a, nq, nullptr)
-                                        : launch_maxsim(s->dtype, order, c.a, nq, nullptr))
+    if (int32_t rc = dist == MV_PROJECTED_EIGEN ? launch_projected_eigen(s->dtype, order, c.a, nq, nullptr)
+                     : dt_is_mm(s->dtype)       ? launch_maxsim_mm(c.qdtype, s->dtype, order, c.a, nq, nullptr)
+                                                : launch_maxsim(s->dtype, order, c.a, nq, nullptr))
         return rc;
     DANN_HIP(hipEventRecord(s->ev1, nullptr));
     uint32_t st = 0;
@@ -183,29 +197,32 @@ int32_t mv_score(const dann_mvset* s, int32_t order, MvCall& c, uint32_t nq, flo
     return DANN_OK;
 }
 
-int32_t mv_maxsim(const dann_mvset* s, int32_t order, const void* queries, const uint32_t* q_offsets, uint32_t nq,
-                  const uint32_t* cand, uint32_t cand_stride, float* out_chamfer, float* out_scores, bool on_device) {
+int32_t mv_maxsim(const dann_mvset* s, MvDistance dist, int32_t order, const void* queries, const uint32_t* q_offsets,
+                  uint32_t nq, const uint32_t* cand, uint32_t cand_stride, float* out_chamfer, float* out_scores,
+                  bool on_device) {
     if (!s || !out_chamfer) return DANN_EINVAL;
+    if (int32_t rc = mv_check_set(s, dist)) return rc;
     DeviceGuard dev(s->device);
     if (!dev.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
     MvCall c;
     if (int32_t rc = mv_prepare(s, order, queries, q_offsets, nq, cand, cand_stride, on_device, c)) return rc;
     if (nq == 0) return DANN_OK;
-    if (on_device) return mv_score(s, order, c, nq, out_chamfer, out_scores);
+    if (on_device) return mv_score(s, dist, order, c, nq, out_chamfer, out_scores);
     const size_t cb = (size_t)nq * cand_stride * 4, sb = (size_t)c.qrows_total * cand_stride * 4;
     DevBuf bc, bs;
     DANN_HIP(bc.alloc(cb));
     if (out_scores) DANN_HIP(bs.alloc(sb));
-    if (int32_t rc = mv_score(s, order, c, nq, bc.as<float>(), out_scores ? bs.as<float>() : nullptr)) return rc;
+    if (int32_t rc = mv_score(s, dist, order, c, nq, bc.as<float>(), out_scores ? bs.as<float>() : nullptr)) return rc;
     DANN_HIP(hipMemcpy(out_chamfer, bc.p, cb, hipMemcpyDeviceToHost));
     if (out_scores && sb) DANN_HIP(hipMemcpy(out_scores, bs.p, sb, hipMemcpyDeviceToHost));
     return DANN_OK;
 }
 
-int32_t mv_rerank(const dann_mvset* s, int32_t order, const void* queries, const uint32_t* q_offsets, uint32_t nq,
-                  const uint32_t* cand, uint32_t cand_stride, uint32_t k, uint32_t* out_ids, float* out_dists,
+int32_t mv_rerank(const dann_mvset* s, MvDistance dist, int32_t order, const void* queries, const uint32_t* q_offsets,
+                  uint32_t nq, const uint32_t* cand, uint32_t cand_stride, uint32_t k, uint32_t* out_ids, float* out_dists,
                   uint32_t* out_counts, bool on_device) {
     if (!s || !out_ids || !out_dists || !out_counts || k == 0) return DANN_EINVAL;
+    if (int32_t rc = mv_check_set(s, dist)) return rc;
     DeviceGuard dev(s->device);
     if (!dev.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
     MvCall c;
@@ -213,7 +230,7 @@ int32_t mv_rerank(const dann_mvset* s, int32_t order, const void* queries, const
     if (nq == 0) return DANN_OK;
     DevBuf bc, bi, bd, bn;
     DANN_HIP(bc.alloc((size_t)nq * cand_stride * 4));
-    if (int32_t rc = mv_score(s, order, c, nq, bc.as<float>(), nullptr)) return rc;
+    if (int32_t rc = mv_score(s, dist, order, c, nq, bc.as<float>(), nullptr)) return rc;
     const size_t ob = (size_t)nq * k * 4;
     uint32_t* d_ids = out_ids;
     float* d_d = out_dists;
@@ -463,27 +480,60 @@ int32_t dann_debug_mvset_kernel_time(const dann_mvset* set, int32_t reset, doubl
 int32_t dann_maxsim_batch(const dann_mvset* set, int32_t order, const void* queries, const uint32_t* q_offsets,
                           uint32_t nq, const uint32_t* cand_ids, uint32_t cand_stride, float* out_chamfer,
                           float* out_scores) try {
-    return mv_maxsim(set, order, queries, q_offsets, nq, cand_ids, cand_stride, out_chamfer, out_scores, false);
+    return mv_maxsim(set, MV_MAXSIM, order, queries, q_offsets, nq, cand_ids, cand_stride, out_chamfer, out_scores,
+                     false);
 } DANN_CATCH_ALL
 
 int32_t dann_maxsim_batch_device(const dann_mvset* set, int32_t order, const void* d_queries, const uint32_t* d_q_offsets,
                                  uint32_t nq, const uint32_t* d_cand_ids, uint32_t cand_stride, float* d_out_chamfer,
                                  float* d_out_scores) try {
-    return mv_maxsim(set, order, d_queries, d_q_offsets, nq, d_cand_ids, cand_stride, d_out_chamfer, d_out_scores, true);
+    return mv_maxsim(set, MV_MAXSIM, order, d_queries, d_q_offsets, nq, d_cand_ids, cand_stride, d_out_chamfer,
+                     d_out_scores, true);
 } DANN_CATCH_ALL
 
 int32_t dann_chamfer_rerank_batch(const dann_mvset* set, int32_t order, const void* queries, const uint32_t* q_offsets,
                                   uint32_t nq, const uint32_t* cand_ids, uint32_t cand_stride, uint32_t k,
                                   uint32_t* out_ids, float* out_dists, uint32_t* out_counts) try {
-    return mv_rerank(set, order, queries, q_offsets, nq, cand_ids, cand_stride, k, out_ids, out_dists, out_counts, false);
+    return mv_rerank(set, MV_MAXSIM, order, queries, q_offsets, nq, cand_ids, cand_stride, k, out_ids, out_dists,
+                     out_counts, false);
 } DANN_CATCH_ALL
 
 int32_t dann_chamfer_rerank_batch_device(const dann_mvset* set, int32_t order, const void* d_queries,
                                          const uint32_t* d_q_offsets, uint32_t nq, const uint32_t* d_cand_ids,
                                          uint32_t cand_stride, uint32_t k, uint32_t* d_out_ids, float* d_out_dists,
                                          uint32_t* d_out_counts) try {
-    return mv_rerank(set, order, d_queries, d_q_offsets, nq, d_cand_ids, cand_stride, k, d_out_ids, d_out_dists,
+    return mv_rerank(set, MV_MAXSIM, order, d_queries, d_q_offsets, nq, d_cand_ids, cand_stride, k, d_out_ids, d_out_dists,
                      d_out_counts, true);
+} DANN_CATCH_ALL
+
+int32_t dann_projected_eigen_batch(const dann_mvset* set, int32_t order, const void* queries, const uint32_t* q_offsets,
+                                   uint32_t nq, const uint32_t* cand_ids, uint32_t cand_stride, float* out_dist,
+                                   float* out_scores) try {
+    return mv_maxsim(set, MV_PROJECTED_EIGEN, order, queries, q_offsets, nq, cand_ids, cand_stride, out_dist, out_scores,
+                     false);
+} DANN_CATCH_ALL
+
+int32_t dann_projected_eigen_batch_device(const dann_mvset* set, int32_t order, const void* d_queries,
+                                          const uint32_t* d_q_offsets, uint32_t nq, const uint32_t* d_cand_ids,
+                                          uint32_t cand_stride, float* d_out_dist, float* d_out_scores) try {
+    return mv_maxsim(set, MV_PROJECTED_EIGEN, order, d_queries, d_q_offsets, nq, d_cand_ids, cand_stride, d_out_dist,
+                     d_out_scores, true);
+} DANN_CATCH_ALL
+
+int32_t dann_projected_eigen_rerank_batch(const dann_mvset* set, int32_t order, const void* queries,
+                                          const uint32_t* q_offsets, uint32_t nq, const uint32_t* cand_ids,
+                                          uint32_t cand_stride, uint32_t k, uint32_t* out_ids, float* out_dists,
+                                          uint32_t* out_counts) try {
+    return mv_rerank(set, MV_PROJECTED_EIGEN, order, queries, q_offsets, nq, cand_ids, cand_stride, k, out_ids, out_dists,
+                     out_counts, false);
+} DANN_CATCH_ALL
+
+int32_t dann_projected_eigen_rerank_batch_device(const dann_mvset* set, int32_t order, const void* d_queries,
+                                                 const uint32_t* d_q_offsets, uint32_t nq, const uint32_t* d_cand_ids,
+                                                 uint32_t cand_stride, uint32_t k, uint32_t* d_out_ids, float* d_out_dists,
+                                                 uint32_t* d_out_counts) try {
+    return mv_rerank(set, MV_PROJECTED_EIGEN, order, d_queries, d_q_offsets, nq, d_cand_ids, cand_stride, k, d_out_ids,
+                     d_out_dists, d_out_counts, true);
 } DANN_CATCH_ALL
 
 int32_t dann_mv_flat_search_batch(const dann_mvset* set, int32_t order, int32_t aggregation, const void* queries,

@@ -245,6 +245,9 @@ struct MaxSimArgs {
     uint32_t* status;          // set to 1 by a candidate id >= ndocs
 };
 int32_t launch_maxsim(int32_t dtype, int32_t order, const MaxSimArgs& a, uint32_t nq, hipStream_t stream);
+// projected_eigen_kernels.hip: the ProjectedEigen distance over an f32 / f16 set, same arguments (out_chamfer takes the
+// totals, out_scores the per-row sums)
+int32_t launch_projected_eigen(int32_t dtype, int32_t order, const MaxSimArgs& a, uint32_t nq, hipStream_t stream);
 // maxsim_mm_kernels.hip.  MinMax images (d_images: nrows x image_bytes, any alignment) -> zero-padded codes at `stride`
 // and header records; and the scores of a (query width, row width) pair the reference has.
 int32_t launch_mm_repack(int32_t dtype, const uint8_t* d_images, uint32_t image_bytes, uint64_t nrows, uint32_t dim,

@@ -25,8 +25,9 @@ struct MsPair {
 };
 
 // Skipped candidates (0xFFFFFFFF) and ids >= ndocs write +infinity (the latter also raise the status word: DANN_EBOUNDS
-// on the host -- an argument check INSTEAD of the read); an empty document writes f32::MAX scores and Chamfer 0.0.
-__device__ __forceinline__ MsPair ms_pair(const MaxSimArgs& a) {
+// on the host -- an argument check INSTEAD of the read); an empty document writes `empty_fill` scores (MaxSim: f32::MAX,
+// the minimum's start; ProjectedEigen: the +0.0 its sums start from) and total 0.0.
+__device__ __forceinline__ MsPair ms_pair(const MaxSimArgs& a, float empty_fill = FLT_MAX) {
     const uint32_t c = blockIdx.x, qi = blockIdx.y;
     const uint32_t q0 = a.qoff[qi], qn = a.qoff[qi + 1] - q0;
     MsPair p;
@@ -53,7 +54,7 @@ __device__ __forceinline__ MsPair ms_pair(const MaxSimArgs& a) {
             p.live = true;
             return p;
         }
-        fill = FLT_MAX;  // (qn == 0: no cell to fill)
+        fill = empty_fill;  // (qn == 0: no cell to fill)
         cham = 0.0f;
     }
     if (p.scores)

@@ -1,10 +1,11 @@
-"""Multi-vector (late-interaction) scoring: dann_mvset + dann_maxsim_batch / dann_chamfer_rerank_batch, and the exhaustive
-search over a whole set, dann_mv_flat_search_batch.
+"""Multi-vector (late-interaction) scoring: dann_mvset + dann_maxsim_batch / dann_chamfer_rerank_batch /
+dann_projected_eigen_batch, and the exhaustive search over a whole set, dann_mv_flat_search_batch.
 
 A document and a query are small matrices of token rows.  MaxSim: per query row, the best inner product over the document's
 rows, as a similarity score (negated); Chamfer: their sum over the query's rows.  `order` picks whose bits come back
 (include/dann.h): MAXSIM_KERNEL = MaxSimKernel::compute_max_sim (matrix cores), MAXSIM_REFERENCE = MaxSim::evaluate /
-Chamfer::evaluate (the pair distance function).
+Chamfer::evaluate (the pair distance function).  ProjectedEigen: the sum over every query row x document row pair of
+-(inner product squared), in row order; the same two orders pick how each inner product is summed.
 
 MinMax-quantised sets (MM1 / MM2 / MM4 / MM8, diskann-quantization/src/minmax/multi/): documents and queries are
 (rows, dann_layer_bytes(dtype, dim)) uint8 matrices of canonical images, as dann_minmax_compress writes them; `dim` must be
@@ -107,34 +108,52 @@ class MultiVectorSet:
             raise ValueError("cand_ids is (candidates,) or (queries, candidates)")
         return qoff, qrows, cand
 
-    def maxsim(self, queries, cand_ids, order=MAXSIM_KERNEL, per_row=False):
-        """Chamfer scores (len(queries) x candidates) of each query against its candidates; skipped entries (SKIP) are
-        +inf.  per_row=True also returns the MaxSim scores: a list with one (candidates x rows(q)) array per query."""
+    def _score(self, fn, queries, cand_ids, order, per_row):
+        """one of the scoring calls (dann_maxsim_batch's signature): the totals, with per_row also the per-row scores"""
         qoff, qrows, cand = self._call_args(queries, cand_ids)
         nq, stride = cand.shape
-        chamfer = np.empty((nq, stride), np.float32)
+        total = np.empty((nq, stride), np.float32)
         scores = np.empty(int(qoff[-1]) * stride, np.float32) if per_row else None
-        check(lib().dann_maxsim_batch(self._h, order, _vp(qrows), _vp(qoff), nq, _vp(cand), stride, _vp(chamfer),
-                                      _vp(scores) if per_row else None), "dann_maxsim_batch")
+        check(getattr(lib(), fn)(self._h, order, _vp(qrows), _vp(qoff), nq, _vp(cand), stride, _vp(total),
+                                 _vp(scores) if per_row else None), fn)
         if not per_row:
-            return chamfer
+            return total
         out = []
         for q in range(nq):
             lo, n = int(qoff[q]), int(qoff[q + 1] - qoff[q])
             out.append(scores[lo * stride:(lo + n) * stride].reshape(stride, n))
-        return chamfer, out
+        return total, out
 
-    def chamfer_rerank(self, queries, cand_ids, k, order=MAXSIM_KERNEL):
-        """(ids, Chamfer scores, counts): per query its candidates by ascending Chamfer score, equal scores in candidate
-        order, the first k (padded with SKIP / +inf); counts[q] = entries written."""
+    def _rerank(self, fn, queries, cand_ids, k, order):
+        """one of the rerank calls (dann_chamfer_rerank_batch's signature)"""
         qoff, qrows, cand = self._call_args(queries, cand_ids)
         nq, stride = cand.shape
         ids = np.empty((nq, k), np.uint32)
         dists = np.empty((nq, k), np.float32)
         counts = np.empty(nq, np.uint32)
-        check(lib().dann_chamfer_rerank_batch(self._h, order, _vp(qrows), _vp(qoff), nq, _vp(cand), stride, k, _vp(ids),
-                                              _vp(dists), _vp(counts)), "dann_chamfer_rerank_batch")
+        check(getattr(lib(), fn)(self._h, order, _vp(qrows), _vp(qoff), nq, _vp(cand), stride, k, _vp(ids), _vp(dists),
+                                 _vp(counts)), fn)
         return ids, dists, counts
+
+    def maxsim(self, queries, cand_ids, order=MAXSIM_KERNEL, per_row=False):
+        """Chamfer scores (len(queries) x candidates) of each query against its candidates; skipped entries (SKIP) are
+        +inf.  per_row=True also returns the MaxSim scores: a list with one (candidates x rows(q)) array per query."""
+        return self._score("dann_maxsim_batch", queries, cand_ids, order, per_row)
+
+    def chamfer_rerank(self, queries, cand_ids, k, order=MAXSIM_KERNEL):
+        """(ids, Chamfer scores, counts): per query its candidates by ascending Chamfer score, equal scores in candidate
+        order, the first k (padded with SKIP / +inf); counts[q] = entries written."""
+        return self._rerank("dann_chamfer_rerank_batch", queries, cand_ids, k, order)
+
+    def projected_eigen(self, queries, cand_ids, order=MAXSIM_KERNEL, per_row=False):
+        """ProjectedEigen distances (len(queries) x candidates): the sum over every query row x document row pair of
+        -(inner product squared), both sums sequential in row order; F32 / F16 sets.  Skipped entries (SKIP) are +inf.
+        per_row=True also returns each query row's sum over the document's rows, laid out as maxsim's scores."""
+        return self._score("dann_projected_eigen_batch", queries, cand_ids, order, per_row)
+
+    def projected_eigen_rerank(self, queries, cand_ids, k, order=MAXSIM_KERNEL):
+        """chamfer_rerank over the ProjectedEigen distances"""
+        return self._rerank("dann_projected_eigen_rerank_batch", queries, cand_ids, k, order)
 
     def _flat_filter(self, match, nq):
         """dann_flat_filter of a bool array over the documents (shared) or nq x ndocs (per query); keep `bits` alive"""

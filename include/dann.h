@@ -1046,6 +1046,39 @@ int32_t dann_chamfer_rerank_batch_device(const dann_mvset* set, int32_t order, c
                                          const uint32_t* d_q_offsets, uint32_t nq, const uint32_t* d_cand_ids,
                                          uint32_t cand_stride, uint32_t k, uint32_t* d_out_ids, float* d_out_dists,
                                          uint32_t* d_out_counts);
+/* ProjectedEigen (multi_vector/distance/projected_eigen.rs; FallbackKernel::projected_eigen_kernel, fallback.rs:105-147,
+ * 207-226): every query row x document row pair contributes.
+ *   score[i]             = sum over the document's rows j = 0 .. d_rows - 1, in row order, of -(ip(i, j) * ip(i, j))
+ *   ProjectedEigen(Q, D) = sum over the query's rows i, in row order, of score[i]
+ * Both are sequential f32 sums from +0.0, and every f32 operation rounds on its own: the multiply, the add (no fma).
+ * Sets: DANN_F32 and DANN_F16, queries in the set's dtype and CSR as for dann_maxsim_batch; a MinMax set answers
+ * DANN_EUNSUPPORTED (the reference defines the distance on Standard<T> matrices only).  Only ip(i, j) depends on `order`:
+ *   DANN_MAXSIM_REFERENCE  ip = InnerProduct::evaluate(q_i, d_j), the pair function behind dann_distance_pairs: the
+ *                          reference's ProjectedEigen::evaluate, bit for bit.
+ *   DANN_MAXSIM_KERNEL     ip = one fma chain over k = 0 .. dim - 1 from +0.0 (f16 widened first, exactly), as
+ *                          v_mfma_f32_32x32x2_f32 produces it.  The reference has no SIMD kernel for this distance: this
+ *                          order is this library's own, the matrix-core form of the same two sums.
+ * Both: a document without rows has ProjectedEigen +0.0 (the reference's callback never runs) and per-row cells +0.0; a
+ * query without rows has ProjectedEigen +0.0; a skipped candidate (0xFFFFFFFF) writes +infinity cells.  A result is never
+ * -0.0 (s + -0.0 == s for every s, +0.0 included).
+ * out_dist: nq x cand_stride.  out_scores: NULL, or score[i] per row in the layout of dann_maxsim_batch's out_scores.
+ * Limits and errors are those of dann_maxsim_batch, in the same order, with DANN_EUNSUPPORTED for a MinMax set right after
+ * the null checks of the set and the outputs.  The rerank forms are dann_chamfer_rerank_batch over these distances.
+ * Outside the contract: NaN or infinite inputs, and ip * ip that overflows. */
+int32_t dann_projected_eigen_batch(const dann_mvset* set, int32_t order, const void* queries, const uint32_t* q_offsets,
+                                   uint32_t nq, const uint32_t* cand_ids, uint32_t cand_stride, float* out_dist,
+                                   float* out_scores);
+int32_t dann_projected_eigen_batch_device(const dann_mvset* set, int32_t order, const void* d_queries,
+                                          const uint32_t* d_q_offsets, uint32_t nq, const uint32_t* d_cand_ids,
+                                          uint32_t cand_stride, float* d_out_dist, float* d_out_scores);
+int32_t dann_projected_eigen_rerank_batch(const dann_mvset* set, int32_t order, const void* queries,
+                                          const uint32_t* q_offsets, uint32_t nq, const uint32_t* cand_ids,
+                                          uint32_t cand_stride, uint32_t k, uint32_t* out_ids, float* out_dists,
+                                          uint32_t* out_counts);
+int32_t dann_projected_eigen_rerank_batch_device(const dann_mvset* set, int32_t order, const void* d_queries,
+                                                 const uint32_t* d_q_offsets, uint32_t nq, const uint32_t* d_cand_ids,
+                                                 uint32_t cand_stride, uint32_t k, uint32_t* d_out_ids, float* d_out_dists,
+                                                 uint32_t* d_out_counts);
 /* Exhaustive multi-vector k-NN: the reference's compute_multivec_ground_truth_from_data (diskann-tools/src/utils/
  * ground_truth.rs:696-787, the compute_multivec_groundtruth tool) for nq queries over the documents
  * [first_doc, first_doc + n) of a set.
